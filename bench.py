@@ -16,11 +16,20 @@ halo exchange over RCCL inside libekpnp.so (ekpnp_slab_attach_comm); torch.distr
 the control plane only: rendezvous, barrier, max over ranks.
 
 One JSON line on rank 0.  `value` counts lattice-node updates of all ranks per wall second of
-the timed region (inputs resident in HBM, barrier + device sync on both sides, max over ranks).
+the timed region (inputs resident in HBM, barrier + device sync on both sides, max over ranks);
+`ms_per_step` is the wall time of one timed step, `--steps` of them are timed.
 `roofline` is for the dominant kernel (the fused pull-stream/collide bulk kernel): algorithmic
 bytes per launch / its mean launch duration measured with HIP events on the kernel's stream.
-`cpu_baseline` is the CPU oracle (test infrastructure, never the measured product) timed on the
-host cores on a bounded sample.
+
+A plain run sets up, warms up, times the steps and prints the line.  `--full` adds what runs after
+the timed region, outside `value`: the copy-bandwidth probe (`roofline.copy_GBps`), the
+batch_moments A/B (`config.batch_moments_ab`), the transport knob A/B of N>1 lines (`comm_ab`) and
+`cpu_baseline`, the CPU oracle (test infrastructure, never the measured product) timed on the host
+cores on a bounded sample.
+
+`--dump-outputs DIR` writes the 11 fields the last timed step left (what Solver.get_field returns)
+as DIR/<field>.npy in float64: every node when all of them fit in 60 MB, else the same fixed,
+seeded sample of nodes of the global lattice (sorted flat indices, dump_sample_index) in every run.
 """
 from __future__ import annotations
 
@@ -430,6 +439,46 @@ def apply_perturbation(sol, O, p):
     sol.set_field("uz", 0.5e-4 * sZ**2 * np.cos(X) * np.cos(Y))
 
 
+DUMP_BUDGET_BYTES = 60_000_000  # --dump-outputs: the data of all files together
+DUMP_SEED = 20240917
+
+
+def dump_sample_index(grid_zyx, n_fields: int, budget: int = DUMP_BUDGET_BYTES, seed: int = DUMP_SEED):
+    """Sorted flat indices into the global (nz, ny, nx) lattice of the nodes --dump-outputs writes, or None for all of them
+    (when n_fields float64 arrays of the whole lattice fit the budget).  A function of the grid alone: every run, build and
+    rank count draws the same nodes."""
+    n = int(np.prod(grid_zyx))
+    k = budget // (8 * n_fields)
+    if n <= k:
+        return None
+    return np.unique(np.random.default_rng(seed).integers(0, n, size=k))
+
+
+def dump_part(sol, grid_zyx, fields):
+    """(z0, {field: values}) of one context: the nodes of dump_sample_index that lie in its planes, in index order"""
+    idx = dump_sample_index(grid_zyx, len(fields))
+    plane = grid_zyx[1] * grid_zyx[2]
+    lo, hi = sol.z0 * plane, (sol.z0 + sol.shape[0]) * plane
+    sel = None if idx is None else idx[(idx >= lo) & (idx < hi)] - lo
+    out = {}
+    for name in fields:
+        a = sol.get_field(name).reshape(-1)
+        out[name] = a if sel is None else a[sel]  # (a copy: the whole field is freed here)
+        del a
+    return sol.z0, out
+
+
+def write_dump(out_dir, parts, grid_zyx, fields):
+    """out_dir/<field>.npy (float64) from the parts of every context, put together in z order: the same arrays as one context
+    of the whole lattice would give (shaped (nz, ny, nx) when every node is written)"""
+    parts = sorted(parts, key=lambda t: t[0])
+    whole = dump_sample_index(grid_zyx, len(fields)) is None
+    os.makedirs(out_dir, exist_ok=True)
+    for name in fields:
+        a = np.concatenate([d[name] for _, d in parts]).astype(np.float64, copy=False)
+        np.save(os.path.join(out_dir, f"{name}.npy"), a.reshape(grid_zyx) if whole else a)
+
+
 def cpu_model() -> str:
     try:
         for line in open("/proc/cpuinfo"):
@@ -667,6 +716,13 @@ def main():
     ap.add_argument("--after-deadline", type=float, default=300.0, metavar="SECONDS",
                     help="what runs after the timed region (knob A/Bs, copy probe, CPU baseline) gets this long; then the measured line is printed "
                          "as it stands, marked, and every rank leaves (class HeadlineGuard).  0: no deadline")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the copy-bandwidth probe, the batch_moments A/B, the transport knob A/B (N>1 and "
+                         "--force-slab lines) and the CPU baseline (N=1); each can still be left out with its --no-* option.  Without it the "
+                         "run ends with the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step left - the 11 fields, every node or a fixed seeded sample of at most 60 MB in all - "
+                         "as DIR/<field>.npy (float64), before anything else runs")
     ap.add_argument("--dry-run", action="store_true", help="check the launch plumbing only: rendezvous, barrier, one JSON line with the workload that WOULD run; no GPU")
     ap.add_argument("--cpu-baseline-only", type=int, default=None, metavar="LATTICES", help="internal: time the CPU oracle and print its JSON (the child of cpu_baseline_in_child)")
     args = ap.parse_args()
@@ -943,6 +999,15 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
 
+    if args.dump_outputs:  # what the last timed step left, before anything else runs; every rank sends its planes to rank 0
+        part = dump_part(sol, (nz_global, ny, nx), pkg.FIELDS)
+        parts = [part]
+        if dist is not None:
+            parts = [None] * world
+            dist.all_gather_object(parts, part)
+        if rank == 0:
+            write_dump(args.dump_outputs, parts, (nz_global, ny, nx), pkg.FIELDS)
+        del part, parts
     rho = sol.get_field("rho")
     finite = bool(np.isfinite(rho).all())
     del rho
@@ -1067,7 +1132,7 @@ def main():
             print(f"bench.py: rank {rank}: after-the-fact leg '{name}' failed: {after_errors[name]}", file=sys.stderr)
             return None
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # secondary denominator: what a plain contiguous copy reaches on THIS device, now
         def copy_probe():
             free_now, _ = torch.cuda.mem_get_info()
@@ -1082,7 +1147,7 @@ def main():
     # The opt-in knob "batch_moments" (include/ekpnp.h) - inside one step(n) call only the last step stores rho, u, c, cn, T.
     # The HEADLINE never uses it (every step of the timed region stores them, as the reference's step does, LBM.cu:807-813);
     # this A/B says what a host that steps in batches between its outputs gets.
-    if not args.no_batch_ab and (native or not slab_path):
+    if args.full and not args.no_batch_ab and (native or not slab_path):
         n_ab = max(10, min(args.steps, 40))
 
         def timed_ms(n):
@@ -1116,7 +1181,7 @@ def main():
 
     # A few steps under each knob that one GPU cannot decide, on the live contexts (ekpnp_tune), so that ONE multi-GPU run
     # says which default is right on xGMI.  Every rank runs every leg.
-    if native and not args.no_comm_ab and args.comm_ab_steps > 0:
+    if args.full and native and not args.no_comm_ab and args.comm_ab_steps > 0:
         base = ab_baseline()
         comm_ab = []
         for label, knobs in COMM_AB_LEGS:
@@ -1129,7 +1194,7 @@ def main():
                 guard.update(out)
 
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             def cpu_leg():
                 runner.close()
                 return cpu_baseline_in_child(nl)

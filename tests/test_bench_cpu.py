@@ -7,6 +7,8 @@ import subprocess
 import sys
 import time
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -404,3 +406,46 @@ def test_more_ranks_than_devices_ends_every_rank_with_a_message():
     assert r.stderr.count("0 HIP device(s) visible for 2 ranks") == 2 and r.stderr.count("--single-device for a functional rehearsal") == 2, r.stderr[-3000:]
     assert "Traceback" not in r.stderr.split("failed (exitcode")[0]  # (the launcher prints its own ChildFailedError afterwards)
     assert r.stdout.strip() == ""
+
+
+def test_dump_sample_is_fixed_and_within_the_budget():
+    """--dump-outputs: every node of a small lattice; on a large one the same sorted, seeded sample in every run, at most
+    60 MB for the 11 float64 fields together"""
+    b = _bench()
+    assert b.dump_sample_index((40, 24, 32), 11) is None
+    a, a2 = b.dump_sample_index((512, 512, 512), 11), b.dump_sample_index((512, 512, 512), 11)
+    assert np.array_equal(a, a2) and np.all(np.diff(a) > 0) and a[0] >= 0 and a[-1] < 512**3
+    assert 0.9 * 60e6 / 88 < a.size and a.size * 88 <= 60e6
+    assert not np.array_equal(a[:1000], b.dump_sample_index((512, 512, 256), 11)[:1000])  # a function of the grid
+
+
+def test_dump_parts_of_slabs_make_the_whole_lattice(tmp_path):
+    """the parts of z slabs (any rank order) give the same files as one context of the whole lattice"""
+    b = _bench()
+    fields = ["rho", "phi", "ux"]
+    rng = np.random.default_rng(1)
+
+    class Ctx:
+        def __init__(self, data, z0, nz):
+            self.data, self.z0, self.shape = data, z0, (nz,) + data["rho"].shape[1:]
+            self.nz = nz
+
+        def get_field(self, name):
+            return self.data[name][self.z0:self.z0 + self.nz].copy()
+
+    for grid in ((6, 5, 4), (300, 200, 96)):  # every node / a sample (96x200x300 x 3 fields > 60 MB)
+        data = {k: rng.standard_normal(grid) for k in fields}
+        b.write_dump(tmp_path / "one", [b.dump_part(Ctx(data, 0, grid[0]), grid, fields)], grid, fields)
+        cuts = [0, grid[0] // 3, grid[0] // 3 + 1, grid[0]]
+        parts = [b.dump_part(Ctx(data, lo, hi - lo), grid, fields) for lo, hi in zip(cuts, cuts[1:])]
+        b.write_dump(tmp_path / "three", parts[::-1], grid, fields)
+        idx = b.dump_sample_index(grid, len(fields))
+        for k in fields:
+            one, three = np.load(tmp_path / "one" / f"{k}.npy"), np.load(tmp_path / "three" / f"{k}.npy")
+            assert one.dtype == np.float64 and np.array_equal(one, three)
+            assert np.array_equal(one, data[k] if idx is None else data[k].reshape(-1)[idx])
+
+
+def test_full_and_dump_outputs_options_exist():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout

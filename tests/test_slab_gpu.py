@@ -277,7 +277,7 @@ def test_bench_under_the_drivers_launcher_two_rccl_ranks(tmp_path):
     env.pop("HSA_ENABLE_IPC_MODE_LEGACY", None)  # bench.py must set it for the ranks of this launch mode by itself
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-           "--single-device", "--workload", "128x128x48", "--comm-ab-steps", "2"]
+           "--single-device", "--workload", "128x128x48", "--comm-ab-steps", "2", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-4000:]
     out = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -297,3 +297,73 @@ def test_bench_under_the_drivers_launcher_two_rccl_ranks(tmp_path):
     assert not [g for g in legs if "error" in g], legs
     assert d["config"]["batch_moments_ab"]["last_step_stores_ms_per_step"] > 0
     assert d["config"]["plane_transforms"]["ranks_on_device"] == 2
+
+
+def _bench_line(args, env=None, launcher=()):
+    r = subprocess.run([sys.executable, *launcher, os.path.join(ROOT, "bench.py"), *args], env=env or dict(os.environ, OMP_NUM_THREADS="1"),
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-4000:]
+    out = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(out) == 1, r.stdout[-2000:]
+    return json.loads(out[0])
+
+
+def _dumped(d):
+    return {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+
+
+def test_plain_bench_line_and_dump_outputs(pkg, tmp_path):
+    """A plain bench.py run times exactly --steps steps, prints the headline keys and none of what --full adds, and
+    --dump-outputs writes the 11 fields the last timed step left: the same bits in a second run, and the same values a
+    Solver driven through the bench's own start-up gives."""
+    shape = (32, 24, 40)
+    args = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "x".join(map(str, shape))]
+    d = _bench_line(args + ["--dump-outputs", str(tmp_path / "a")])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["config"]["finite"] is True
+    assert abs(d["value"] * d["ms_per_step"] - np.prod(shape) / 1e3) <= 1e-2 * np.prod(shape) / 1e3  # value and ms_per_step: one step
+    assert "cpu_baseline" not in d and "comm_ab" not in d and d["config"]["batch_moments_ab"] is None and d["roofline"]["copy_GBps"] is None
+    _bench_line(args + ["--dump-outputs", str(tmp_path / "b")])
+    a, b = _dumped(tmp_path / "a"), _dumped(tmp_path / "b")
+    assert sorted(a) == sorted(pkg.FIELDS)
+    for k in a:
+        assert a[k].dtype == np.float64 and a[k].shape == shape[::-1] and np.array_equal(a[k], b[k]), k
+    assert sum(v.nbytes for v in a.values()) <= 60e6
+
+    import bench
+
+    p = pkg.default_params(*shape)
+    p.n_lattices = 4  # (what bench.py runs on an NXxNYxNZ workload)
+    with pkg.Solver(p) as s:
+        s.initialization()
+        bench.apply_perturbation(s, None, p)
+        s.fast_Poisson()
+        s.init_equilibrium()
+        s.step(1)
+        s.step(3)
+        for k in pkg.FIELDS:
+            want = s.get_field(k)
+            assert np.linalg.norm(a[k] - want) <= 1e-12 * max(np.linalg.norm(want), 1e-300), k
+
+
+def test_dump_outputs_of_two_rccl_ranks_equal_one_context(pkg, O, tmp_path):
+    """--dump-outputs on a lattice too large to write whole (a seeded sample of nodes): two ranks under the driver's launcher
+    (one device, --single-device) put together the same sample as one context, to the rounding of the slab solve."""
+    wl = ["--workload", "128x128x64", "--steps", "2", "--warmup", "1"]
+    _bench_line(["--gpus", "1", *wl, "--dump-outputs", str(tmp_path / "one")])
+    env = dict(os.environ, OMP_NUM_THREADS="1")
+    env.pop("HSA_ENABLE_IPC_MODE_LEGACY", None)
+    launcher = ("-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()))
+    d = _bench_line(["--gpus", "2", "--single-device", *wl, "--dump-outputs", str(tmp_path / "two")], env=env, launcher=launcher)
+    assert d["n_gpus"] == 2 and "comm_ab" not in d
+    one, two = _dumped(tmp_path / "one"), _dumped(tmp_path / "two")
+    assert sorted(one) == sorted(two) == sorted(pkg.FIELDS)
+    n = one["rho"].size
+    import bench
+
+    assert n == bench.dump_sample_index((64, 128, 128), 11).size < 128 * 128 * 64 and sum(v.nbytes for v in one.values()) <= 60e6
+    for k in one:
+        assert one[k].shape == two[k].shape == (n,), k
+    err = O.rel_l2(two, one)
+    assert len(err) == len(O.GROUPS) and all(v < (1e-7 if k == "u" else 1e-11) for k, v in err.items()), err

@@ -12,11 +12,11 @@ O=gpurun_out
 run() { echo "== $*" >&2; "$@" 2>>$O/r05_rehearsals.err; }
 : > $O/r05_rehearsals.err
 for wl in 512x512x128 1024x1024x128 cfg3; do
-  run timeout -k 10 300 python bench.py --force-slab --workload $wl --no-cpu-baseline --steps 30 --warmup 5 >> $O/r05_one_rank_ring_comm_ab.jsonl || exit 1
+  run timeout -k 10 300 python bench.py --full --force-slab --workload $wl --no-cpu-baseline --steps 30 --warmup 5 >> $O/r05_one_rank_ring_comm_ab.jsonl || exit 1
 done
-run timeout -k 10 300 python bench.py --force-slab --workload 1024x1024x128 --in-place --no-cpu-baseline --steps 30 --warmup 5 >> $O/r05_one_rank_ring_comm_ab.jsonl || exit 1
+run timeout -k 10 300 python bench.py --full --force-slab --workload 1024x1024x128 --in-place --no-cpu-baseline --steps 30 --warmup 5 >> $O/r05_one_rank_ring_comm_ab.jsonl || exit 1
 for n in 2 4; do
-  run timeout -k 10 400 python bench.py --gpus $n --scale-z 8 --single-device --steps 10 --warmup 3 --comm-ab-steps 5 >> $O/r05_rehearsal_rccl_ranks_one_gpu.jsonl || exit 1
+  run timeout -k 10 400 python bench.py --full --gpus $n --scale-z 8 --single-device --steps 10 --warmup 3 --comm-ab-steps 5 >> $O/r05_rehearsal_rccl_ranks_one_gpu.jsonl || exit 1
 done
 run timeout -k 10 400 env EKPNP_OWN_FFT=0 python bench.py --gpus 4 --scale-z 8 --single-device --steps 10 --warmup 3 --no-comm-ab >> $O/r05_shared_device_own_fft_off_on.jsonl || exit 1
 run timeout -k 10 600 env EKPNP_OWN_FFT=1 python bench.py --gpus 4 --scale-z 8 --single-device --steps 10 --warmup 3 --no-comm-ab >> $O/r05_shared_device_own_fft_off_on.jsonl || exit 1
