@@ -100,7 +100,6 @@ static void drop_graph(Ctx& c);
 
 namespace ekpnp {
 int ctx_tune(Ctx& c, const char* knob, int value) {
-  if (std::strcmp(knob, "ab_zchunk") == 0 && value >= 0) { c.ab_zchunk = value; return EKPNP_OK; }
   if (std::strcmp(knob, "bulk_yband") == 0 && value >= -1 && value < 0x7fff) { c.bulk_yband = value; drop_graph(c); return EKPNP_OK; }
   // slab launch shapes (same bits either way): the lead-in launch of the interior sweep, one launch for both faces
   if (std::strcmp(knob, "lead_planes") == 0 && value >= 0 && c.slab) { c.lead_planes = value; return EKPNP_OK; }
@@ -109,10 +108,8 @@ int ctx_tune(Ctx& c, const char* knob, int value) {
   // library moves itself may ask for more than one (an external transport gathers the whole buffer in one piece)
   if (std::strcmp(knob, "edge_chunks") == 0 && value >= 1 && value <= 16 && c.slab && (value == 1 || c.team)) { c.edge_chunks = value; return EKPNP_OK; }
   if (std::strcmp(knob, "poisson_blocks") == 0 && value >= 0 && value <= 256 && !c.slab) { c.poisson_blocks = value; drop_graph(c); return EKPNP_OK; }
-  if (std::strcmp(knob, "poisson_zchunk") == 0 && value >= 0 && !c.slab) { c.poisson_zchunk = value; drop_graph(c); return EKPNP_OK; }
   if (std::strcmp(knob, "merged_walls") == 0) { c.merged_walls = value != 0; drop_graph(c); return EKPNP_OK; }
   if (std::strcmp(knob, "tri_partition") == 0 && value >= 0 && value <= 2) { c.tri_partition = value; drop_graph(c); return EKPNP_OK; }
-  if (std::strcmp(knob, "tri_wide") == 0 && (value == 0 || value == 1)) { c.tri_wide = value != 0 && c.tri_lds_ok && tridiag_wide_prepare_device(); drop_graph(c); return EKPNP_OK; }
   if (std::strcmp(knob, "batch_moments") == 0 && (value == 0 || value == 1)) { c.batch_moments = value != 0; return EKPNP_OK; }
   if (std::strcmp(knob, "lazy_efield") == 0 && (value == 0 || value == 1)) {  // the A/B partner of the EPHI kernels: 0 = k_phi_efield in every solve
     const int rc = ensure_efield(c);
@@ -125,7 +122,7 @@ int ctx_tune(Ctx& c, const char* knob, int value) {
 }
 }  // namespace ekpnp
 
-// measurement hook (tools/sweep_zchunk.py, bench.py's comm_ab): change a launch-shape or transport knob of a live context
+// measurement hook (bench.py's comm_ab): change a launch-shape or transport knob of a live context
 extern "C" int ekpnp_tune(ekpnp_ctx* ctx, const char* knob, int value) {
   if (!ctx || !knob) return EKPNP_ERR_INVALID;
   Ctx& c = ctx->c;
@@ -337,20 +334,16 @@ extern "C" int ekpnp_pass_order(const ekpnp_ctx* ctx, int* band_rows, int* poiss
   const Ctx& c = ctx->c;
   if (band_rows) *band_rows = bulk_band_rows(c);
   if (poisson_blocks) *poisson_blocks = poisson_block_count(c);
-  if (poisson_zchunk) *poisson_zchunk = !c.slab && c.own_fft && c.poisson_zchunk > 0 && c.poisson_zchunk < c.fft_nz ? c.poisson_zchunk : 0;
+  if (poisson_zchunk) *poisson_zchunk = 0;
   return EKPNP_OK;
 }
 
-// the population buffers inside their one allocation: A0 A1 A2 A3 B0 B1 B2 B3 (buffer-major; EKPNP_POP_ORDER=1, an
-// experiment of round 3: lattice-major A0 B0 A1 B1 ... - no difference, profiles/r03_direction_sweep.log)
+// the population buffers inside their one allocation: A0 A1 A2 A3 B0 B1 B2 B3 (buffer-major; lattice-major A0 B0 A1 B1 ...
+// made no difference, profiles/r03_direction_sweep.log)
 static void carve_arena(Ctx& c, void* base, size_t pitch) {
-  static const bool lattice_major = std::getenv("EKPNP_POP_ORDER") != nullptr && std::atoi(std::getenv("EKPNP_POP_ORDER")) == 1;
   const int nb = c.inplace ? 1 : 2, nl = c.p.n_lattices;
   for (int b = 0; b < nb; ++b)
-    for (int l = 0; l < nl; ++l) {
-      const int k = lattice_major ? l * nb + b : b * nl + l;
-      c.pop[b][l] = (double*)((char*)base + pitch * k);
-    }
+    for (int l = 0; l < nl; ++l) c.pop[b][l] = (double*)((char*)base + pitch * (b * nl + l));
 }
 
 static int create_impl(const ekpnp_params* p, int rank, int nranks, bool slab, ekpnp_ctx** out) {
@@ -387,7 +380,6 @@ static int create_impl(const ekpnp_params* p, int rank, int nranks, bool slab, e
   if (hipGetDevice(&c.device) != hipSuccess) { c.err = "hipGetDevice failed"; return bail(EKPNP_ERR_HIP); }
   c.tri_lds_ok = tridiag_prepare_device();
   if (hipDeviceGetAttribute(&c.ncus, hipDeviceAttributeMultiprocessorCount, c.device) != hipSuccess || c.ncus < 1) { (void)hipGetLastError(); c.ncus = 256; }
-  if (const char* e = std::getenv("EKPNP_BULK_ZCHUNK")) c.ab_zchunk = std::atoi(e) > 0 ? std::atoi(e) : 0;
   if (const char* e = std::getenv("EKPNP_BULK_YBAND")) c.bulk_yband = std::atoi(e) < -1 ? -1 : (std::atoi(e) > 0x7ffe ? 0x7ffe : std::atoi(e));
   c.merged_walls = std::getenv("EKPNP_NO_MERGED_WALLS") == nullptr;
   if (const char* e = std::getenv("EKPNP_LAZY_E")) c.lazy_efield = std::atoi(e) != 0 ? 1 : 0;
@@ -396,12 +388,7 @@ static int create_impl(const ekpnp_params* p, int rank, int nranks, bool slab, e
   if (const char* e = std::getenv("EKPNP_MERGED_FACES")) c.merged_faces = std::atoi(e) != 0;
   if (const char* e = std::getenv("EKPNP_SLAB_LEAD_PLANES")) c.lead_planes = std::atoi(e) < 0 ? 0 : std::atoi(e);
   if (const char* e = std::getenv("EKPNP_POISSON_BLOCKS")) c.poisson_blocks = std::atoi(e) < 0 ? 0 : (std::atoi(e) > 256 ? 256 : std::atoi(e));
-  if (const char* e = std::getenv("EKPNP_POISSON_ZCHUNK")) c.poisson_zchunk = std::atoi(e) < 0 ? 0 : std::atoi(e);
   if (const char* e = std::getenv("EKPNP_EDGE_CHUNKS")) c.edge_chunks = std::atoi(e) < 1 ? 1 : (std::atoi(e) > 16 ? 16 : std::atoi(e));
-  {
-    const char* e = std::getenv("EKPNP_TRI_WIDE");
-    c.tri_wide = c.tri_lds_ok && (e ? std::atoi(e) != 0 : false) && tridiag_wide_prepare_device();
-  }
   if (const char* e = std::getenv("EKPNP_TRI_PARTITION")) c.tri_partition = std::atoi(e) < 0 ? 0 : (std::atoi(e) > 2 ? 2 : std::atoi(e));
   // In-place mode: one buffer per lattice with `shift` spare planes.  A sweep writes plane z of
   // the new state `shift` planes below (parity 0, bulk launches of `zchunk` planes in ascending z)
@@ -416,36 +403,17 @@ static int create_impl(const ekpnp_params* p, int rank, int nranks, bool slab, e
   // All population buffers are carved out of ONE allocation.  With a hipMalloc per buffer (8 of 29 GB on
   // cfg3) the step time of otherwise identical contexts spread over 42.5 ... 44.2 ms depending on where
   // the driver happened to place them; out of one 233 GB allocation it is 42.5 ... 42.7 ms, every time
-  // (profiles/r02_population_arena.log).  EKPNP_POP_ARENA=<bytes> puts a gap between the buffers (0 and
-  // 4096 measured the same), EKPNP_POP_ARENA=-1 restores one allocation per buffer (the A/B partner).
-  static const long long arena_gap = std::getenv("EKPNP_POP_ARENA") ? std::atoll(std::getenv("EKPNP_POP_ARENA")) : 0;
-  bool arena = arena_gap >= 0;
-  size_t pop_pitch = 0;
-  int pop_nbuf = 0;
+  // (profiles/r02_population_arena.log; a gap of 4096 bytes between the buffers measured the same as none).
+  const int pop_nbuf = (c.inplace ? 1 : 2) * p->n_lattices;
+  const size_t pop_pitch = (popbytes + 255) / 256 * 256;
+  bool arena = hipMalloc(&c.pop_alloc[0][0], pop_pitch * pop_nbuf) == hipSuccess;
   if (arena) {
-    const int nbuf = (c.inplace ? 1 : 2) * p->n_lattices;
-    const size_t pitch = (popbytes + (size_t)arena_gap + 255) / 256 * 256;
-    pop_pitch = pitch;
-    pop_nbuf = nbuf;
-    // EKPNP_POP_CONTIGUOUS=1 (experiment, round 3): ask the driver for physically contiguous VRAM (hipDeviceMallocContiguous)
-    static const bool want_contig = std::getenv("EKPNP_POP_CONTIGUOUS") != nullptr && std::atoi(std::getenv("EKPNP_POP_CONTIGUOUS")) != 0;
-    bool got = false;
-    if (want_contig) {
-      got = hipExtMallocWithFlags(&c.pop_alloc[0][0], pitch * nbuf, hipDeviceMallocContiguous) == hipSuccess;
-      if (!got) { (void)hipGetLastError(); c.pop_alloc[0][0] = nullptr; }
-      if (std::getenv("EKPNP_DEBUG_ARENA")) std::fprintf(stderr, "ekpnp: contiguous arena %s\n", got ? "granted" : "REFUSED, plain hipMalloc");
-    }
-    if (got || hipMalloc(&c.pop_alloc[0][0], pitch * nbuf) == hipSuccess) {
-      c.bytes += pitch * nbuf;
-      if (std::getenv("EKPNP_DEBUG_ARENA")) std::fprintf(stderr, "ekpnp: population arena %p, %zu buffers of %zu bytes\n", c.pop_alloc[0][0], (size_t)nbuf, pitch);
-      carve_arena(c, c.pop_alloc[0][0], pitch);
-    } else {  // no contiguous range of that size (a fragmented device): one allocation per buffer may still fit
-      (void)hipGetLastError();
-      c.pop_alloc[0][0] = nullptr;
-      arena = false;
-    }
-  }
-  if (!arena) {
+    c.bytes += pop_pitch * pop_nbuf;
+    if (std::getenv("EKPNP_DEBUG_ARENA")) std::fprintf(stderr, "ekpnp: population arena %p, %zu buffers of %zu bytes\n", c.pop_alloc[0][0], (size_t)pop_nbuf, pop_pitch);
+    carve_arena(c, c.pop_alloc[0][0], pop_pitch);
+  } else {  // no contiguous range of that size (a fragmented device): one allocation per buffer may still fit
+    (void)hipGetLastError();
+    c.pop_alloc[0][0] = nullptr;
     for (int b = 0; b < (c.inplace ? 1 : 2); ++b)
       for (int l = 0; l < p->n_lattices; ++l) {
         if ((rc = dev_alloc(c, &c.pop_alloc[b][l], popbytes))) return bail(rc);
@@ -458,19 +426,8 @@ static int create_impl(const ekpnp_params* p, int rank, int nranks, bool slab, e
   // The 11 macroscopic arrays are equally sized (a power of two bytes on cfg2/cfg3) and are walked
   // in lockstep by the kernels; identical placement modulo the HBM channel interleave makes all of
   // their streams queue on the same channels.  Each owned array is therefore skewed by a different
-  // multiple of `skew` bytes inside a slightly larger allocation (EKPNP_FIELD_SKEW: tuning knob).
-  static const size_t skew = std::getenv("EKPNP_FIELD_SKEW") ? (size_t)std::atoll(std::getenv("EKPNP_FIELD_SKEW")) : 4096;
-  // EKPNP_FIELD_ARENA=1 (tuning experiment): the 11 arrays out of one allocation, same skew
-  static const bool field_arena = std::getenv("EKPNP_FIELD_ARENA") != nullptr && std::atoi(std::getenv("EKPNP_FIELD_ARENA")) != 0;
-  if (field_arena) {
-    const size_t pitch = (c.nloc * sizeof(double) + (size_t)EKPNP_NFIELDS * skew + 255) / 256 * 256;
-    if ((rc = dev_alloc(c, &c.fld_arena, pitch * EKPNP_NFIELDS))) return bail(rc);
-    for (int i = 0; i < EKPNP_NFIELDS; ++i) {
-      c.fld[i] = (double*)((char*)c.fld_arena + pitch * i + (size_t)i * skew);
-      c.fld_owned[i] = true;
-      if (hipMemsetAsync(c.fld[i], 0, c.nloc * sizeof(double), c.stream) != hipSuccess) { c.err = "hipMemsetAsync failed"; return bail(EKPNP_ERR_HIP); }
-    }
-  } else
+  // multiple of `skew` bytes inside a slightly larger allocation.
+  constexpr size_t skew = 4096;
   for (int i = 0; i < EKPNP_NFIELDS; ++i) {
     c.fld_bytes[i] = c.nloc * sizeof(double) + (size_t)EKPNP_NFIELDS * skew;
     if ((rc = dev_alloc(c, &c.fld_alloc[i], c.fld_bytes[i]))) { c.fld_bytes[i] = 0; return bail(rc); }
@@ -548,7 +505,6 @@ extern "C" int ekpnp_destroy(ekpnp_ctx* ctx) {
     if (c.stage[l]) (void)hipFree(c.stage[l]);
   for (int i = 0; i < EKPNP_NFIELDS; ++i)
     if (c.fld_alloc[i] && c.fld_owned[i]) (void)hipFree(c.fld_alloc[i]);
-  if (c.fld_arena) (void)hipFree(c.fld_arena);
   if (c.work) (void)hipFree(c.work);
   if (c.spec) (void)hipFree(c.spec);
   if (c.cprime) (void)hipFree(c.cprime);
@@ -754,32 +710,17 @@ static int poisson_single(Ctx& c, bool allow_lazy) {
   if (!c.rhs_ready) launch_poisson_rhs(c);
   c.rhs_ready = false;
   const int nb = poisson_block_count(c);
-  const int zc = c.own_fft && c.poisson_zchunk > 0 && c.poisson_zchunk < c.fft_nz ? c.poisson_zchunk : 0;
-  if (nb > 1 || zc) {
-    // The passes in pieces that stay in the Infinity Cache from one pass to the next (poisson.hip: poisson_block; same kernels,
-    // same bits).  Plane chunks: rows + columns of one run of planes back to back; column blocks: the middle passes of one
-    // kx block back to back.  Both: forward by plane chunks, then z solve + y inverse by column blocks, then all rows.
-    const ModeBlock all = poisson_block_whole(c);
-    if (zc) {
-      for (int z0 = 0; z0 < c.fft_nz; z0 += zc) {
-        const int n = c.fft_nz - z0 < zc ? c.fft_nz - z0 : zc;
-        if (int frc = plane_fft_forward_rows(c, z0, n)) return frc;
-        plane_fft_forward_columns(c, all, z0, n);
-      }
-    } else if (int frc = plane_fft_forward_rows(c)) return frc;
+  if (nb > 1) {
+    // The middle passes (y forward, z solve, y inverse) of one kx column block back to back, so that the block stays in the
+    // Infinity Cache from one pass to the next (poisson.hip: poisson_block; same kernels, same bits).
+    if (int frc = plane_fft_forward_rows(c)) return frc;
     for (int k = 0; k < nb; ++k) {
-      const ModeBlock blk = nb > 1 ? poisson_block(c, k) : all;
-      if (!zc) plane_fft_forward_columns(c, blk);
-      launch_tridiag(c, nb > 1 ? &blk : nullptr);
-      if (nb > 1) plane_fft_inverse_columns(c, blk);
+      const ModeBlock blk = poisson_block(c, k);
+      plane_fft_forward_columns(c, blk);
+      launch_tridiag(c, &blk);
+      plane_fft_inverse_columns(c, blk);
     }
-    if (nb == 1) {  // (plane chunks only)
-      for (int z0 = 0; z0 < c.fft_nz; z0 += zc) {
-        const int n = c.fft_nz - z0 < zc ? c.fft_nz - z0 : zc;
-        plane_fft_inverse_columns(c, all, z0, n);
-        if (int frc = plane_fft_inverse_rows(c, z0, n)) return frc;
-      }
-    } else if (int frc = plane_fft_inverse_rows(c)) return frc;
+    if (int frc = plane_fft_inverse_rows(c)) return frc;
   } else {
     if (int frc = plane_fft_forward(c)) return frc;
     launch_tridiag(c);
@@ -967,12 +908,7 @@ static int collide_range(Ctx& c, int zb, int ze, bool timed) {
     int rc = timing_begin(c, &stop);
     if (rc) return rc;
   }
-  // the two-buffer sweep in launches of c.ab_zchunk planes (0: one launch); ekpnp_tune / EKPNP_BULK_ZCHUNK
-  const int zchunk = c.ab_zchunk;
-  if (zchunk > 0)
-    for (int z = zb; z < ze; z += zchunk) launch_collide_bulk(c, z, z + zchunk < ze ? z + zchunk : ze);
-  else
-    launch_collide_bulk(c, zb, ze);
+  launch_collide_bulk(c, zb, ze);  // the two-buffer sweep in one launch (launches of fewer planes: profiles/r02_sweep_bulk_zchunk.log)
   if (stop) {
     HIPCHK(c, hipEventRecord(*stop, c.stream));
     c.timed_nodes = (long long)(ze - zb) * (long long)c.plane;

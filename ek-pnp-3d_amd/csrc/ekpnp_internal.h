@@ -38,14 +38,8 @@ __host__ __device__ constexpr int opp_of(int d) { return d == 0 ? 0 : ((d & 1) ?
 // 38.87 -> 38.62 - 38.71 ms on cfg3 (alternating legs on one box, profiles/r05g_ab_grouped_slots.log; round 1's copy probe had
 // priced a scattered numbering at 0.35 %).  The numbering of the ARITHMETIC (d, opp_of, the order of every sum) is the
 // reference's as before: only where a population lies in its tile changed - and with it the population part of the
-// checkpoint files, hence their new format id "EKPNPCK2".  EKPNP_SLOT_BY_DIRECTION builds the A/B partner (slot = d).
-__host__ __device__ constexpr int slot_of(int d) {
-#ifdef EKPNP_SLOT_BY_DIRECTION
-  return d;
-#else
-  return (ez_of(d) + 1) * 9 + (ey_of(d) + 1) * 3 + (ex_of(d) + 1);
-#endif
-}
+// checkpoint files, hence their new format id "EKPNPCK2".
+__host__ __device__ constexpr int slot_of(int d) { return (ez_of(d) + 1) * 9 + (ey_of(d) + 1) * 3 + (ex_of(d) + 1); }
 __host__ __device__ constexpr double w_of(int d) {
   return d == 0 ? 8.0 / 27.0 : d <= 6 ? 2.0 / 27.0 : d <= 18 ? 1.0 / 54.0 : 1.0 / 216.0;  // LBM.h:109-112
 }
@@ -67,10 +61,7 @@ __host__ __device__ constexpr int dn_dir(int k) {
 // lie gigabytes apart (pure-copy ceiling of the two shapes on one box: 5.95 vs 5.48 TB/s,
 // profiles/r01_stream_probe_aosoa.log).  Lanes of the last tile beyond nx are never touched.
 constexpr int TILE = Q * 64;
-#ifndef EKPNP_TRI_CHECK
-#define EKPNP_TRI_CHECK 16  // tuning knob (8 / 32 measured: profiles/r02_tridiag_variants.log)
-#endif
-constexpr int TRI_CHECK = EKPNP_TRI_CHECK;  // the z solves keep every TRI_CHECK-th row of c' and of d' (poisson.hip TRI_BS)
+constexpr int TRI_CHECK = 16;  // the z solves keep every TRI_CHECK-th row of c' and of d' (poisson.hip TRI_BS; 8 / 32 measured: profiles/r02_tridiag_variants.log)
 __host__ __device__ inline long long pop_xoff(int x) { return (long long)(x >> 6) * TILE + (x & 63); }
 
 // z partition of the slabs: rank r owns planes [slab_begin(r), slab_begin(r+1)); sizes differ by at most one
@@ -171,7 +162,7 @@ void launch_init_fields(Ctx&);
 void launch_pbe(Ctx&);
 void launch_pbe_relax(Ctx&, double* phi_old, double omega);
 void launch_init_equilibrium(Ctx&);
-int bulk_band_rows(const Ctx&, int rchunk = 64);  // rows per band of the interior sweep in effect (0: plane after plane)
+int bulk_band_rows(const Ctx&);  // rows per band of the interior sweep in effect (0: plane after plane)
 void launch_collide_all(Ctx&);  // launch-bound lattices: plates and bulk in ONE launch (single two-buffer context)
 void launch_collide_bulk(Ctx&, int zl_begin, int zl_end);
 void launch_collide_bulk(Ctx&, const KArgs&, int zl_begin, int zl_end);
@@ -193,18 +184,16 @@ int plane_fft_inverse(Ctx&);    // fft_spec() -> fft_out()
 void launch_tridiag(Ctx&, const ModeBlock* block = nullptr);  // the whole spectrum, or the kx columns of one block
 int poisson_block_count(const Ctx&);                    // column blocks of a single context's solve (Ctx::poisson_blocks; 1 where they do not apply)
 ModeBlock poisson_block(const Ctx&, int block);
-ModeBlock poisson_block_whole(const Ctx&);              // all kx columns
 bool tridiag_prepare_device();  // per-device function attributes of the partition z solves (current device)
-bool tridiag_wide_prepare_device();  // ... of the 16-wavefront forms (128 KB of LDS)
 void launch_phi_efield(Ctx&);
 void launch_slab_thomas_local(Ctx&, int block = 0);    // stage 1 of the slab z solve on mode block `block`
 void launch_slab_reduce_correct(Ctx&, int block = 0);  // stage 2 on mode block `block` (its edge values gathered)
 int edge_chunk_count(const Ctx&);                       // mode blocks of this context's slab solve (Ctx::edge_chunks, at most nxh / 8)
 ModeBlock mode_block(const Ctx&, int block);
-int plane_fft_forward_rows(Ctx&, int z0 = 0, int nz = -1);                       // the transforms in pieces (rows of all planes / columns of one block)
-void plane_fft_forward_columns(Ctx&, const ModeBlock&, int z0 = 0, int nz = -1);
-void plane_fft_inverse_columns(Ctx&, const ModeBlock&, int z0 = 0, int nz = -1);
-int plane_fft_inverse_rows(Ctx&, int z0 = 0, int nz = -1);
+int plane_fft_forward_rows(Ctx&);                       // the transforms in pieces (rows of all planes / columns of one block)
+void plane_fft_forward_columns(Ctx&, const ModeBlock&);
+void plane_fft_inverse_columns(Ctx&, const ModeBlock&);
+int plane_fft_inverse_rows(Ctx&);
 void launch_phi_halo_pack(Ctx&);
 // diag.hip
 constexpr int DIAG_SCRATCH = 1024 + 8;
@@ -233,7 +222,6 @@ struct Ctx {
   bool inplace = false;
   int shift = 0;               // planes the lattice moves per sweep in in-place mode (0 in A/B mode)
   int zchunk = 0;              // planes per bulk launch in in-place mode (shift >= zchunk + 1)
-  int ab_zchunk = 0;           // two-buffer mode: planes per bulk launch of the sweep (0: one launch)
   int bulk_yband = -1;         // the interior sweep (in place: each of its launches) takes bands of this many rows of EVERY plane, band after band, instead of
                                // plane after plane (lbm_kernels.hip: bulk_row_of_block): the three uses of a phi row lie within the Infinity
                                // Cache's reach.  -1: decided from the plane's traffic (bulk_dispatch), 0: plane after plane (ekpnp_tune
@@ -270,7 +258,6 @@ struct Ctx {
   bool fld_owned[EKPNP_NFIELDS] = {};
   void* fld_alloc[EKPNP_NFIELDS] = {};  // what hipMalloc returned for an owned field (fld[i] is skewed into it)
   size_t fld_bytes[EKPNP_NFIELDS] = {}; // size of that allocation (skew pad included)
-  void* fld_arena = nullptr;            // EKPNP_FIELD_ARENA: the owned fields share this one allocation
   double* work = nullptr;
   double2* spec = nullptr;
   // the transforms run over the owned interior planes [fft_z0, fft_z0 + fft_nz): right-hand side in
@@ -295,8 +282,6 @@ struct Ctx {
                                    // > 1: the EDGE all-gather of block k runs on the comm stream beside the column pass of block k + 1
   int poisson_blocks = 0;          // single context (0: decided from the spectrum's size, poisson.hip: poisson_block_count): kx column blocks of the solve's middle passes (y forward, z solve, y inverse of one block back to
                                    // back, so that the block stays in the Infinity Cache between them; ekpnp_tune "poisson_blocks", EKPNP_POISSON_BLOCKS)
-  int poisson_zchunk = 0;          // single context, own transforms: planes per chunk of the row + column passes (rows and columns of one chunk back
-                                   // to back: the chunk is still in the Infinity Cache; 0 = whole passes; ekpnp_tune "poisson_zchunk", EKPNP_POISSON_ZCHUNK)
   double* phi_old = nullptr;       // PB relaxation state (ekpnp_pbe_begin/end)
   double* diag = nullptr;          // reduction scratch (DIAG_SCRATCH doubles)
   double* vwall = nullptr;         // {voltage, voltage, voltage2, voltage2}
@@ -316,7 +301,6 @@ struct Ctx {
   double2* fft_tw = nullptr;       // their twiddle table exp(-2 pi i k / 1024)
   hipfftHandle plan_fwd = 0, plan_inv = 0;
   bool tri_lds_ok = false;  // this context's device grants the partition z solves their dynamic LDS (tridiag_prepare_device)
-  bool tri_wide = false;    // columns of more than 256 rows: 16 modes (wavefronts) per workgroup = 256-byte pieces of every row (EKPNP_TRI_WIDE, ekpnp_tune "tri_wide")
   int ncus = 0;             // compute units of the context's device (the grid of the pipelined z solves)
   int tri_partition = 1;  // z solve of a single context: 0 serial sweeps, 1 partition solve on large lattices, 2 wherever it applies
   bool have_fwd = false, have_inv = false;  // each handle is destroyed on its own (a failing second plan must not leak the first)

@@ -12,9 +12,10 @@
 //   A workgroup owns COLS adjacent kx columns of one plane - COLS x 16 bytes of every row - with 64 threads per column.
 //   Stockham autosort through one LDS image [row][column]; stage 0 reads the rows straight from global memory, the
 //   last stage writes them straight back (in place: a workgroup reads all of its elements before it writes any).
-//     512 rows:  radix 8 x 8 x 8,  COLS = 8 (one full 128-byte line per row), 72 KB of LDS
-//     1024 rows: radix 16 x 8 x 8, COLS = 4 (64 bytes per row; the workgroup that owns the other half of the line runs
-//                on the same XCD right behind it, so the line is fetched from HBM once), 80 KB of LDS
+//     512 rows:  radix 8 x 8 x 8,  COLS = 4, 40 KB of LDS
+//     1024 rows: radix 16 x 8 x 8, COLS = 4, 80 KB of LDS
+//   (64 bytes per row: the workgroup that owns the other half of the 128-byte line runs on the same XCD right behind it,
+//   so the line is fetched from HBM once)
 //   Twiddles exp(-2 pi i k / N) from a table the host computed in long double, kept in LDS.
 // Unnormalised in both directions, like cuFFT / rocFFT.  The spectrum row pitch nxh is a multiple of 8 (capi.hip); the
 // padding columns beyond NX/2 are transformed along (never read by anyone).
@@ -29,7 +30,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdlib>
 
 namespace ekpnp {
 
@@ -90,60 +90,12 @@ __device__ __forceinline__ void fy_dft16(double2 (&v)[16]) {
 
 constexpr size_t fy_lds_bytes(int n, int cols) { return (size_t)(n * cols + n) * sizeof(double2); }
 
-// ---- 512 rows: radix 8 x 8 x 8, 8 columns per workgroup ----------------------------------------------------------
-template <int SIGN>
-__global__ void __launch_bounds__(512) k_fft_y512(double2* __restrict__ spec, const double2* __restrict__ tw, int nxh, long long plane_stride) {
-  constexpr int N = 512, COLS = 8;
-  extern __shared__ double2 fy_lds[];
-  double2* buf = fy_lds;            // [512 rows][8 columns]
-  double2* w = fy_lds + N * COLS;   // exp(-2 pi i k / 512)
-  const int c = threadIdx.x & 7, t = threadIdx.x >> 3;  // column, butterfly 0..63
-  double2* base = spec + (long long)blockIdx.y * plane_stride + (long long)blockIdx.x * COLS + c;
-  double2 v[8];
-#pragma unroll
-  for (int r = 0; r < 8; ++r) v[r] = base[(long long)(t + 64 * r) * nxh];
-  w[threadIdx.x] = tw[threadIdx.x];
-  // stage 0 (sub-transform length 1): no twiddles; X[k] -> row 8 t + k
-  fy_dft8<SIGN>(v);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) buf[(8 * t + fy_rev3(i)) * COLS + c] = v[i];
-  __syncthreads();
-  // stage 1 (length 8): twiddle exp(-+2 pi i (t mod 8) r / 64); X[k] -> row (t / 8) 64 + (t mod 8) + 8 k
-#pragma unroll
-  for (int r = 0; r < 8; ++r) v[r] = buf[(t + 64 * r) * COLS + c];
-  {
-    const int k = t & 7;
-#pragma unroll
-    for (int r = 1; r < 8; ++r) v[r] = fy_mul_tw<SIGN>(v[r], w[k * r * 8]);
-  }
-  fy_dft8<SIGN>(v);
-  __syncthreads();  // every thread holds its inputs: the image may be overwritten
-  {
-    const int j0 = (t >> 3) * 64 + (t & 7);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) buf[(j0 + 8 * fy_rev3(i)) * COLS + c] = v[i];
-  }
-  __syncthreads();
-  // stage 2 (length 64): twiddle exp(-+2 pi i t r / 512); X[k] -> row t + 64 k
-#pragma unroll
-  for (int r = 0; r < 8; ++r) v[r] = buf[(t + 64 * r) * COLS + c];
-#pragma unroll
-  for (int r = 1; r < 8; ++r) v[r] = fy_mul_tw<SIGN>(v[r], w[t * r]);
-  fy_dft8<SIGN>(v);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) base[(long long)(t + 64 * fy_rev3(i)) * nxh] = v[i];
-}
-
 // LDS row of the 1024-row image: a row is only 64 bytes (a quarter of the 64 banks), so rows whose index differs by a
 // multiple of 4 share their banks - and stage 0 writes rows 16 t + k for neighbouring t in the same instruction.  The low
 // two bits of the row are XOR-ed with bits 4-5 (a bijection inside every aligned group of 4 rows).
-#ifndef EKPNP_FFTY_NO_SWIZZLE
 __device__ __forceinline__ int fy_row(int r) { return r ^ ((r >> 4) & 3); }
-#else
-__device__ __forceinline__ int fy_row(int r) { return r; }
-#endif
 
-// ---- 512 rows, 4 columns per workgroup (round 3): radix 8 x 8 x 8 like k_fft_y512, but 64 bytes per row and workgroup,
+// ---- 512 rows: radix 8 x 8 x 8, 4 columns per workgroup (round 3; round 2's kernel took 8): 64 bytes per row and workgroup,
 // 40 KB of LDS (4 workgroups per CU instead of 2), the two halves of a line paired on one XCD like k_fft_y1024
 __device__ __forceinline__ int fy_row8(int r) { return r ^ ((r >> 3) & 3); }  // stage 0 writes rows 8 t + k for neighbouring t
 template <int SIGN>
@@ -285,9 +237,7 @@ inline void fft_y_twiddles(int ny, double2* h) {
 inline bool fft_y_prepare(int ny) {
   hipError_t e = hipSuccess;
   if (ny == 512) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fft_y512<-1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fy_lds_bytes(512, 8));
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fft_y512<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fy_lds_bytes(512, 8));
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fft_y512c4<-1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fy_lds_bytes(512, 4));
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fft_y512c4<-1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fy_lds_bytes(512, 4));
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fft_y512c4<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fy_lds_bytes(512, 4));
   } else {
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fft_y1024<-1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fy_lds_bytes(1024, 4));
@@ -305,26 +255,14 @@ inline void fft_y_launch(double2* spec, const double2* tw, int ny, int nxh, int 
   if (ngroups < 0) { group0 = 0; ngroups = nxh / 8; }
   if (ngroups == 0) return;
   const long long ps = (long long)ny * nxh;
+  const int npairs = nplanes * ngroups;
+  const unsigned blocks = (unsigned)((npairs + 7) / 8) * 8 * 2;
   if (ny == 512) {
-    // EKPNP_FFTY512_COLS=8: the 8-column kernel of round 2 (the A/B partner)
-    static const bool cols8 = std::getenv("EKPNP_FFTY512_COLS") != nullptr && std::atoi(std::getenv("EKPNP_FFTY512_COLS")) == 8;
-    if (cols8 && group0 == 0 && ngroups == nxh / 8) {
-      const dim3 grid(nxh / 8, nplanes);
-      if (sign < 0)
-        hipLaunchKernelGGL(k_fft_y512<-1>, grid, dim3(512), fy_lds_bytes(512, 8), stream, spec, tw, nxh, ps);
-      else
-        hipLaunchKernelGGL(k_fft_y512<1>, grid, dim3(512), fy_lds_bytes(512, 8), stream, spec, tw, nxh, ps);
-    } else {
-      const int npairs = nplanes * ngroups;
-      const unsigned blocks = (unsigned)((npairs + 7) / 8) * 8 * 2;
-      if (sign < 0)
-        hipLaunchKernelGGL(k_fft_y512c4<-1>, dim3(blocks), dim3(256), fy_lds_bytes(512, 4), stream, spec, tw, nxh, ps, npairs, group0, ngroups);
-      else
-        hipLaunchKernelGGL(k_fft_y512c4<1>, dim3(blocks), dim3(256), fy_lds_bytes(512, 4), stream, spec, tw, nxh, ps, npairs, group0, ngroups);
-    }
+    if (sign < 0)
+      hipLaunchKernelGGL(k_fft_y512c4<-1>, dim3(blocks), dim3(256), fy_lds_bytes(512, 4), stream, spec, tw, nxh, ps, npairs, group0, ngroups);
+    else
+      hipLaunchKernelGGL(k_fft_y512c4<1>, dim3(blocks), dim3(256), fy_lds_bytes(512, 4), stream, spec, tw, nxh, ps, npairs, group0, ngroups);
   } else {
-    const int npairs = nplanes * ngroups;
-    const unsigned blocks = (unsigned)((npairs + 7) / 8) * 8 * 2;
     if (sign < 0)
       hipLaunchKernelGGL(k_fft_y1024<-1>, dim3(blocks), dim3(256), fy_lds_bytes(1024, 4), stream, spec, tw, nxh, ps, npairs, group0, ngroups);
     else

@@ -15,7 +15,6 @@
 // stores of a wave fill one contiguous 13.8 KB tile, the 27 loads are 512-byte segments of the
 // tiles of the 9 neighbour rows; row bases are wave-uniform (SGPR), the direction is an immediate
 // offset and only the three x offsets live in VGPRs.
-#include <cstdlib>
 #include <type_traits>
 #include <utility>
 
@@ -152,9 +151,6 @@ __device__ __forceinline__ void equilibrium(const KArgs& a, double m, double vx,
 // ------------------------------------------------------------------------------------------
 // bulk kernel: every owned plane that is not a wall plane
 
-#ifndef EKPNP_BULK_MIN_WAVES
-#define EKPNP_BULK_MIN_WAVES 1  // tuning knob: min waves per SIMD the register allocator must allow
-#endif
 // the work of one bulk workgroup: row `row` of the launch (y = row % ny, plane zl_begin + row / ny), x block xb
 // EPHI: E is not read from the Ex / Ey / Ez arrays but formed from phi right here - gpu_efield's central differences
 // (poisson.cu:45-55) in the expression of k_phi_efield, 0.5*(a - b)/d, hence the same bits -, one component per wave
@@ -194,11 +190,7 @@ __device__ __forceinline__ void bulk_body(const KArgs& a, const int zl_begin, co
       }
     }
     const double* rowp = src + ((long long)(zg - cz) * a.ny + ys[cy + 1]) * a.rowstride + slot_of(d) * 64;
-#ifdef EKPNP_NT_LOADS  // A/B partner: non-temporal loads (every population is pulled exactly once) LOSE 3 %, profiles/r02_sweep_nt_loads.log
-    f[d] = __builtin_nontemporal_load(rowp + xo[cx + 1]);
-#else
-    f[d] = rowp[xo[cx + 1]];
-#endif
+    f[d] = rowp[xo[cx + 1]];  // (non-temporal loads - every population is pulled exactly once - lose 3 %, profiles/r02_sweep_nt_loads.log)
   });
 
   if constexpr (NL > 1) {
@@ -268,12 +260,8 @@ __device__ __forceinline__ void bulk_body(const KArgs& a, const int zl_begin, co
   auto store = [&](auto ic, double v) {
     constexpr int d = decltype(ic)::value;
     // non-temporal: the populations written here are not read again before the next step
-    // (+1 % on cfg3, profiles/r01_sweep_libs.log); EKPNP_PLAIN_STORES builds the A/B partner
-#ifdef EKPNP_PLAIN_STORES
-    if (act) dst[slot_of(d) * 64] = v;
-#else
+    // (+1 % on cfg3, profiles/r01_sweep_libs.log)
     if (act) __builtin_nontemporal_store(v, dst + slot_of(d) * 64);
-#endif
     if constexpr (EDGE && ez_of(d) != 0) {
       // ... and one that leaves through the face goes into the send buffer as well (what k_halo_pack would copy there)
       double* __restrict__ hb = ez_of(d) < 0 ? a.halo_out_dn : a.halo_out_up;
@@ -300,13 +288,16 @@ __device__ __forceinline__ void bulk_body(const KArgs& a, const int zl_begin, co
   }
 }
 
+// rows per run of the XCD-aware placement below, in every launcher of the collide kernels
+constexpr int BULK_RCHUNK = 64;
+
 // row of the launch a workgroup works on (XCD-aware placement), or -1 when it is beyond the last row
 __device__ __forceinline__ int bulk_row_of_block(const int nrows, const int nxb, const int rchunk_arg, int& xb, const int ny = 0) {
   // XCD-aware placement.  Workgroups are dealt round-robin over the 8 XCDs (bid % 8 picks the
   // XCD).  Each XCD is given runs of `rchunk` CONSECUTIVE x rows (and walks along x inside a row),
   // so that every one of the 27+27 direction streams is sequential per XCD instead of a 1-in-8
   // row comb.  Measured on cfg3 (512^3, 4 lattices): 45.0 ms with rows dealt one by one,
-  // 43.0 ms with runs of >= 8 rows (profiles/r01_sweep_map.log); 64 is used.
+  // 43.0 ms with runs of >= 8 rows (profiles/r01_sweep_map.log); BULK_RCHUNK = 64 is used.
   const int bid = blockIdx.x;
   const int xcd = bid & 7, slot = bid >> 3;
   const int r = slot / nxb;
@@ -325,7 +316,7 @@ __device__ __forceinline__ int bulk_row_of_block(const int nrows, const int nxb,
 }
 
 template <int NL, bool PULL, bool EPHI>
-__global__ void __launch_bounds__(64 * NL, EKPNP_BULK_MIN_WAVES) k_collide_bulk(const KArgs a, const int zl_begin, const int nrows, const int nxb, const int rchunk) {
+__global__ void __launch_bounds__(64 * NL, 1) k_collide_bulk(const KArgs a, const int zl_begin, const int nrows, const int nxb, const int rchunk) {
   int xb;
   const int row = bulk_row_of_block(nrows, nxb, rchunk, xb, a.ny);
   if (row < 0) return;  // whole workgroup leaves together
@@ -334,7 +325,7 @@ __global__ void __launch_bounds__(64 * NL, EKPNP_BULK_MIN_WAVES) k_collide_bulk(
 
 // one plane, a slab's first or last (not a plate): halos straight to / from the exchange buffers
 template <int NL, bool PULL, bool EPHI>
-__global__ void __launch_bounds__(64 * NL, EKPNP_BULK_MIN_WAVES) k_collide_edge(const KArgs a, const int zl, const int nrows, const int nxb, const int rchunk) {
+__global__ void __launch_bounds__(64 * NL, 1) k_collide_edge(const KArgs a, const int zl, const int nrows, const int nxb, const int rchunk) {
   int xb;
   const int row = bulk_row_of_block(nrows, nxb, rchunk, xb);
   if (row < 0) return;
@@ -773,10 +764,10 @@ void launch_init_equilibrium(Ctx& c) {
 }
 
 // rows per band of the interior sweep in effect (0: plane after plane): Ctx::bulk_yband, or the rule above bulk_dispatch's launch
-int bulk_band_rows(const Ctx& c, int rchunk) {
+int bulk_band_rows(const Ctx& c) {
   int yband = c.bulk_yband;
   if (yband < 0) yband = (size_t)c.p.nx * c.p.ny * (size_t)(c.p.n_lattices * 27 * 16 + 80) > ((size_t)192 << 20) ? 128 : 0;
-  return yband > 0 && yband < 0x7fff && yband < c.p.ny && c.p.ny % yband == 0 && yband % rchunk == 0 ? yband : 0;
+  return yband > 0 && yband < 0x7fff && yband < c.p.ny && c.p.ny % yband == 0 && yband % BULK_RCHUNK == 0 ? yband : 0;
 }
 
 template <int NL>
@@ -784,10 +775,8 @@ static void bulk_dispatch(Ctx& c, const KArgs& a, int zl_begin, int zl_end) {
   const int nrows = (zl_end - zl_begin) * c.p.ny;
   if (nrows <= 0) return;
   const int nxb = (c.p.nx + 63) / 64;
-  static const int rchunk_env = std::getenv("EKPNP_BULK_RCHUNK") ? std::atoi(std::getenv("EKPNP_BULK_RCHUNK")) : 64;  // tuning knob
-  int rchunk = rchunk_env < 1 ? 1 : (rchunk_env > 0xffff ? 0xffff : rchunk_env);
   // rows per XCD, rounded up to whole runs: the 8 XCDs together cover [0, 8*per_xcd) >= nrows
-  const long long per_xcd = ((long long)nrows + 8LL * rchunk - 1) / (8LL * rchunk) * rchunk;
+  const long long per_xcd = ((long long)nrows + 8LL * BULK_RCHUNK - 1) / (8LL * BULK_RCHUNK) * BULK_RCHUNK;
   dim3 g((unsigned)(8 * per_xcd * nxb)), b(64 * NL);
   // y bands (bulk_row_of_block; in-place contexts: inside each of the sweep's launches of `zchunk` planes - a launch writes only
   // where no plane it reads lies, whatever the order of its workgroups).  The
@@ -797,7 +786,7 @@ static void bulk_dispatch(Ctx& c, const KArgs& a, int zl_begin, int zl_end) {
   // slab (bands of 64 and 256 rows gain about half of that; profiles/r05c_ab_bulk_yband*.jsonl).  Same arithmetic per node,
   // another order of the workgroups: same bits.  Default (-1): bands of 128 rows where a plane's sweep moves more than
   // 192 MiB and NY is a multiple of 128; smaller planes (256 x 256: 90 - 118 MB) are within the cache's reach as they are.
-  rchunk |= bulk_band_rows(c, rchunk) << 16;
+  const int rchunk = BULK_RCHUNK | bulk_band_rows(c) << 16;
   const bool ephi = collide_takes_e_from_phi(c);
   if (c.streamed_state) {
     if (ephi) hipLaunchKernelGGL((k_collide_bulk<NL, false, (NL > 1)>), g, b, 0, c.stream, a, zl_begin, nrows, nxb, rchunk);
@@ -811,7 +800,7 @@ static void bulk_dispatch(Ctx& c, const KArgs& a, int zl_begin, int zl_end) {
 
 template <int NL>
 static void edge_dispatch(Ctx& c, const KArgs& a, int zl) {
-  const int nrows = c.p.ny, nxb = (c.p.nx + 63) / 64, rchunk = 64;
+  const int nrows = c.p.ny, nxb = (c.p.nx + 63) / 64, rchunk = BULK_RCHUNK;
   const long long per_xcd = ((long long)nrows + 8LL * rchunk - 1) / (8LL * rchunk) * rchunk;
   dim3 g((unsigned)(8 * per_xcd * nxb)), b(64 * NL);
   const bool ephi = collide_takes_e_from_phi(c);
@@ -827,7 +816,7 @@ static void edge_dispatch(Ctx& c, const KArgs& a, int zl) {
 
 template <int NL>
 static void faces_dispatch(Ctx& c, const KArgs& lo, const KArgs& hi, int lo_plate, int hi_plate) {
-  const int nrows = 2 * c.p.ny, nxb = (c.p.nx + 63) / 64, rchunk = 64;
+  const int nrows = 2 * c.p.ny, nxb = (c.p.nx + 63) / 64, rchunk = BULK_RCHUNK;
   const long long per_xcd = ((long long)nrows + 8LL * rchunk - 1) / (8LL * rchunk) * rchunk;
   dim3 g((unsigned)(8 * per_xcd * nxb)), b(64 * NL);
   const bool ephi = collide_takes_e_from_phi(c);
@@ -862,7 +851,7 @@ void launch_collide_bulk_edge(Ctx& c, const KArgs& a, int zl) {
 template <int NL>
 static void all_dispatch(Ctx& c, const KArgs& a) {
   const int nrows_bulk = (c.nzl - 2) * c.p.ny, nrows = nrows_bulk + 2 * c.p.ny;
-  const int nxb = (c.p.nx + 63) / 64, rchunk = 64;
+  const int nxb = (c.p.nx + 63) / 64, rchunk = BULK_RCHUNK;
   const long long per_xcd = ((long long)nrows + 8LL * rchunk - 1) / (8LL * rchunk) * rchunk;
   dim3 g((unsigned)(8 * per_xcd * nxb)), b(64 * NL);
   const bool ephi = collide_takes_e_from_phi(c);

@@ -54,32 +54,25 @@ int plane_fft_setup(Ctx& c) {
 // The transforms in pieces, for the slab solve with mode blocks (own passes only; with rocFFT plans the 2-D transform is one
 // call, issued with the first / last piece): forward = rows of all planes, then the columns of block k; inverse = the columns
 // of block k, then the rows of all planes.
-// (z0, nz: a run of the transform's planes, for the plane chunks of a single context's solve - "poisson_zchunk"; nz < 0: all)
-int plane_fft_forward_rows(Ctx& c, int z0, int nz) {
+int plane_fft_forward_rows(Ctx& c) {
   if (!c.own_fft) return plane_fft_forward(c);
-  if (nz < 0) { z0 = 0; nz = c.fft_nz; }
-  fft_x_forward(c.fft_in() + (size_t)z0 * c.plane, reinterpret_cast<double2*>(c.fft_spec()) + (size_t)z0 * c.p.ny * c.nxh, c.fft_tw, c.p.nx, c.nxh,
-                (long long)c.p.ny * nz, c.stream);
+  fft_x_forward(c.fft_in(), reinterpret_cast<double2*>(c.fft_spec()), c.fft_tw, c.p.nx, c.nxh, (long long)c.p.ny * c.fft_nz, c.stream);
   note_launch(c, "k_fft_x_r2c");
   return EKPNP_OK;
 }
-void plane_fft_forward_columns(Ctx& c, const ModeBlock& b, int z0, int nz) {
+void plane_fft_forward_columns(Ctx& c, const ModeBlock& b) {
   if (!c.own_fft) return;
-  if (nz < 0) { z0 = 0; nz = c.fft_nz; }
-  fft_y_launch(reinterpret_cast<double2*>(c.fft_spec()) + (size_t)z0 * c.p.ny * c.nxh, c.fft_tw + c.p.nx, c.p.ny, c.nxh, nz, -1, c.stream, b.x0 / 8, b.bw / 8);
+  fft_y_launch(reinterpret_cast<double2*>(c.fft_spec()), c.fft_tw + c.p.nx, c.p.ny, c.nxh, c.fft_nz, -1, c.stream, b.x0 / 8, b.bw / 8);
   note_launch(c, "k_fft_y<-1>");
 }
-void plane_fft_inverse_columns(Ctx& c, const ModeBlock& b, int z0, int nz) {
+void plane_fft_inverse_columns(Ctx& c, const ModeBlock& b) {
   if (!c.own_fft) return;
-  if (nz < 0) { z0 = 0; nz = c.fft_nz; }
-  fft_y_launch(reinterpret_cast<double2*>(c.fft_spec()) + (size_t)z0 * c.p.ny * c.nxh, c.fft_tw + c.p.nx, c.p.ny, c.nxh, nz, +1, c.stream, b.x0 / 8, b.bw / 8);
+  fft_y_launch(reinterpret_cast<double2*>(c.fft_spec()), c.fft_tw + c.p.nx, c.p.ny, c.nxh, c.fft_nz, +1, c.stream, b.x0 / 8, b.bw / 8);
   note_launch(c, "k_fft_y<1>");
 }
-int plane_fft_inverse_rows(Ctx& c, int z0, int nz) {
+int plane_fft_inverse_rows(Ctx& c) {
   if (!c.own_fft) return plane_fft_inverse(c);
-  if (nz < 0) { z0 = 0; nz = c.fft_nz; }
-  fft_x_inverse(reinterpret_cast<const double2*>(c.fft_spec()) + (size_t)z0 * c.p.ny * c.nxh, c.fft_out() + (size_t)z0 * c.plane, c.fft_tw, c.p.nx, c.nxh,
-                (long long)c.p.ny * nz, c.stream);
+  fft_x_inverse(reinterpret_cast<const double2*>(c.fft_spec()), c.fft_out(), c.fft_tw, c.p.nx, c.nxh, (long long)c.p.ny * c.fft_nz, c.stream);
   note_launch(c, "k_fft_x_c2r");
   return EKPNP_OK;
 }
@@ -175,17 +168,11 @@ __global__ void k_build_cprime(double* cprime, int nx, int ny, int nz, int nxh, 
 constexpr int TRI_BS = TRI_CHECK;
 // The solution rows are not read again before the inverse transform has gone through all of them:
 // non-temporal stores (0.744 -> 0.723 ms on 512^3; non-temporal LOADS in the forward sweep change
-// nothing: profiles/r02_tridiag_variants.log).  EKPNP_TRI_PLAIN_STORE builds the A/B partner.
-#ifndef EKPNP_TRI_PLAIN_STORE
+// nothing: profiles/r02_tridiag_variants.log).
 #define TRI_STORE(ptr, v) do { double2 v_ = (v); __builtin_nontemporal_store(v_.x, &(ptr)->x); __builtin_nontemporal_store(v_.y, &(ptr)->y); } while (0)
-#else
-#define TRI_STORE(ptr, v) (*(ptr) = (v))
-#endif
 #define TRI_LOAD_FWD(ptr) (*(ptr))
-#ifndef EKPNP_TRI_THREADS
-#define EKPNP_TRI_THREADS 64  // tuning knob: modes (threads) per workgroup of the z solve
-#endif
-__global__ void __launch_bounds__(EKPNP_TRI_THREADS) k_tridiag(PArgs a) {
+constexpr int TRI_THREADS = 64;  // modes (threads) per workgroup of the z solve
+__global__ void __launch_bounds__(TRI_THREADS) k_tridiag(PArgs a) {
   const int m = blockIdx.x * blockDim.x + threadIdx.x;
   const long long ms = (long long)a.ny * a.nxh;
   if (m >= ms) return;
@@ -281,14 +268,10 @@ __global__ void __launch_bounds__(EKPNP_TRI_THREADS) k_tridiag(PArgs a) {
 // tests/test_parity_gpu.py::test_partition_z_solve_extreme_anisotropy compares it with the serial IEEE-division
 // sweeps at dz/dx = 1e-3 and 1e3.
 __device__ __forceinline__ double recip(double x) {
-#ifdef EKPNP_TRI_IEEE_DIV
-  return 1.0 / x;
-#else
   double r = __builtin_amdgcn_rcp(x);
   r = fma(fma(-x, r, 1.0), r, r);
   r = fma(fma(-x, r, 1.0), r, r);
   return r;
-#endif
 }
 // The body serves the single context (rows = planes 1 .. NZ-2, zero beyond both ends) and, since round 3, a z slab
 // (rows = the slab's own unknown rows; x just below the first and just above the last row are the interface values
@@ -301,12 +284,12 @@ __device__ __forceinline__ double recip(double x) {
 // 4 (5) levels and serves all of them at once, and a workgroup covers 32 (16) adjacent modes: 512 (256) contiguous
 // bytes per row.
 // ---- the pieces of the partition solve (shared by the one-shot kernels and the pipelined ones below) ---------------------
-template <int R, int LANES, int NW = 8>
+template <int R, int LANES>
 struct TriPart {
   static constexpr int MPW = 64 / LANES;        // modes per wavefront
-  static constexpr int MC = NW * MPW;           // modes (LDS columns) per workgroup of NW wavefronts (8; 16: twice as wide pieces of every row)
+  static constexpr int MC = 8 * MPW;            // modes (LDS columns) per workgroup of 8 wavefronts
   static_assert(LANES * R <= 512 && 64 % LANES == 0, "a column has LANES x R row slots");
-  static constexpr int TR = 64 * NW / MC;       // rows loaded per pass of the workgroup
+  static constexpr int TR = 64 * 8 / MC;        // rows loaded per pass of the workgroup
   static constexpr int FM = (MC < 16 ? MC : 16) - 1;  // the column index is XOR-ed with the owning lane (mod 16 columns = 256 bytes of banks)
   static constexpr int IMAGE = LANES * R * MC;  // double2 elements of one LDS image [LANES R slots][MC columns] = R x 8 KB
 
@@ -345,9 +328,9 @@ struct TriPart {
 
 // the solve proper, on an LDS image: every lane takes its R rows out of the image, eliminates, takes part in the cyclic
 // reduction of the interface rows and puts its R solution rows back
-template <int R, int LANES, bool SLAB, int NW = 8>
+template <int R, int LANES, bool SLAB>
 __device__ __forceinline__ void tridiag_part_solve(const PArgs& a, double2* __restrict__ img, const long long m0, const int n, const double* __restrict__ bound) {
-  using TP = TriPart<R, LANES, NW>;
+  using TP = TriPart<R, LANES>;
   constexpr int MPW = TP::MPW, MC = TP::MC, FM = TP::FM;
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int l = lane % LANES;                 // lane within its mode: owns slots R l .. R l + R - 1
@@ -441,10 +424,10 @@ __device__ __forceinline__ void tridiag_part_solve(const PArgs& a, double2* __re
   mine[(R - 1) * MC] = make_double2(yx * a.inv_nxny, yy * a.inv_nxny);
 }
 
-template <int R, int LANES, bool SLAB, int NW = 8>
+template <int R, int LANES, bool SLAB>
 __device__ __forceinline__ void tridiag_part_body(const PArgs& a, double2* __restrict__ rows, const int n, const double* __restrict__ bound) {
-  using TP = TriPart<R, LANES, NW>;
-  extern __shared__ double2 tp_lds[];    // [LANES R slots][MC columns] = R x NW KB
+  using TP = TriPart<R, LANES>;
+  extern __shared__ double2 tp_lds[];    // [LANES R slots][MC columns] = R x 8 KB
   const long long ms = (long long)a.ny * a.nxh;
   const long long m0 = (long long)blockIdx.x * TP::MC;  // numbered within the kernel's mode block (block_mode)
   const long long mcol = block_mode(a, m0 + threadIdx.x % TP::MC);
@@ -454,24 +437,24 @@ __device__ __forceinline__ void tridiag_part_body(const PArgs& a, double2* __res
     TP::put(tp_lds, v);
   }
   __syncthreads();
-  tridiag_part_solve<R, LANES, SLAB, NW>(a, tp_lds, m0, n, bound);
+  tridiag_part_solve<R, LANES, SLAB>(a, tp_lds, m0, n, bound);
   __syncthreads();
   TP::store(rows, ms, mcol, n, tp_lds);
 }
 
 // What bounds this kernel, with counters, and the five restructurings that were built, measured and removed again in round 4
-// (pipelined with register prefetch, wave-specialised, early-exit reduction, chain-free pivots; 16 modes per workgroup stays
-// as the tri_wide knob): DESIGN.md section 4 - the access pattern (510 pieces of 128 bytes, a plane apart, per workgroup),
-// 4.4 TB/s, which a plain copy of that shape does not beat either.
-template <int R, int LANES = 64, int NW = 8>
-__global__ void __launch_bounds__(64 * NW) k_tridiag_part(PArgs a) {
-  tridiag_part_body<R, LANES, false, NW>(a, a.spec + (long long)a.ny * a.nxh, a.nz - 2, nullptr);
+// (pipelined with register prefetch, wave-specialised, early-exit reduction, chain-free pivots, 16 modes per workgroup):
+// DESIGN.md section 4 - the access pattern (510 pieces of 128 bytes, a plane apart, per workgroup), 4.4 TB/s, which a plain
+// copy of that shape does not beat either.
+template <int R, int LANES = 64>
+__global__ void __launch_bounds__(512) k_tridiag_part(PArgs a) {
+  tridiag_part_body<R, LANES, false>(a, a.spec + (long long)a.ny * a.nxh, a.nz - 2, nullptr);
 }
 
 // z slab: the same solve on the slab's m unknown rows (first one on local plane row_a), spectrum read once
-template <int R, int LANES = 64, int NW = 8>
-__global__ void __launch_bounds__(64 * NW) k_slab_part(PArgs a, int row_a, int m, const double* __restrict__ bound) {
-  tridiag_part_body<R, LANES, true, NW>(a, a.spec + (long long)row_a * a.ny * a.nxh, m, bound);
+template <int R, int LANES = 64>
+__global__ void __launch_bounds__(512) k_slab_part(PArgs a, int row_a, int m, const double* __restrict__ bound) {
+  tridiag_part_body<R, LANES, true>(a, a.spec + (long long)row_a * a.ny * a.nxh, m, bound);
 }
 
 // Short channels (NZ - 2 <= 64 unknown rows, e.g. the reference's own 51 planes): the serial
@@ -524,10 +507,7 @@ __global__ void __launch_bounds__(256) k_tridiag_pcr64(PArgs a) {
 // planes marched per thread: 16 on large lattices (no measurable difference between 1 and 64
 // there, profiles/r01_sweep_phi_zchunk.log), 1 on small ones where the serial chain of a column
 // would be the whole run time of the kernel
-#ifndef EKPNP_PHI_ZCHUNK
-#define EKPNP_PHI_ZCHUNK 16  // A/B knob
-#endif
-constexpr int PHI_ZCHUNK_LARGE = EKPNP_PHI_ZCHUNK;
+constexpr int PHI_ZCHUNK_LARGE = 16;
 
 // One thread marches up a column of PHI_ZCHUNK planes with phi(z-1), phi(z), phi(z+1) in
 // registers: every phi value is read once for the three z uses (the x+-1 / y+-1 neighbours come
@@ -546,11 +526,8 @@ constexpr int PHI_ZCHUNK_LARGE = EKPNP_PHI_ZCHUNK;
 typedef double pair8 __attribute__((ext_vector_type(2), aligned(8)));
 __device__ __forceinline__ void store_pair(double* p, double a, double b) {
   pair8 v = {a, b};
-#ifndef EKPNP_PHI_PLAIN_STORE  // E is next read by the collide of the following step, tens of ms later:
+  // E is next read by the collide of the following step, tens of ms later:
   __builtin_nontemporal_store(v, reinterpret_cast<pair8*>(p));  // non-temporal (814 vs 823-848 us, profiles/r02_phi_variants.log)
-#else
-  *reinterpret_cast<pair8*>(p) = v;
-#endif
 }
 __device__ __forceinline__ double2 load_pair(const double* p) {
   const pair8 v = *reinterpret_cast<const pair8*>(p);
@@ -1064,11 +1041,6 @@ int build_cprime(Ctx& c) {
 // Slabs of up to 512 unknown rows take the read-once pair (k_slab_edges + k_slab_part: the spectrum is read once for
 // the solve, plus the few rows at either end of the block for the edge values); taller slabs and
 // ekpnp_tune(ctx, "tri_partition", 0) (the A/B partner) keep the serial pair k_slab_thomas_local + k_slab_reduce_correct.
-// EKPNP_TRI_WIDE_MODES=0: one wavefront per mode also on short columns (the A/B partner of LANES = 16 / 32)
-static inline bool wide_modes() {
-  static const bool on = !(std::getenv("EKPNP_TRI_WIDE_MODES") && std::atoi(std::getenv("EKPNP_TRI_WIDE_MODES")) == 0);
-  return on;
-}
 static inline bool slab_read_once(const Ctx& c) { return c.tri_partition > 0 && c.tri_lds_ok && c.nxh % 8 == 0 && c.slab_m >= 1 && c.slab_m <= 512; }
 
 // ---- mode blocks of the slab z solve ("edge_chunks", ekpnp_internal.h: Ctx::edge_chunks) --------------------------------
@@ -1082,9 +1054,9 @@ static inline bool slab_read_once(const Ctx& c) { return c.tri_partition > 0 && 
 // (ny 8 gu a multiple of 32 modes; gu = 1 on every lattice with ny a multiple of 4), the same units on every rank.
 static int slab_part_modes(const Ctx& c) {  // modes per workgroup of the k_slab_part instantiation this slab runs
   const int m = c.slab_m, nm = c.p.ny * c.nxh;
-  if (m <= 128) return wide_modes() && nm % 32 == 0 ? 32 : 8;
-  if (m <= 256) return wide_modes() && nm % 16 == 0 ? 16 : 8;
-  return c.tri_wide && nm % 16 == 0 ? 16 : 8;
+  if (m <= 128) return nm % 32 == 0 ? 32 : 8;
+  if (m <= 256) return nm % 16 == 0 ? 16 : 8;
+  return 8;
 }
 static int gcd_int(int a, int b) { return b == 0 ? a : gcd_int(b, a % b); }
 static int block_unit_groups(const Ctx& c) {
@@ -1159,10 +1131,7 @@ void launch_slab_reduce_correct(Ctx& c, int k) {
     else if (m <= 128) SLAB_PART(2, 64, 8, "2");
     else if (m <= 256 && mc == 16) SLAB_PART(8, 32, 16, "8,32");
     else if (m <= 256) SLAB_PART(4, 64, 8, "4");
-    else if (mc == 16) {
-      hipLaunchKernelGGL((k_slab_part<8, 64, 16>), dim3(nm / 16), dim3(1024), 16 * 8192, c.stream, a, c.slab_row_a, m, bound);
-      note_launch(c, "k_slab_part<8,64,16>");
-    } else SLAB_PART(8, 64, 8, "8");
+    else SLAB_PART(8, 64, 8, "8");
 #undef SLAB_PART
     return;
   }
@@ -1201,13 +1170,6 @@ bool tridiag_prepare_device() {
   if (e != hipSuccess) { (void)hipGetLastError(); return false; }
   return true;
 }
-// the 16-wavefront forms (128 KB of LDS): a device that does not grant it keeps the 8-wavefront kernels
-bool tridiag_wide_prepare_device() {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tridiag_part<8, 64, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, 16 * 8192);
-  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_slab_part<8, 64, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, 16 * 8192);
-  if (e != hipSuccess) { (void)hipGetLastError(); return false; }
-  return true;
-}
 
 // launch + name of one instantiation of the partition solve
 #define TRI_PART(RR, LL, GROUP, NAME)                                                                                            \
@@ -1239,12 +1201,6 @@ int poisson_block_count(const Ctx& c) {
   const int gu = block_unit_groups(c), units = (c.nxh / 8 + gu - 1) / gu;
   return want > units ? units : want;
 }
-ModeBlock poisson_block_whole(const Ctx& c) {
-  ModeBlock b{};
-  b.x0 = 0;
-  b.bw = c.nxh;
-  return b;
-}
 ModeBlock poisson_block(const Ctx& c, int k) {
   ModeBlock b{};
   const int groups = c.nxh / 8, gu = block_unit_groups(c), units = (groups + gu - 1) / gu, nb = poisson_block_count(c);
@@ -1269,20 +1225,16 @@ void launch_tridiag(Ctx& c, const ModeBlock* blk) {
   if (rows <= 64) {
     hipLaunchKernelGGL(k_tridiag_pcr64, dim3((nm + 3) / 4), dim3(256), 0, c.stream, a);
     note_launch(c, "k_tridiag_pcr64");
-  } else if (part && large && rows <= 128 && wide_modes() && nm % 32 == 0) {
+  } else if (part && large && rows <= 128 && nm % 32 == 0) {
     TRI_PART(8, 16, 32, "8,16");
-  } else if (part && large && rows <= 256 && wide_modes() && nm % 16 == 0) {
+  } else if (part && large && rows <= 256 && nm % 16 == 0) {
     TRI_PART(8, 32, 16, "8,32");
   } else if (part && large && rows <= 256) {
     TRI_PART(4, 64, 8, "4");
-  } else if (part && large && rows <= 512 && c.tri_wide && nm % 16 == 0) {
-    // 16 wavefronts = 16 adjacent modes per workgroup: every row is read and written in 256-byte pieces instead of 128-byte ones
-    hipLaunchKernelGGL((k_tridiag_part<8, 64, 16>), dim3(nb / 16), dim3(1024), 16 * 8192, c.stream, a);
-    note_launch(c, "k_tridiag_part<8,64,16>");
   } else if (part && large && rows <= 512) {
     TRI_PART(8, 64, 8, "8");
   } else {
-    hipLaunchKernelGGL(k_tridiag, dim3((nm + EKPNP_TRI_THREADS - 1) / EKPNP_TRI_THREADS), dim3(EKPNP_TRI_THREADS), 0, c.stream, a);
+    hipLaunchKernelGGL(k_tridiag, dim3((nm + TRI_THREADS - 1) / TRI_THREADS), dim3(TRI_THREADS), 0, c.stream, a);
     note_launch(c, "k_tridiag");
   }
 }
@@ -1295,12 +1247,9 @@ void launch_phi_efield(Ctx& c) {
   const int zchunk = small ? 1 : PHI_ZCHUNK_LARGE;
   const int nrows = c.p.ny * ((c.nzl + zchunk - 1) / zchunk);
   const long long per_xcd = ((long long)nrows + 8 * 64 - 1) / (8 * 64) * 64;
-  static const bool no_x2 = std::getenv("EKPNP_PHI_X1") != nullptr;  // A/B knob: the one-node-per-lane kernel everywhere
-  if (!small && !no_x2 && c.p.nx % 128 == 0) {  // whole waves of node pairs
-#ifndef EKPNP_PHI_X2_THREADS
-#define EKPNP_PHI_X2_THREADS 256  // A/B knob
-#endif
-    const int bx = c.p.nx >= 2 * EKPNP_PHI_X2_THREADS ? EKPNP_PHI_X2_THREADS : c.p.nx / 2;  // threads per block, each two nodes
+  if (!small && c.p.nx % 128 == 0) {  // whole waves of node pairs
+    constexpr int X2_THREADS = 256;
+    const int bx = c.p.nx >= 2 * X2_THREADS ? X2_THREADS : c.p.nx / 2;  // threads per block, each two nodes
     const int nxb = (c.p.nx + 2 * bx - 1) / (2 * bx);  // the last block of a row may be partly idle (whole waves: nx % 128 == 0)
     hipLaunchKernelGGL(k_phi_efield_x2<PHI_ZCHUNK_LARGE>, dim3((unsigned)(8 * per_xcd * nxb)), dim3(bx), 0, c.stream, a, nxb, nrows);
     note_launch(c, "k_phi_efield_x2<PHI_ZCHUNK_LARGE>");

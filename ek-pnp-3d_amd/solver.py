@@ -472,7 +472,7 @@ class Solver:
 
     def pass_order(self) -> dict:
         """the cache-aware orders in effect: {"band_rows": rows per band of the interior sweep (0: plane after plane),
-        "poisson_blocks": kx column blocks of the solve's middle passes, "poisson_zchunk": planes per chunk of its row + column passes}"""
+        "poisson_blocks": kx column blocks of the solve's middle passes, "poisson_zchunk": always 0 (plane chunks are retired)}"""
         b, nb, zc = C.c_int(), C.c_int(), C.c_int()
         self._ck(self._L.ekpnp_pass_order(self._h, C.byref(b), C.byref(nb), C.byref(zc)))
         return {"band_rows": b.value, "poisson_blocks": nb.value, "poisson_zchunk": zc.value}

@@ -264,22 +264,17 @@ int ekpnp_placement_report(ekpnp_ctx* ctx, int* n_tried, int* chosen, double* sw
  * copy of `bytes` bytes on the context's stream: the secondary denominator SURVEY.md 8(d) asks
  * for next to the 8 TB/s spec figure.  Allocates and frees 2 x `bytes` of scratch. */
 int ekpnp_copy_bandwidth(ekpnp_ctx* ctx, size_t bytes, double* gb_per_s);
-/* Launch-shape knobs of a live context, for tuning sweeps (tools/sweep_zchunk.py).  "ab_zchunk":
- * planes per launch of the two-buffer collide sweep (0 = the whole sweep in one launch).
+/* Launch-shape knobs of a live context, for tuning sweeps.
  * "merged_walls": 1 (default) = lattices of up to 4 M nodes collide plates and bulk in ONE launch,
  * 0 = always separate launches (what large lattices, in-place contexts and slabs do anyway); same
  * results bit for bit.  "tri_partition": the z solve of a single context - 0 = the serial Thomas sweeps
  * everywhere, 1 (default) = the partition solve (spectrum read once) on large lattices of 67 to 514 planes,
  * 2 = wherever it applies; the two solve the same system in a different elimination order (equal to rounding).
- * "tri_wide": 1 = 16 modes (wavefronts) per workgroup on columns of more than 256 rows (256-byte pieces of every row; 3 %
- * faster in isolation, default 0), same bits.
  * "bulk_yband" (EKPNP_BULK_YBAND): the interior sweep takes bands of that many rows of EVERY plane, band after band, instead of
  * plane after plane, so that the phi rows the collide reads three times (as z+1, z, z-1: E is formed from phi) are still in
  * the 256 MiB Infinity Cache when they come back.  -1 (default) = bands of 128 rows where the sweep of one plane moves more
  * than 192 MiB (cfg3: bulk kernel 38.69 -> 38.45 ms) and plane order elsewhere, 0 = plane order, n = bands of n rows (a
  * multiple of 64 that divides NY; anything else is ignored).  Another order of the workgroups: same bits.
- * "poisson_zchunk" (EKPNP_POISSON_ZCHUNK, default 0 = off): rows + columns of runs of that many planes back to back - the
- * measured alternative to "poisson_blocks" (gains less); same bits.
  * "poisson_blocks" (EKPNP_POISSON_BLOCKS; single contexts on 512- / 1024-wide planes whose z solve is the partition solve):
  * the solve's three middle passes - y forward, z solve, y inverse - taken kx block by kx block, the three passes of one block
  * back to back, so that part of a block is still in the 256 MiB Infinity Cache when the next pass wants it.  0 (default) = the
@@ -312,7 +307,9 @@ int ekpnp_copy_bandwidth(ekpnp_ctx* ctx, size_t bytes, double* gb_per_s);
  *     with every peer (plus a device copy of the rank's own piece) instead of ncclAllGather: on xGMI every peer is one hop
  *     away on a link of its own, so a rank's piece leaves on all links at once.  The pieces land where the all-gather puts
  *     them: same bits.  Which of the two is faster between devices only a multi-GPU run can say (a `comm_ab` leg).
- * bench.py runs a few steps under each of these after its timed region on N > 1 GPUs (`comm_ab`). */
+ * bench.py runs a few steps under each of these after its timed region on N > 1 GPUs (`comm_ab`).
+ * Any other name or an out-of-range value returns EKPNP_ERR_INVALID ("unknown knob or bad value"), the retired
+ * "ab_zchunk", "tri_wide" and "poisson_zchunk" included. */
 int ekpnp_tune(ekpnp_ctx* ctx, const char* knob, int value);
 /* Every kernel launch of the library is checked: a rejected launch makes the entry point return
  * EKPNP_ERR_HIP with the KERNEL's name in ekpnp_last_error.  With EKPNP_DEBUG_SYNC set in the
@@ -411,11 +408,11 @@ int ekpnp_rccl_available(void);
  * and that with GPU_MAX_HW_QUEUES=1 both transforms run at full speed (42.8 / 44.0 ms per step).  The library prints this
  * advice once when ranks_on_device > 1 and the variable is unset; bench.py --single-device and the test workers set it. */
 int ekpnp_plane_transforms(const ekpnp_ctx* ctx, int* own_passes, int* ranks_on_device);
-/* The orders in effect that keep re-used rows in the Infinity Cache (ekpnp_tune "bulk_yband", "poisson_blocks", "poisson_zchunk";
+/* The orders in effect that keep re-used rows in the Infinity Cache (ekpnp_tune "bulk_yband", "poisson_blocks";
  * no reference counterpart: one thread per node in plane order, LBM.cu:474, and one 3-D transform, poisson.cu:86): *band_rows =
  * rows per band of the interior sweep (0: plane after plane), *poisson_blocks = kx column blocks of a single context's solve
- * (1: whole passes; always 1 on a slab), *poisson_zchunk = planes per chunk of its row + column passes (0: whole passes).
- * Any pointer may be NULL. */
+ * (1: whole passes; always 1 on a slab), *poisson_zchunk = always 0 (the plane chunks of the row + column passes were retired;
+ * the output stays for callers that print it).  Any pointer may be NULL. */
 int ekpnp_pass_order(const ekpnp_ctx* ctx, int* band_rows, int* poisson_blocks, int* poisson_zchunk);
 /* Failure semantics of the collective calls (no reference counterpart: the reference exit()s on any error,
  * LBM.cu:35-53).  Once RCCL is bound and the (small, host-side) team object exists, ekpnp_slab_attach_comm always

@@ -136,3 +136,24 @@ print("RC2", rc2)
     assert r.returncode == 0, (r.stdout, r.stderr[-2000:])
     assert "RC 2 MSG ekpnp_comm_unique_id:" in r.stdout and "no_such_librccl.so cannot be loaded" in r.stdout, r.stdout
     assert "RC2 2" in r.stdout
+
+
+def test_environment_knobs_are_the_documented_ones():
+    """Every EKPNP_* variable the library reads is a row of INTEGRATION.md section 8, and every row is read: a settled A/B
+    experiment leaves no environment selector behind.  Nor a compile-time one: csrc/ has no #if / #ifdef / #ifndef on an
+    EKPNP_* macro (the A/B library of an experiment is built with the Makefile's EXTRA, not with switches left in the code)."""
+    csrc = os.path.join(ROOT, "ek-pnp-3d_amd", "csrc")
+    read, switched = set(), []
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".h", ".cpp")):
+            continue
+        for i, line in enumerate(open(os.path.join(csrc, f)), 1):
+            read.update(re.findall(r'getenv\("(EKPNP_[A-Z0-9_]+)"\)', line))
+            if re.match(r"\s*#\s*if(n?def)?\s.*\bEKPNP_", line):
+                switched.append(f"{f}:{i}: {line.strip()}")
+    txt = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    section = re.search(r"^## 8\..*?(?=^## |\Z)", txt, flags=re.S | re.M).group(0)
+    documented = set(re.findall(r"EKPNP_[A-Z0-9_]+", section))
+    assert read, "no getenv(\"EKPNP_...\") found in csrc/"
+    assert read == documented, f"read but not documented: {sorted(read - documented)}; documented but not read: {sorted(documented - read)}"
+    assert not switched, switched

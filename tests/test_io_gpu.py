@@ -299,7 +299,7 @@ sys.path.insert(0, %r)
 import __graft_entry__ as G
 pkg = G.load_package()
 import os
-p = pkg.default_params(16, 8, int(os.environ.get("EKPNP_TEST_NZ", "12"))); p.pb_iterations = 3
+p = pkg.default_params(int(os.environ.get("EKPNP_TEST_NX", "16")), int(os.environ.get("EKPNP_TEST_NY", "8")), int(os.environ.get("EKPNP_TEST_NZ", "12"))); p.pb_iterations = 3
 with pkg.Solver(p) as s:
     try:
         s.initialization(); s.init_equilibrium(); s.step(2)
@@ -318,10 +318,13 @@ with pkg.Solver(p) as s:
     cases = [({"EKPNP_INJECT_LAUNCH_FAILURE": "k_pbe_relax"}, "k_pbe_relax"),
              ({"EKPNP_INJECT_LAUNCH_FAILURE": "k_collide_all"}, "k_collide_all"),  # small lattice: plates + bulk in one launch
              ({"EKPNP_INJECT_LAUNCH_FAILURE": "k_collide_bulk", "EKPNP_NO_MERGED_WALLS": "1"}, "k_collide_bulk")]
-    # the z solve has four kernels; each launch is noted under the name of the kernel that was really launched
-    for nz, knob, kernel, wide in (("12", "1", "k_tridiag_pcr64", "1"), ("300", "2", "k_tridiag_part<8>", "1"), ("131", "2", "k_tridiag_part<8,32>", "1"),
-                                   ("100", "2", "k_tridiag_part<8,16>", "1"), ("131", "2", "k_tridiag_part<4>", "0"), ("300", "0", "k_tridiag", "1")):
-        cases.append(({"EKPNP_INJECT_LAUNCH_FAILURE": kernel, "EKPNP_TEST_NZ": nz, "EKPNP_TRI_PARTITION": knob, "EKPNP_TRI_WIDE_MODES": wide}, kernel))
+    # the z solve has six kernels; each launch is noted under the name of the kernel that was really launched.  The 8 x 7
+    # plane has 56 modes (nxh = 8), not a multiple of 16: its 129-row columns take <4> where the 16 x 8 plane's take <8,32>
+    for nz, knob, kernel, (nx, ny) in (("12", "1", "k_tridiag_pcr64", (16, 8)), ("300", "2", "k_tridiag_part<8>", (16, 8)),
+                                       ("131", "2", "k_tridiag_part<8,32>", (16, 8)), ("100", "2", "k_tridiag_part<8,16>", (16, 8)),
+                                       ("131", "2", "k_tridiag_part<4>", (8, 7)), ("300", "0", "k_tridiag", (16, 8))):
+        cases.append(({"EKPNP_INJECT_LAUNCH_FAILURE": kernel, "EKPNP_TEST_NX": str(nx), "EKPNP_TEST_NY": str(ny), "EKPNP_TEST_NZ": nz,
+                       "EKPNP_TRI_PARTITION": knob}, kernel))
     with ThreadPoolExecutor(max_workers=4) as pool:
         results = list(pool.map(lambda c: run(c[0], tmp_path / ("x_%d.npy" % cases.index(c))), cases))
         a, b = pool.map(lambda eo: run(*eo), [({}, tmp_path / "a.npy"), ({"EKPNP_DEBUG_SYNC": "1"}, tmp_path / "b.npy")])

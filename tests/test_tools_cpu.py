@@ -97,7 +97,7 @@ def test_summarize_profile_arithmetic_on_a_synthetic_profile_directory(tmp_path)
     pmc(src / "calib_write" / "pmc_counter_collection.csv", [(copy8, 1000, true_kib), (shift, 1000, true_kib)])
     sweep = "void ekpnp::k_collide_bulk<4, true, true>(ekpnp::KArgs, int, int, int, int)"
     first = "void ekpnp::k_collide_bulk<4, false, true>(ekpnp::KArgs, int, int, int, int)"
-    wall, tri = "void ekpnp::k_collide_wall<4, true, true>(ekpnp::KArgs)", "void ekpnp::k_tridiag_part<8, 64, 8>(ekpnp::PArgs)"
+    wall, tri = "void ekpnp::k_collide_wall<4, true, true>(ekpnp::KArgs)", "void ekpnp::k_tridiag_part<8, 64>(ekpnp::PArgs)"
     # sweep: two big launches (mean 100 and 200 KiB raw) and a replica launch that must not count
     pmc(src / "pmc_fetch" / "pmc_counter_collection.csv", [(sweep, 64, 1.0), (sweep, 4096, 90.0), (sweep, 4096, 110.0), (first, 4096, 95.0), (wall, 128, 3.0), (tri, 256, 10.0)])
     pmc(src / "pmc_write" / "pmc_counter_collection.csv", [(sweep, 64, 1.0), (sweep, 4096, 200.0), (sweep, 4096, 200.0), (first, 4096, 200.0), (wall, 128, 2.0), (tri, 256, 11.0)])
