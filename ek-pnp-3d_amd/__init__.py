@@ -12,6 +12,8 @@ from .solver import (  # noqa: F401
     FIELD_ID,
     EkpnpError,
     Group,
+    PROFILE_ID,
+    PROFILE_NAMES,
     Params,
     STAGE_NAMES,
     Solver,

@@ -517,6 +517,7 @@ extern "C" int ekpnp_destroy(ekpnp_ctx* ctx) {
   if (c.phi_old) (void)hipFree(c.phi_old);
   if (c.diag) (void)hipFree(c.diag);
   if (c.vwall) (void)hipFree(c.vwall);
+  if (c.stats_part) (void)hipFree(c.stats_part);  // (stats_out and stats_acc lie in the same allocation)
   for (int k = 0; k < 4; ++k) {
     if (c.halo[k]) (void)hipFree(c.halo[k]);
     if (c.phi_halo[k]) (void)hipFree(c.phi_halo[k]);

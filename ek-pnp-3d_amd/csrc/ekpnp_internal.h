@@ -201,6 +201,11 @@ void launch_current(Ctx&, double* scratch);
 void launch_umax(Ctx&, double* scratch);
 void launch_max_abs_diff(Ctx&, const double* p, const double* q, double* scratch);
 void launch_copy16(Ctx&, const void* src, void* dst, size_t bytes);
+// stats.hip: plane sums of the current fields into Ctx::stats_out ([EKPNP_NPROFILES][nzl]); acc != null: acc = acc + them as well
+int stats_workgroups_per_plane(const Ctx&);
+void launch_plane_sums(Ctx&, double* acc);
+// the text file of ekpnp_save_profiles / ekpnp_group_save_profiles: sums is [EKPNP_NPROFILES][nzl], planes z0 .. z0 + nzl - 1
+int stats_write_file(const char* path, const ekpnp_params& p, int z0, int nzl, int samples, double time, const double* sums, std::string& err);
 
 struct Ctx {
   ekpnp_params p{};
@@ -285,6 +290,12 @@ struct Ctx {
   double* phi_old = nullptr;       // PB relaxation state (ekpnp_pbe_begin/end)
   double* diag = nullptr;          // reduction scratch (DIAG_SCRATCH doubles)
   double* vwall = nullptr;         // {voltage, voltage, voltage2, voltage2}
+  // plane profiles (stats.hip), one allocation made on first use: per-workgroup partial sums [nzl][workgroups per plane][EKPNP_NPROFILES],
+  // then the plane sums of the last pass and the running sums of ekpnp_stats_accumulate, [EKPNP_NPROFILES][nzl] each
+  double* stats_part = nullptr;
+  double* stats_out = nullptr;
+  double* stats_acc = nullptr;
+  int stats_samples = 0;           // ekpnp_stats_accumulate calls since the last reset (host side: the calls only enqueue)
   int collide_phase = 0;           // 0 idle, 1 boundary planes done
   // slab edge planes without pack / unpack copies (KArgs::halo_*): knob, and where the current halos are
   bool halo_direct = true;         // EKPNP_HALO_DIRECT=0: k_halo_pack / k_halo_unpack as in rounds 1-3 (the A/B partner)

@@ -59,6 +59,7 @@ int main(int argc, char* argv[]) {
   std::string out = ".";
   double exf = 0.0, uw = 0.0, chargeinf = -1.0, Ra = -1.0, TH = -1.0;
   double converged_tol = 0.0;  // > 0: ekpnp_initialization_converged instead of the reference's fixed 501 Picard sweeps
+  unsigned profiles_every = 0;  // > 0: ekpnp_stats_accumulate after every that many iterations, profiles.dat at the end
   int batch = 0;  // 1: ekpnp_step(n) from one output mark to the next instead of one stream_collide_save + fast_Poisson pair per iteration
   std::vector<std::pair<std::string, int>> tunes;  // --tune knob=value: ekpnp_tune / ekpnp_group_tune right after creation
   for (int i = 1; i < argc; ++i) {
@@ -94,6 +95,7 @@ int main(int argc, char* argv[]) {
     else if ((v = val("--TH"))) TH = std::atof(v);
     else if ((v = val("--converged-init"))) converged_tol = std::atof(v);
     else if ((v = val("--batch"))) batch = std::atoi(v);
+    else if ((v = val("--profiles-every"))) profiles_every = (unsigned)std::atoi(v);
     else if ((v = val("--tune"))) {
       const char* eq = std::strchr(v, '=');
       if (!eq || eq == v) { std::fprintf(stderr, "--tune wants knob=value, got %s\n", v); return 2; }
@@ -104,7 +106,11 @@ int main(int argc, char* argv[]) {
                    "usage: ekpnp_main [--nx N --ny N --nz N] [--steps N] [--nsave N] [--print-current N] [--read-previous 0|1|2]\n"
                    "                  [--binary-state 0|1] [--gpus N [--transport auto|rccl|copy] [--devices d0,d1,...]]\n"
                    "                  [--lattices 1|3|4] [--exf F --uw U --chargeinf C --Ra R --TH T] [--out DIR] [--converged-init TOL]\n"
-                   "                  [--tune knob=value ...] [--batch 0|1]\n"
+                   "                  [--tune knob=value ...] [--batch 0|1] [--profiles-every N]\n"
+                   "  --profiles-every N: after every N-th iteration the plane sums of the fields (z profiles of the fields, their squares,\n"
+                   "  the fluxes uz*T, uz*c, uz*cn and the body force (c - cn)*E; reduced on the device, ekpnp_stats_accumulate) are added to\n"
+                   "  running sums, and the time-averaged plane means go to profiles.dat at the end (ekpnp_save_profiles); every other file is\n"
+                   "  byte for byte what it is without the flag.\n"
                    "  --batch 1: the time loop advances with ONE ekpnp_step(ctx, n) call from each output mark (Tecplot zone, current / umax\n"
                    "  line) to the next, with the knob batch_moments on (only the last step of a call stores rho, u, c, cn, T: nothing looks at\n"
                    "  the steps in between); the same files, byte for byte, as the default loop, which mirrors main.cu:189-224 call by call.\n"
@@ -196,7 +202,7 @@ int main(int argc, char* argv[]) {
     if (batch) {
       // iterations i .. j in one call, j = the next iteration something looks at the fields (or the last one)
       unsigned j = i;
-      while (j + 1 < nsteps && !(j % nsave == 1 || j % print_current == 1)) ++j;
+      while (j + 1 < nsteps && !(j % nsave == 1 || j % print_current == 1 || (profiles_every && (j + 1) % profiles_every == 0))) ++j;
       CK(RUN(step, (int)(j - i + 1)));
       for (unsigned k = i; k <= j; ++k) t = t + P.dt;  // the same additions as the loop below makes, so the files carry the same time
       i = j;
@@ -215,6 +221,7 @@ int main(int argc, char* argv[]) {
       std::printf("Iteration: %u, physical time: %g, Current = %g\n", i, t, I);
       CK(RUN(record_umax, f_umax.c_str(), 1, t));
     }
+    if (profiles_every && (i + 1) % profiles_every == 0) CK(RUN(stats_accumulate));  // enqueues only: the loop runs on
   }
   CK(RUN(synchronize));
   const double runtime = std::chrono::duration<double>(std::chrono::steady_clock::now() - begin).count();
@@ -229,6 +236,7 @@ int main(int argc, char* argv[]) {
   CK(RUN(save_data_tecplot, f_data.c_str(), 1, t, 1));  // main.cu:253
   CK(RUN(save_data_end, f_end.c_str(), 0, t));          // main.cu:256-257
   if (binary_state) CK(RUN(save_state, f_bin.c_str(), t));
+  if (profiles_every) CK(RUN(save_profiles, (out + "/profiles.dat").c_str(), t));
   CK(grp ? ekpnp_group_destroy(grp) : ekpnp_destroy(ctx));    // main.cu:264-290
   return 0;
 }

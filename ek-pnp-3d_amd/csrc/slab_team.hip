@@ -1375,3 +1375,58 @@ extern "C" int ekpnp_group_load_checkpoint(ekpnp_group* g, const char* path, dou
   if (time) *time = h.time;
   return EKPNP_OK;
 }
+
+// ---- plane profiles (stats.hip) over the slabs: a plane lives on one slab, so every slab reduces its own planes on its own device
+// and the host places its columns at z0 of the whole-lattice arrays [EKPNP_NPROFILES][NZ]; nothing is exchanged
+static int team_gather_profiles(Team& T, bool running, double* host, int* samples) {
+  const int nz = S(T, 0).p.nz;
+  std::vector<double> part;
+  for (size_t i = 0; i < T.m.size(); ++i) {
+    int rc = use(T, (int)i);
+    if (rc) return rc;
+    Ctx& c = S(T, (int)i);
+    part.resize((size_t)EKPNP_NPROFILES * c.nzl);
+    int n = 0;
+    THIP(T, hipStreamSynchronize(T.cs[i]));
+    TSLAB(T, (int)i, running ? ekpnp_stats_get(T.m[i], part.data(), &n) : ekpnp_plane_sums(T.m[i], part.data()));
+    if (running && i > 0 && n != *samples) { T.err = "the slabs of this group have taken different numbers of samples"; return EKPNP_ERR_INVALID; }
+    if (running) *samples = n;
+    for (int q = 0; q < EKPNP_NPROFILES; ++q)
+      for (int z = 0; z < c.nzl; ++z) host[(size_t)q * nz + c.z0 + z] = part[(size_t)q * c.nzl + z];
+  }
+  return EKPNP_OK;
+}
+extern "C" int ekpnp_group_plane_sums(ekpnp_group* g, double* host_out) {
+  NEEDLIVEGROUP(g);
+  if (!host_out) { T.err = "NULL pointer"; return EKPNP_ERR_INVALID; }
+  return team_gather_profiles(T, false, host_out, nullptr);
+}
+extern "C" int ekpnp_group_stats_get(ekpnp_group* g, double* host_out, int* n_samples) {
+  NEEDLIVEGROUP(g);
+  if (!host_out || !n_samples) { T.err = "NULL pointer"; return EKPNP_ERR_INVALID; }
+  *n_samples = 0;
+  return team_gather_profiles(T, true, host_out, n_samples);
+}
+static int team_stats_call(Team& T, bool accumulate) {
+  for (size_t i = 0; i < T.m.size(); ++i) {
+    int rc = use(T, (int)i);
+    if (rc) return rc;
+    TSLAB(T, (int)i, accumulate ? ekpnp_stats_accumulate(T.m[i]) : ekpnp_stats_reset(T.m[i]));
+  }
+  return EKPNP_OK;
+}
+extern "C" int ekpnp_group_stats_reset(ekpnp_group* g) { NEEDLIVEGROUP(g); return group_fail(T, team_stats_call(T, false)); }
+// enqueues on every slab's compute stream, which is where the last exchange of a step has been waited for already; a failure
+// leaves some slabs one sample ahead of the others, so it poisons the group like any other verb that computes
+extern "C" int ekpnp_group_stats_accumulate(ekpnp_group* g) { NEEDLIVEGROUP(g); return group_fail(T, team_stats_call(T, true)); }
+extern "C" int ekpnp_group_save_profiles(ekpnp_group* g, const char* path, double time) {
+  NEEDLIVEGROUP(g);
+  if (!path) { T.err = "NULL path"; return EKPNP_ERR_INVALID; }
+  const ekpnp_params& p = S(T, 0).p;
+  std::vector<double> h((size_t)EKPNP_NPROFILES * p.nz);
+  int samples = 0;
+  int rc = team_gather_profiles(T, true, h.data(), &samples);
+  if (rc == EKPNP_OK && samples == 0) rc = team_gather_profiles(T, false, h.data(), nullptr);  // nothing accumulated: the current fields
+  if (rc) return rc;
+  return stats_write_file(path, p, 0, p.nz, samples, time, h.data(), T.err);
+}

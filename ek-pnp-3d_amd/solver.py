@@ -26,6 +26,9 @@ _LIBNAME = "libekpnp.so"
 
 FIELDS = ["rho", "c", "cn", "phi", "ux", "uy", "uz", "Ex", "Ey", "Ez", "T"]
 FIELD_ID = {n: i for i, n in enumerate(FIELDS)}
+# the EKPNP_NPROFILES plane sums of ekpnp_plane_sums, in id order (include/ekpnp.h: EKPNP_PROF_*); q stands for c - cn
+PROFILE_NAMES = FIELDS + ["ux_ux", "uy_uy", "uz_uz", "c_c", "cn_cn", "T_T", "uz_T", "uz_c", "uz_cn", "q_Ex", "q_Ez", "ux_uz", "q_q"]
+PROFILE_ID = {n: i for i, n in enumerate(PROFILE_NAMES)}
 
 
 class EkpnpError(RuntimeError):
@@ -183,6 +186,17 @@ def load_library():
         "ekpnp_group_read_data": (i32, [ctx, C.c_char_p, pd]),
         "ekpnp_group_save_state": (i32, [ctx, C.c_char_p, dbl]),
         "ekpnp_group_read_state": (i32, [ctx, C.c_char_p, pd]),
+        # plane profiles and running statistics
+        "ekpnp_plane_sums": (i32, [ctx, C.c_void_p]),
+        "ekpnp_stats_reset": (i32, [ctx]),
+        "ekpnp_stats_accumulate": (i32, [ctx]),
+        "ekpnp_stats_get": (i32, [ctx, C.c_void_p, C.POINTER(i32)]),
+        "ekpnp_save_profiles": (i32, [ctx, C.c_char_p, dbl]),
+        "ekpnp_group_plane_sums": (i32, [ctx, C.c_void_p]),
+        "ekpnp_group_stats_reset": (i32, [ctx]),
+        "ekpnp_group_stats_accumulate": (i32, [ctx]),
+        "ekpnp_group_stats_get": (i32, [ctx, C.c_void_p, C.POINTER(i32)]),
+        "ekpnp_group_save_profiles": (i32, [ctx, C.c_char_p, dbl]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError if the library does not export it
@@ -417,6 +431,31 @@ class Solver:
         t = C.c_double()
         self._ck(self._L.ekpnp_read_state(self._h, os.fsencode(path), C.byref(t)))
         return t.value
+
+    # -- plane profiles and running statistics (no reference counterpart) --------------------
+    def plane_sums(self) -> np.ndarray:
+        """[len(PROFILE_NAMES)][nz_local]: sums over the nx*ny nodes of each owned plane of the current fields, their
+        squares and the flux / body-force products, reduced on the device (a mean is a sum / (nx*ny))."""
+        out = np.empty((len(PROFILE_NAMES), self.nz_local), dtype=np.float64)
+        self._ck(self._L.ekpnp_plane_sums(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def stats_reset(self):
+        self._ck(self._L.ekpnp_stats_reset(self._h))
+
+    def stats_accumulate(self):
+        """running sums += plane sums of the current fields; enqueues only (place it between two step() calls)"""
+        self._ck(self._L.ekpnp_stats_accumulate(self._h))
+
+    def stats_get(self):
+        """(running sums [len(PROFILE_NAMES)][nz_local], number of samples)"""
+        out, n = np.empty((len(PROFILE_NAMES), self.nz_local), dtype=np.float64), C.c_int()
+        self._ck(self._L.ekpnp_stats_get(self._h, out.ctypes.data_as(C.c_void_p), C.byref(n)))
+        return out, n.value
+
+    def save_profiles(self, path: str, time: float = 0.0):
+        """text file of the time-averaged plane means of the owned planes (ekpnp_save_profiles)"""
+        self._ck(self._L.ekpnp_save_profiles(self._h, os.fsencode(path), float(time)))
 
     def tune(self, knob: str, value: int):
         self._ck(self._L.ekpnp_tune(self._h, knob.encode(), int(value)))
@@ -657,6 +696,26 @@ class Group:
         t = C.c_double()
         self._ck(self._L.ekpnp_group_read_state(self._g, os.fsencode(path), C.byref(t)))
         return t.value
+
+    def plane_sums(self) -> np.ndarray:
+        """[len(PROFILE_NAMES)][NZ]: every slab reduces its own planes on its own device"""
+        out = np.empty((len(PROFILE_NAMES), self.p.nz), dtype=np.float64)
+        self._ck(self._L.ekpnp_group_plane_sums(self._g, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def stats_reset(self):
+        self._ck(self._L.ekpnp_group_stats_reset(self._g))
+
+    def stats_accumulate(self):
+        self._ck(self._L.ekpnp_group_stats_accumulate(self._g))
+
+    def stats_get(self):
+        out, n = np.empty((len(PROFILE_NAMES), self.p.nz), dtype=np.float64), C.c_int()
+        self._ck(self._L.ekpnp_group_stats_get(self._g, out.ctypes.data_as(C.c_void_p), C.byref(n)))
+        return out, n.value
+
+    def save_profiles(self, path: str, time: float = 0.0):
+        self._ck(self._L.ekpnp_group_save_profiles(self._g, os.fsencode(path), float(time)))
 
     def save_checkpoint(self, path: str):
         self._ck(self._L.ekpnp_group_save_checkpoint(self._g, os.fsencode(path)))

@@ -237,6 +237,64 @@ int ekpnp_compute_parameters(const ekpnp_params* p, double* T, double* M, double
  * pad width is floor(log10(nsteps) + 1) like the reference derives from its NSTEPS. */
 int ekpnp_save_scalar(ekpnp_ctx* ctx, const char* name, int field_id, unsigned n, unsigned nsteps);
 
+/* ---- plane profiles and running statistics (no reference counterpart) ---------------------------
+ * What a channel-flow run is plotted by: sums over the nx*ny nodes of every z plane of the fields, their squares
+ * and the convective / body-force products, formed on the device in ONE pass that reads the eleven field arrays
+ * once (88 B per node) - instead of ekpnp_get_field of every field and a loop on the host, the pattern of
+ * main.cu:211-222.  Slabs are cut along z, so a plane lives on one rank and nothing here communicates.
+ * Ids of the EKPNP_NPROFILES sums of a plane; the first eleven are the field ids, q stands for c - cn: */
+enum {
+  EKPNP_PROF_RHO = 0,
+  EKPNP_PROF_C = 1,
+  EKPNP_PROF_CN = 2,
+  EKPNP_PROF_PHI = 3,
+  EKPNP_PROF_UX = 4,
+  EKPNP_PROF_UY = 5,
+  EKPNP_PROF_UZ = 6,
+  EKPNP_PROF_EX = 7,
+  EKPNP_PROF_EY = 8,
+  EKPNP_PROF_EZ = 9,
+  EKPNP_PROF_T = 10,
+  EKPNP_PROF_UX_UX = 11,
+  EKPNP_PROF_UY_UY = 12,
+  EKPNP_PROF_UZ_UZ = 13,
+  EKPNP_PROF_C_C = 14,
+  EKPNP_PROF_CN_CN = 15,
+  EKPNP_PROF_T_T = 16,
+  EKPNP_PROF_UZ_T = 17,   /* convective heat flux            */
+  EKPNP_PROF_UZ_C = 18,   /* convective ion fluxes           */
+  EKPNP_PROF_UZ_CN = 19,
+  EKPNP_PROF_Q_EX = 20,   /* body force (c - cn) E           */
+  EKPNP_PROF_Q_EZ = 21,
+  EKPNP_PROF_UX_UZ = 22,  /* Reynolds shear stress           */
+  EKPNP_PROF_Q_Q = 23,    /* (c - cn)^2                      */
+  EKPNP_NPROFILES = 24
+};
+/* The sums of this context's planes of the fields as ekpnp_get_field would return them at this moment (the
+ * pre-collision moments of the last sweep, LBM.cu:807-813, phi and E of the last solve - a lazy solve's E arrays
+ * are brought up to date first; wall planes included, no extrapolation), into host_out[EKPNP_NPROFILES][nz_local].
+ * Nothing is normalised: a mean is a sum / (nx*ny).  Complete on return.
+ * Reproducibility: no atomics; the order in which the terms of a plane are added depends on nx and ny ONLY (fixed
+ * runs of nodes per workgroup, fixed trees inside, the workgroups' partial sums added in ascending order), so a
+ * plane's sums are the same bits in a two-buffer, an in-place, a slab context and a group of any size. */
+int ekpnp_plane_sums(ekpnp_ctx* ctx, double* host_out);
+/* Running sums over time, kept on the device: reset zeroes them and the sample count; accumulate adds the plane sums
+ * of the current fields (acc = acc + sample per entry, in call order) and counts one sample - it ONLY ENQUEUES on the
+ * context's stream and never waits for it, so it can sit between two ekpnp_step calls of a batched loop; get copies
+ * the running sums ([EKPNP_NPROFILES][nz_local]) and the count out (zeros and 0 before the first accumulate).
+ * Device memory (partial sums, one result and one running array) is allocated on first use and counted by
+ * ekpnp_device_bytes.  The running sums are NOT part of ekpnp_save_checkpoint / ekpnp_save_state files. */
+int ekpnp_stats_reset(ekpnp_ctx* ctx);
+int ekpnp_stats_accumulate(ekpnp_ctx* ctx);
+int ekpnp_stats_get(ekpnp_ctx* ctx, double* host_out, int* n_samples);
+/* Text file of the time-averaged plane means of this context's planes (a slab: its own planes, one file per rank,
+ * like ekpnp_save_state).  Line 1: "# ekpnp profiles nx <nx> ny <ny> nz <nz> z0 <z0> nz_local <n> samples <s> time <t>";
+ * line 2: "# z zcoord" and the EKPNP_NPROFILES names (rho c cn phi ux uy uz Ex Ey Ez T ux_ux uy_uy uz_uz c_c cn_cn T_T
+ * uz_T uz_c uz_cn q_Ex q_Ez ux_uz q_q); then one row per plane: the global z (%d), z*dz and the means (%.17g), single
+ * spaces.  Mean = running sum / (samples * nx*ny); with no sample taken the file holds the means of the current fields
+ * and says "samples 0". */
+int ekpnp_save_profiles(ekpnp_ctx* ctx, const char* path, double time);
+
 /* ---- measurement hooks (bench.py; no reference counterpart) ------------------ */
 /* When enabled, every launch of the bulk collide/stream kernel is bracketed by
  * HIP events on the context's stream; the sum is returned by ..._get. */
@@ -486,6 +544,13 @@ int ekpnp_group_save_state(ekpnp_group* g, const char* path, double time);
 int ekpnp_group_read_state(ekpnp_group* g, const char* path, double* time);
 int ekpnp_group_save_checkpoint(ekpnp_group* g, const char* path);
 int ekpnp_group_load_checkpoint(ekpnp_group* g, const char* path, double* time);
+/* the plane profiles above over the whole lattice: every slab reduces its own planes on its own device (no exchange),
+ * host arrays are [EKPNP_NPROFILES][NZ] with slab i's columns at its z0; one whole-lattice file */
+int ekpnp_group_plane_sums(ekpnp_group* g, double* host_out);
+int ekpnp_group_stats_reset(ekpnp_group* g);
+int ekpnp_group_stats_accumulate(ekpnp_group* g);                     /* enqueues only, like ekpnp_stats_accumulate */
+int ekpnp_group_stats_get(ekpnp_group* g, double* host_out, int* n_samples);
+int ekpnp_group_save_profiles(ekpnp_group* g, const char* path, double time);
 
 #ifdef __cplusplus
 }
