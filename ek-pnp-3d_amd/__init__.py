@@ -16,6 +16,7 @@ from .solver import (  # noqa: F401
     PROFILE_NAMES,
     Params,
     STAGE_NAMES,
+    SnapshotSpec,
     Solver,
     TRANSPORT_AUTO,
     TRANSPORT_COPY,
@@ -28,4 +29,6 @@ from .solver import (  # noqa: F401
     load_library,
     rccl_available,
     slab_extent,
+    snapshot_extent,
+    snapshot_spec,
 )

@@ -518,6 +518,7 @@ extern "C" int ekpnp_destroy(ekpnp_ctx* ctx) {
   if (c.diag) (void)hipFree(c.diag);
   if (c.vwall) (void)hipFree(c.vwall);
   if (c.stats_part) (void)hipFree(c.stats_part);  // (stats_out and stats_acc lie in the same allocation)
+  snapshot_release(c);  // waits for the side stream's copies; pending snapshots are discarded
   for (int k = 0; k < 4; ++k) {
     if (c.halo[k]) (void)hipFree(c.halo[k]);
     if (c.phi_halo[k]) (void)hipFree(c.phi_halo[k]);

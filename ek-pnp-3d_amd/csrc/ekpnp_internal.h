@@ -206,6 +206,19 @@ int stats_workgroups_per_plane(const Ctx&);
 void launch_plane_sums(Ctx&, double* acc);
 // the text file of ekpnp_save_profiles / ekpnp_group_save_profiles: sums is [EKPNP_NPROFILES][nzl], planes z0 .. z0 + nzl - 1
 int stats_write_file(const char* path, const ekpnp_params& p, int z0, int nzl, int samples, double time, const double* sums, std::string& err);
+// snapshot.hip: coarsened FP32 snapshots through two staging slots and a side stream (SnapState: made on first use)
+struct SnapState;
+int snapshot_check_spec(const ekpnp_params& p, const ekpnp_snapshot_spec* s, std::string& err);
+// enqueue one snapshot of the context's own sampled planes, [nfields][planes][Y][X] floats (path == null: into memory only);
+// a third pending one first finishes the oldest
+int snapshot_enqueue(Ctx&, const ekpnp_snapshot_spec& spec, bool big_endian, const char* path, double time);
+int snapshot_pending_count(const Ctx&);
+// wait for the copy of the oldest (or newest) pending snapshot: the pinned buffer, its first output plane, planes and bytes
+int snapshot_land(Ctx&, bool newest, const float** host, int* k0, int* kn, size_t* bytes);
+void snapshot_pop(Ctx&, bool newest);
+void snapshot_release(Ctx&);  // ekpnp_destroy: pending ones are discarded, buffers, events and the side stream freed
+int snapshot_write_header(FILE* f, const ekpnp_params& p, const ekpnp_snapshot_spec& s, double time, int k0, int kn);
+int snapshot_write_field_header(FILE* f, int field_id);
 
 struct Ctx {
   ekpnp_params p{};
@@ -296,6 +309,7 @@ struct Ctx {
   double* stats_out = nullptr;
   double* stats_acc = nullptr;
   int stats_samples = 0;           // ekpnp_stats_accumulate calls since the last reset (host side: the calls only enqueue)
+  SnapState* snap = nullptr;       // snapshot pipeline (snapshot.hip), made by the first snapshot call
   int collide_phase = 0;           // 0 idle, 1 boundary planes done
   // slab edge planes without pack / unpack copies (KArgs::halo_*): knob, and where the current halos are
   bool halo_direct = true;         // EKPNP_HALO_DIRECT=0: k_halo_pack / k_halo_unpack as in rounds 1-3 (the A/B partner)

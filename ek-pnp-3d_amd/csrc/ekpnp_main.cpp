@@ -60,6 +60,8 @@ int main(int argc, char* argv[]) {
   double exf = 0.0, uw = 0.0, chargeinf = -1.0, Ra = -1.0, TH = -1.0;
   double converged_tol = 0.0;  // > 0: ekpnp_initialization_converged instead of the reference's fixed 501 Picard sweeps
   unsigned profiles_every = 0;  // > 0: ekpnp_stats_accumulate after every that many iterations, profiles.dat at the end
+  unsigned snap_every = 0;      // > 0: a coarsened FP32 snapshot snap_<step>.vtk after every that many iterations (ekpnp_snapshot_begin / _finish)
+  ekpnp_snapshot_spec snap_spec = {0u, 1, 1, 1};
   int batch = 0;  // 1: ekpnp_step(n) from one output mark to the next instead of one stream_collide_save + fast_Poisson pair per iteration
   std::vector<std::pair<std::string, int>> tunes;  // --tune knob=value: ekpnp_tune / ekpnp_group_tune right after creation
   for (int i = 1; i < argc; ++i) {
@@ -96,6 +98,24 @@ int main(int argc, char* argv[]) {
     else if ((v = val("--converged-init"))) converged_tol = std::atof(v);
     else if ((v = val("--batch"))) batch = std::atoi(v);
     else if ((v = val("--profiles-every"))) profiles_every = (unsigned)std::atoi(v);
+    else if ((v = val("--snap-every"))) snap_every = (unsigned)std::atoi(v);
+    else if ((v = val("--snap-coarsen"))) {
+      if (std::sscanf(v, "%d,%d,%d", &snap_spec.cx, &snap_spec.cy, &snap_spec.cz) != 3) { std::fprintf(stderr, "--snap-coarsen wants cx,cy,cz, got %s\n", v); return 2; }
+    }
+    else if ((v = val("--snap-fields"))) {
+      static const char* const names[EKPNP_NFIELDS] = {"rho", "c", "cn", "phi", "ux", "uy", "uz", "Ex", "Ey", "Ez", "T"};
+      snap_spec.fields = 0u;
+      for (const char* q = v; *q;) {
+        const char* e = q;
+        while (*e && *e != ',') ++e;
+        int id = -1;
+        for (int k = 0; k < EKPNP_NFIELDS; ++k)
+          if (std::strlen(names[k]) == (size_t)(e - q) && std::strncmp(names[k], q, (size_t)(e - q)) == 0) id = k;
+        if (id < 0) { std::fprintf(stderr, "--snap-fields wants names out of rho,c,cn,phi,ux,uy,uz,Ex,Ey,Ez,T, got %s\n", v); return 2; }
+        snap_spec.fields |= 1u << id;
+        q = *e ? e + 1 : e;
+      }
+    }
     else if ((v = val("--tune"))) {
       const char* eq = std::strchr(v, '=');
       if (!eq || eq == v) { std::fprintf(stderr, "--tune wants knob=value, got %s\n", v); return 2; }
@@ -107,6 +127,12 @@ int main(int argc, char* argv[]) {
                    "                  [--binary-state 0|1] [--gpus N [--transport auto|rccl|copy] [--devices d0,d1,...]]\n"
                    "                  [--lattices 1|3|4] [--exf F --uw U --chargeinf C --Ra R --TH T] [--out DIR] [--converged-init TOL]\n"
                    "                  [--tune knob=value ...] [--batch 0|1] [--profiles-every N]\n"
+                   "                  [--snap-every N [--snap-coarsen cx,cy,cz] [--snap-fields rho,uz,...]]\n"
+                   "  --snap-every N: after every N-th iteration a coarsened FP32 snapshot of the fields goes to snap_<step, 7 digits>.vtk (legacy\n"
+                   "  VTK, big-endian floats: ParaView and VisIt read it as is).  z is sampled every cz-th plane (cz divides nz - 1: both plates are\n"
+                   "  kept), x and y are means over cx x cy blocks (each 1, 2, 4 or 8); default 1,1,1 and all eleven fields.  The snapshot is\n"
+                   "  begun at the mark (ekpnp_snapshot_begin: coarsened on the device, copied out on a side stream) and its file is written at\n"
+                   "  the next mark or at the end (ekpnp_snapshot_finish), while the time loop runs on; every other file is unchanged.\n"
                    "  --profiles-every N: after every N-th iteration the plane sums of the fields (z profiles of the fields, their squares,\n"
                    "  the fluxes uz*T, uz*c, uz*cn and the body force (c - cn)*E; reduced on the device, ekpnp_stats_accumulate) are added to\n"
                    "  running sums, and the time-averaged plane means go to profiles.dat at the end (ekpnp_save_profiles); every other file is\n"
@@ -202,7 +228,8 @@ int main(int argc, char* argv[]) {
     if (batch) {
       // iterations i .. j in one call, j = the next iteration something looks at the fields (or the last one)
       unsigned j = i;
-      while (j + 1 < nsteps && !(j % nsave == 1 || j % print_current == 1 || (profiles_every && (j + 1) % profiles_every == 0))) ++j;
+      while (j + 1 < nsteps && !(j % nsave == 1 || j % print_current == 1 || (profiles_every && (j + 1) % profiles_every == 0) ||
+                                 (snap_every && (j + 1) % snap_every == 0))) ++j;
       CK(RUN(step, (int)(j - i + 1)));
       for (unsigned k = i; k <= j; ++k) t = t + P.dt;  // the same additions as the loop below makes, so the files carry the same time
       i = j;
@@ -222,7 +249,14 @@ int main(int argc, char* argv[]) {
       CK(RUN(record_umax, f_umax.c_str(), 1, t));
     }
     if (profiles_every && (i + 1) % profiles_every == 0) CK(RUN(stats_accumulate));  // enqueues only: the loop runs on
+    if (snap_every && (i + 1) % snap_every == 0) {
+      char name[32];
+      std::snprintf(name, sizeof name, "/snap_%07u.vtk", i + 1);
+      CK(RUN(snapshot_finish));  // the file of the previous mark: its copy landed long ago, the device keeps stepping meanwhile
+      CK(RUN(snapshot_begin, &snap_spec, (out + name).c_str(), t));  // enqueues only
+    }
   }
+  if (snap_every) CK(RUN(snapshot_finish));
   CK(RUN(synchronize));
   const double runtime = std::chrono::duration<double>(std::chrono::steady_clock::now() - begin).count();
 

@@ -27,6 +27,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <new>
 
 #include "ekpnp_internal.h"
@@ -126,6 +127,10 @@ struct Team {
   bool poisoned = false;
   std::string poison;
   bool comm_broken = false;  // an RCCL call failed inside a collective: its kernels may never finish, the communicators are aborted, not drained
+  // in-process groups: the whole-lattice snapshots begun and not finished yet (ekpnp_group_snapshot_begin), oldest first; every slab
+  // holds one pending snapshot of its own planes per entry (snapshot.hip)
+  struct Snap { ekpnp_snapshot_spec spec; std::string path; double time; };
+  std::deque<Snap> snaps;
 };
 
 static inline Ctx& S(Team& T, int i) { return T.m[i]->c; }
@@ -1430,3 +1435,102 @@ extern "C" int ekpnp_group_save_profiles(ekpnp_group* g, const char* path, doubl
   if (rc) return rc;
   return stats_write_file(path, p, 0, p.nz, samples, time, h.data(), T.err);
 }
+
+// ---- coarsened FP32 snapshots (snapshot.hip) over the slabs: z is sampled, so an output plane lives on one slab; every slab
+// coarsens and lands its own planes through its own staging slots and side stream, and the host places them per field in z order
+static inline unsigned snap_mask(const ekpnp_snapshot_spec& s) { return s.fields ? s.fields : (1u << EKPNP_NFIELDS) - 1u; }
+static int team_snapshot_enqueue(Team& T, const ekpnp_snapshot_spec& spec, bool big_endian) {
+  for (size_t i = 0; i < T.m.size(); ++i) {
+    int rc = use(T, (int)i);
+    if (rc) return rc;
+    TSLAB(T, (int)i, snapshot_enqueue(S(T, (int)i), spec, big_endian, nullptr, 0.0));
+  }
+  return EKPNP_OK;
+}
+// the slabs' pending snapshot (oldest or newest) gathered: sink(field slot, first output plane, planes, floats of that slab and field)
+template <class Sink>
+static int team_snapshot_gather(Team& T, const ekpnp_snapshot_spec& spec, bool newest, Sink&& sink) {
+  const ekpnp_params& p = S(T, 0).p;
+  const size_t per_plane = (size_t)(p.nx / spec.cx) * (size_t)(p.ny / spec.cy);
+  const int nf = __builtin_popcount(snap_mask(spec));
+  int rc = EKPNP_OK;
+  std::vector<const float*> h(T.m.size(), nullptr);
+  std::vector<int> k0(T.m.size(), 0), kn(T.m.size(), 0);
+  for (size_t i = 0; i < T.m.size() && rc == EKPNP_OK; ++i) {
+    if ((rc = use(T, (int)i))) break;
+    rc = snapshot_land(S(T, (int)i), newest, &h[i], &k0[i], &kn[i], nullptr);
+    if (rc) T.err = "slab " + std::to_string(S(T, (int)i).rank) + ": " + S(T, (int)i).err;
+  }
+  for (int f = 0; f < nf && rc == EKPNP_OK; ++f)
+    for (size_t i = 0; i < T.m.size() && rc == EKPNP_OK; ++i)
+      if (kn[i]) rc = sink(f, k0[i], kn[i], h[i] + (size_t)f * kn[i] * per_plane);
+  for (size_t i = 0; i < T.m.size(); ++i) snapshot_pop(S(T, (int)i), newest);  // dropped whatever happened: the slabs stay aligned
+  return rc;
+}
+static int team_snapshot_finish_oldest(Team& T) {
+  const Team::Snap sn = T.snaps.front();
+  T.snaps.pop_front();
+  const ekpnp_params& p = S(T, 0).p;
+  const size_t per_plane = (size_t)(p.nx / sn.spec.cx) * (size_t)(p.ny / sn.spec.cy);
+  FILE* f = std::fopen(sn.path.c_str(), "wb");
+  if (f) snapshot_write_header(f, p, sn.spec, sn.time, 0, (p.nz - 1) / sn.spec.cz + 1);
+  int last_field = -1;
+  const unsigned mask = snap_mask(sn.spec);
+  int rc = team_snapshot_gather(T, sn.spec, false, [&](int slot, int, int kn, const float* src) {
+    if (!f) return EKPNP_OK;
+    if (slot != last_field) {
+      int id = -1;
+      for (int i = 0, n = 0; i < EKPNP_NFIELDS; ++i)
+        if ((mask & (1u << i)) && n++ == slot) id = i;
+      snapshot_write_field_header(f, id);
+      last_field = slot;
+    }
+    std::fwrite(src, sizeof(float), (size_t)kn * per_plane, f);
+    return EKPNP_OK;
+  });
+  if (!f) {
+    if (rc == EKPNP_OK) { T.err = "snapshot: cannot open " + sn.path; rc = EKPNP_ERR_INVALID; }
+    return rc;
+  }
+  const bool bad = std::ferror(f) != 0;
+  if ((std::fclose(f) != 0 || bad) && rc == EKPNP_OK) { T.err = "snapshot: write error on " + sn.path; rc = EKPNP_ERR_INVALID; }
+  return rc;
+}
+extern "C" int ekpnp_group_snapshot_read(ekpnp_group* g, const ekpnp_snapshot_spec* spec, float* host_out) {
+  NEEDLIVEGROUP(g);
+  if (!spec || !host_out) { T.err = "snapshot: NULL pointer"; return EKPNP_ERR_INVALID; }
+  const ekpnp_params& p = S(T, 0).p;
+  if (int rc = snapshot_check_spec(p, spec, T.err)) return rc;
+  while (T.snaps.size() >= 2)
+    if (int rc = team_snapshot_finish_oldest(T)) return rc;
+  if (int rc = team_snapshot_enqueue(T, *spec, false)) return group_fail(T, rc);
+  const size_t per_plane = (size_t)(p.nx / spec->cx) * (size_t)(p.ny / spec->cy), Z = (size_t)(p.nz - 1) / spec->cz + 1;
+  return team_snapshot_gather(T, *spec, true, [&](int slot, int k0, int kn, const float* src) {
+    std::memcpy(host_out + ((size_t)slot * Z + k0) * per_plane, src, (size_t)kn * per_plane * sizeof(float));
+    return EKPNP_OK;
+  });
+}
+// enqueues only, on every slab's compute stream (as ekpnp_group_stats_accumulate); the header is written at finish too: a path
+// that cannot be opened fails there
+extern "C" int ekpnp_group_snapshot_begin(ekpnp_group* g, const ekpnp_snapshot_spec* spec, const char* path, double time) {
+  NEEDLIVEGROUP(g);
+  if (!spec || !path) { T.err = "snapshot: NULL pointer"; return EKPNP_ERR_INVALID; }
+  if (int rc = snapshot_check_spec(S(T, 0).p, spec, T.err)) return rc;
+  while (T.snaps.size() >= 2)
+    if (int rc = team_snapshot_finish_oldest(T)) return rc;
+  if (int rc = team_snapshot_enqueue(T, *spec, true)) return group_fail(T, rc);
+  T.snaps.push_back(Team::Snap{*spec, path, time});
+  return EKPNP_OK;
+}
+extern "C" int ekpnp_group_snapshot_finish(ekpnp_group* g) {
+  NEEDLIVEGROUP(g);
+  int first = EKPNP_OK;
+  std::string msg;
+  while (!T.snaps.empty()) {
+    const int rc = team_snapshot_finish_oldest(T);
+    if (rc && !first) { first = rc; msg = T.err; }
+  }
+  if (first) T.err = msg;
+  return first;
+}
+extern "C" int ekpnp_group_snapshot_pending(const ekpnp_group* g) { return g ? (int)g->t.snaps.size() : 0; }

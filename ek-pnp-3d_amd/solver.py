@@ -35,6 +35,32 @@ class EkpnpError(RuntimeError):
     pass
 
 
+class SnapshotSpec(C.Structure):
+    """Mirror of `ekpnp_snapshot_spec` (include/ekpnp.h): field bit mask (0 = all eleven) and the coarsening cx, cy, cz."""
+
+    _fields_ = [("fields", C.c_uint32), ("cx", C.c_int32), ("cy", C.c_int32), ("cz", C.c_int32)]
+
+
+def snapshot_spec(fields=None, coarsen=(1, 1, 1)) -> SnapshotSpec:
+    """fields: None (all eleven), a bit mask over the field ids, or names; the output keeps ascending id order"""
+    if fields is None:
+        mask = 0
+    elif isinstance(fields, int):
+        mask = fields
+    else:
+        mask = 0
+        for n in fields:
+            mask |= 1 << FIELD_ID[n]
+        if mask == 0:
+            raise ValueError("snapshot: no field selected")
+    cx, cy, cz = (int(v) for v in coarsen)
+    return SnapshotSpec(mask, cx, cy, cz)
+
+
+def _snapshot_names(spec: SnapshotSpec) -> list:
+    return [n for i, n in enumerate(FIELDS) if spec.fields == 0 or (spec.fields >> i) & 1]
+
+
 class Params(C.Structure):
     """Mirror of `ekpnp_params` (include/ekpnp.h)."""
 
@@ -197,6 +223,16 @@ def load_library():
         "ekpnp_group_stats_accumulate": (i32, [ctx]),
         "ekpnp_group_stats_get": (i32, [ctx, C.c_void_p, C.POINTER(i32)]),
         "ekpnp_group_save_profiles": (i32, [ctx, C.c_char_p, dbl]),
+        # coarsened FP32 snapshots
+        "ekpnp_snapshot_extent": (i32, [C.POINTER(Params), C.POINTER(SnapshotSpec), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(sz)]),
+        "ekpnp_snapshot_read": (i32, [ctx, C.POINTER(SnapshotSpec), C.c_void_p, C.POINTER(i32), C.POINTER(i32)]),
+        "ekpnp_snapshot_begin": (i32, [ctx, C.POINTER(SnapshotSpec), C.c_char_p, dbl]),
+        "ekpnp_snapshot_finish": (i32, [ctx]),
+        "ekpnp_snapshot_pending": (i32, [ctx]),
+        "ekpnp_group_snapshot_read": (i32, [ctx, C.POINTER(SnapshotSpec), C.c_void_p]),
+        "ekpnp_group_snapshot_begin": (i32, [ctx, C.POINTER(SnapshotSpec), C.c_char_p, dbl]),
+        "ekpnp_group_snapshot_finish": (i32, [ctx]),
+        "ekpnp_group_snapshot_pending": (i32, [ctx]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError if the library does not export it
@@ -212,6 +248,18 @@ def default_params(nx: int, ny: int, nz: int) -> Params:
     if rc:
         raise EkpnpError(f"ekpnp_default_params({nx},{ny},{nz}) -> {rc}")
     return p
+
+
+def snapshot_extent(p: Params, fields=None, coarsen=(1, 1, 1)):
+    """(X, Y, Z, payload bytes) of a snapshot of the WHOLE lattice (ekpnp_snapshot_extent: host arithmetic, no device);
+    raises EkpnpError with the library's message for a spec it refuses"""
+    L = load_library()
+    spec = snapshot_spec(fields, coarsen)
+    X, Y, Z, b = C.c_int(), C.c_int(), C.c_int(), C.c_size_t()
+    rc = L.ekpnp_snapshot_extent(C.byref(p), C.byref(spec), C.byref(X), C.byref(Y), C.byref(Z), C.byref(b))
+    if rc:
+        raise EkpnpError(f"status {rc}: {L.ekpnp_last_error(None).decode()}")
+    return X.value, Y.value, Z.value, int(b.value)
 
 
 def slab_extent(nz: int, rank: int, nranks: int):
@@ -456,6 +504,42 @@ class Solver:
     def save_profiles(self, path: str, time: float = 0.0):
         """text file of the time-averaged plane means of the owned planes (ekpnp_save_profiles)"""
         self._ck(self._L.ekpnp_save_profiles(self._h, os.fsencode(path), float(time)))
+
+    # -- coarsened FP32 snapshots (no reference counterpart) -----------------------------------
+    def snapshot_planes(self, cz: int = 1):
+        """(first output plane, number of output planes) of this context for a z sampling step cz: planes k with k*cz owned"""
+        k0 = (self.z0 + cz - 1) // cz
+        k1 = (self.z0 + self.nz_local - 1) // cz
+        return k0, max(0, k1 - k0 + 1)
+
+    def snapshot(self, fields=None, coarsen=(1, 1, 1)) -> dict:
+        """name -> float32 [Zlocal][Y][X]: every cz-th plane of this context (both plates kept), means over cx x cy blocks added
+        in a fixed order in float64, rounded once to float32 (ekpnp_snapshot_read; complete on return).  The first output
+        plane of a slab is snapshot_planes(cz)[0]."""
+        spec = snapshot_spec(fields, coarsen)
+        if self._L.ekpnp_snapshot_extent(C.byref(self.p), C.byref(spec), None, None, None, None):
+            raise EkpnpError(f"status 1: {self._L.ekpnp_last_error(None).decode()}")
+        names = _snapshot_names(spec)
+        X, Y = self.p.nx // spec.cx, self.p.ny // spec.cy
+        out = np.empty((len(names), self.snapshot_planes(spec.cz)[1], Y, X), dtype=np.float32)
+        k0, kn = C.c_int(), C.c_int()
+        self._ck(self._L.ekpnp_snapshot_read(self._h, C.byref(spec), out.ctypes.data_as(C.c_void_p), C.byref(k0), C.byref(kn)))
+        assert (k0.value, kn.value) == self.snapshot_planes(spec.cz)
+        return {n: out[i] for i, n in enumerate(names)}
+
+    def snapshot_begin(self, path: str, fields=None, coarsen=(1, 1, 1), time: float = 0.0):
+        """enqueue a snapshot for the legacy VTK file `path` and return at once (place it between two step() calls);
+        snapshot_finish() writes the file.  At most two are pending: a third begin first finishes the oldest."""
+        spec = snapshot_spec(fields, coarsen)
+        self._ck(self._L.ekpnp_snapshot_begin(self._h, C.byref(spec), os.fsencode(path), float(time)))
+
+    def snapshot_finish(self):
+        """wait for the copies of the pending snapshots (not for the compute stream) and write their files"""
+        self._ck(self._L.ekpnp_snapshot_finish(self._h))
+
+    @property
+    def snapshot_pending(self) -> int:
+        return int(self._L.ekpnp_snapshot_pending(self._h))
 
     def tune(self, knob: str, value: int):
         self._ck(self._L.ekpnp_tune(self._h, knob.encode(), int(value)))
@@ -716,6 +800,26 @@ class Group:
 
     def save_profiles(self, path: str, time: float = 0.0):
         self._ck(self._L.ekpnp_group_save_profiles(self._g, os.fsencode(path), float(time)))
+
+    def snapshot(self, fields=None, coarsen=(1, 1, 1)) -> dict:
+        """name -> float32 [Z][Y][X] of the whole lattice: every slab coarsens and lands its own sampled planes"""
+        spec = snapshot_spec(fields, coarsen)
+        X, Y, Z, _ = snapshot_extent(self.p, spec.fields, coarsen)
+        names = _snapshot_names(spec)
+        out = np.empty((len(names), Z, Y, X), dtype=np.float32)
+        self._ck(self._L.ekpnp_group_snapshot_read(self._g, C.byref(spec), out.ctypes.data_as(C.c_void_p)))
+        return {n: out[i] for i, n in enumerate(names)}
+
+    def snapshot_begin(self, path: str, fields=None, coarsen=(1, 1, 1), time: float = 0.0):
+        spec = snapshot_spec(fields, coarsen)
+        self._ck(self._L.ekpnp_group_snapshot_begin(self._g, C.byref(spec), os.fsencode(path), float(time)))
+
+    def snapshot_finish(self):
+        self._ck(self._L.ekpnp_group_snapshot_finish(self._g))
+
+    @property
+    def snapshot_pending(self) -> int:
+        return int(self._L.ekpnp_group_snapshot_pending(self._g))
 
     def save_checkpoint(self, path: str):
         self._ck(self._L.ekpnp_group_save_checkpoint(self._g, os.fsencode(path)))

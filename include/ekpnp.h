@@ -295,6 +295,61 @@ int ekpnp_stats_get(ekpnp_ctx* ctx, double* host_out, int* n_samples);
  * and says "samples 0". */
 int ekpnp_save_profiles(ekpnp_ctx* ctx, const char* path, double time);
 
+/* ---- coarsened FP32 snapshots written while the run continues (no reference counterpart) --------------
+ * What a picture of the vortices needs (the reference's users study square and hexagonal cells, LBM.cu:646-661):
+ * FP32, coarser than the lattice, and without stopping the time loop - instead of ekpnp_get_field of every field
+ * (1.07 GB of FP64 each at 512^3, through pageable memory while the stream waits) or one %10.6f text row per node.
+ * One launch reads only the planes it needs, block-averages in x and y, converts to float and leaves a buffer 16 to
+ * 64 times smaller than the fields; a side stream copies it to pinned host memory while ekpnp_step keeps the
+ * compute stream busy.
+ * Spec: fields is a bit mask over the field ids EKPNP_RHO .. EKPNP_T (0 = all eleven; fields appear in ascending id
+ * order); cx and cy are each 1, 2, 4 or 8 and divide nx and ny; cz >= 1 divides nz - 1.  Anything else is
+ * EKPNP_ERR_INVALID with a message that names the offending number.
+ * Output lattice X = nx/cx, Y = ny/cy, Z = (nz-1)/cz + 1:
+ *   - z is SAMPLED, not averaged: output plane k is global plane k*cz, so both plates are always kept with their
+ *     boundary values (the usual NZ = 2^k + 1 works with every power-of-two cz), a plane lives on one rank, slabs
+ *     need no communication and skipped planes are never read;
+ *   - x and y are block means in a FIXED order: S = v(X*cx, Y*cy, k*cz), then the other cx*cy - 1 values one at a
+ *     time, yy ascending outside and xx ascending inside, as plain FP64 S = S + v; the node is (float)(S / (cx*cy)),
+ *     rounded to nearest (cx*cy is a power of two: the division is exact).  No tree, no shuffle, no atomic: the bits
+ *     depend on the field values alone - not on the launch shape, the buffer mode or the decomposition.  NaN and Inf
+ *     propagate;
+ *   - the fields are what ekpnp_get_field would return at that moment (phi, Ex, Ey or Ez selected: a lazy solve's
+ *     arrays are brought up to date first; "batch_moments": as for ekpnp_stats_accumulate). */
+typedef struct ekpnp_snapshot_spec {
+  uint32_t fields;
+  int32_t cx, cy, cz;
+} ekpnp_snapshot_spec;
+/* Host arithmetic only, needs no device: the output extents of the WHOLE lattice and the payload bytes
+ * nfields*X*Y*Z*4 (any of the four out pointers may be NULL).  The message of a refused spec is
+ * ekpnp_last_error of NULL. */
+int ekpnp_snapshot_extent(const ekpnp_params* p, const ekpnp_snapshot_spec* spec, int* X, int* Y, int* Z, size_t* payload_bytes);
+/* Synchronous, into memory: this context's sampled planes as native-endian float [nfields][Zlocal][Y][X];
+ * z_first / z_count receive the index of its first output plane and how many it holds (0 is legal for a slab). */
+int ekpnp_snapshot_read(ekpnp_ctx* ctx, const ekpnp_snapshot_spec* spec, float* host_out, int* z_first, int* z_count);
+/* The pipeline.  begin ENQUEUES ONLY and returns without waiting: the compute stream waits for the staging slot's
+ * previous copy, runs the kernel and records an event; the side stream waits for that event, copies to pinned host
+ * memory and records "landed".  finish waits for "landed" only - never for the compute stream - and then writes the
+ * file on the calling thread, so the host writes while the device steps (no worker threads); it lands and writes
+ * every pending snapshot, and the first error wins.  At most two snapshots are pending: a third begin first
+ * finishes the oldest.  ekpnp_destroy discards what is still pending (no file).  Two device staging slots, two
+ * pinned host buffers, one side stream and the events are made by the first snapshot call, sized to the spec and
+ * re-allocated when a later spec needs more; the device bytes are counted by ekpnp_device_bytes.
+ * File: legacy VTK, readable by ParaView and VisIt as is -
+ *   "# vtk DataFile Version 3.0"
+ *   "ekpnp snapshot time <%.17g> nx <nx> ny <ny> nz <nz> coarsen <cx> <cy> <cz> z_first <k0>"
+ *   "BINARY", "DATASET STRUCTURED_POINTS", "DIMENSIONS X Y Zfile",
+ *   "ORIGIN (cx-1)*dx/2 (cy-1)*dy/2 k0*cz*dz", "SPACING cx*dx cy*dy cz*dz", "POINT_DATA n",
+ *   then per field "SCALARS <name> float 1", "LOOKUP_TABLE default" and the big-endian floats (the kernel stores them
+ *   byte-swapped), names rho c cn phi ux uy uz Ex Ey Ez T.  File size = text + payload bytes, nothing else.
+ * A single context writes the whole lattice; a slab context (stand-alone or attached) writes its own planes, one file
+ * per rank like ekpnp_save_state, z_first and ORIGIN saying where they sit; a slab that holds no sampled plane writes
+ * no file and returns EKPNP_OK.  The file is opened at FINISH: a path that cannot be opened fails there (or in the
+ * third begin that finishes it), the snapshot is dropped and the context stays usable. */
+int ekpnp_snapshot_begin(ekpnp_ctx* ctx, const ekpnp_snapshot_spec* spec, const char* path, double time);
+int ekpnp_snapshot_finish(ekpnp_ctx* ctx);
+int ekpnp_snapshot_pending(const ekpnp_ctx* ctx);
+
 /* ---- measurement hooks (bench.py; no reference counterpart) ------------------ */
 /* When enabled, every launch of the bulk collide/stream kernel is bracketed by
  * HIP events on the context's stream; the sum is returned by ..._get. */
@@ -551,6 +606,13 @@ int ekpnp_group_stats_reset(ekpnp_group* g);
 int ekpnp_group_stats_accumulate(ekpnp_group* g);                     /* enqueues only, like ekpnp_stats_accumulate */
 int ekpnp_group_stats_get(ekpnp_group* g, double* host_out, int* n_samples);
 int ekpnp_group_save_profiles(ekpnp_group* g, const char* path, double time);
+/* the snapshots above over the whole lattice, ONE file: every slab coarsens and lands its own sampled planes through its
+ * own staging slots and side stream (no exchange), the host places them per field in z order; host_out is
+ * float [nfields][Z][Y][X]; the arrays and the file are byte for byte those of a single context */
+int ekpnp_group_snapshot_read(ekpnp_group* g, const ekpnp_snapshot_spec* spec, float* host_out);
+int ekpnp_group_snapshot_begin(ekpnp_group* g, const ekpnp_snapshot_spec* spec, const char* path, double time);  /* enqueues only */
+int ekpnp_group_snapshot_finish(ekpnp_group* g);
+int ekpnp_group_snapshot_pending(const ekpnp_group* g);
 
 #ifdef __cplusplus
 }
