@@ -12,6 +12,9 @@ from .solver import (  # noqa: F401
     FIELD_ID,
     EkpnpError,
     Group,
+    MONITOR_ID,
+    MONITOR_NAMES,
+    MonitorSpec,
     PROFILE_ID,
     PROFILE_NAMES,
     Params,
@@ -27,6 +30,8 @@ from .solver import (  # noqa: F401
     exported_symbols,
     library_path,
     load_library,
+    monitor_mask,
+    monitor_spec_check,
     rccl_available,
     slab_extent,
     snapshot_extent,

@@ -138,6 +138,10 @@ static void drop_graph(Ctx& c) {
   c.graph_cur = -1;
 }
 
+namespace ekpnp {
+void drop_step_graph(Ctx& c) { drop_graph(c); }
+}  // namespace ekpnp
+
 // ---- lazy E (round 4; Ctx::e_stale) -------------------------------------------------------------------------------
 namespace ekpnp {
 bool lazy_efield_ok(const Ctx& c) {
@@ -519,6 +523,7 @@ extern "C" int ekpnp_destroy(ekpnp_ctx* ctx) {
   if (c.vwall) (void)hipFree(c.vwall);
   if (c.stats_part) (void)hipFree(c.stats_part);  // (stats_out and stats_acc lie in the same allocation)
   snapshot_release(c);  // waits for the side stream's copies; pending snapshots are discarded
+  monitor_release(c);
   for (int k = 0; k < 4; ++k) {
     if (c.halo[k]) (void)hipFree(c.halo[k]);
     if (c.phi_halo[k]) (void)hipFree(c.phi_halo[k]);
@@ -1112,8 +1117,12 @@ static int capture_two_steps(ekpnp_ctx* ctx) {
   const double t0 = c.t;
   const bool stale0 = c.e_stale, phiv0 = c.e_phi_valid;
   if (hipStreamBeginCapture(c.stream, hipStreamCaptureModeThreadLocal) != hipSuccess) { (void)hipGetLastError(); c.graph_failed = true; return EKPNP_OK; }
+  // an armed monitor with every = 1 rides inside the graph: its row's slot comes from the device-side cursor
+  const bool rows = monitor_every(c) == 1;
   int rc = one_step(ctx);
+  if (rc == EKPNP_OK && rows) rc = monitor_enqueue_row(c);
   if (rc == EKPNP_OK) rc = one_step(ctx);
+  if (rc == EKPNP_OK && rows) rc = monitor_enqueue_row(c);
   hipGraph_t g = nullptr;
   hipError_t e = hipStreamEndCapture(c.stream, &g);
   // nothing has executed: restore the host-side state the two calls advanced
@@ -1141,33 +1150,51 @@ extern "C" int ekpnp_step(ekpnp_ctx* ctx, int nsteps) {
   if (nsteps < 0) return fail(c, "nsteps < 0");
   if (c.slab) return c.team ? team_ctx_step(c, nsteps) : fail(c, "slab context without a transport: attach one, use ekpnp_group_*, or drive the split calls yourself");
   int i = 0;
+  // one step enqueued call by call; an armed monitor counts it and appends its row when it is due ("batch_moments": a
+  // sampled step stores its moments, like the call's last one)
+  const bool batch = batch_moments_ok(c);
+  auto eager_step = [&]() -> int {
+    c.skip_moments = batch && i < nsteps - 1 && monitor_steps_to_sample(c) != 1;  // only the call's LAST step can be looked at
+    int rc = one_step(ctx);
+    c.skip_moments = false;
+    if (rc == EKPNP_OK && c.mon) rc = monitor_step_done(c);
+    ++i;
+    return rc;
+  };
   // the first step after init_equilibrium does not pull; one whose E was set from outside reads the E arrays: neither is
   // the step the graph below captures
   if ((c.streamed_state || (lazy_efield_ok(c) && !c.e_phi_valid)) && nsteps > 0) {
     int rc = one_step(ctx);
+    if (rc == EKPNP_OK && c.mon) rc = monitor_step_done(c);
     if (rc) return rc;
     ++i;
   }
   if (graph_wanted(c, nsteps - i)) {
-    if (!c.graph2 || c.graph_cur != c.cur) {
+    // every = 1: the rows are part of the captured steps.  every > 1: the captured pair holds no row and is replayed where
+    // neither of the next two steps is sampled; a sampled step (and one that brings `cur` back to the captured parity) is
+    // enqueued call by call - the same kernels either way, the same bits.
+    const int every = monitor_every(c);
+    if (!c.graph2 || (c.graph_cur != c.cur && every <= 1)) {
       int rc = capture_two_steps(ctx);
       if (rc) return rc;
     }
     while (c.graph2 && nsteps - i >= 2) {
+      if (every > 1 && (c.graph_cur != c.cur || monitor_steps_to_sample(c) <= 2)) {
+        if (int rc = eager_step()) return rc;
+        continue;
+      }
       HIPCHK(c, hipGraphLaunch(c.graph2, c.stream));
       mark_solved(c, lazy_efield_ok(c));
       c.t = c.t + c.p.dt;
+      if (every == 1) monitor_replayed_row(c, c.t);
       c.t = c.t + c.p.dt;
+      if (every == 1) monitor_replayed_row(c, c.t);
+      if (every > 1) monitor_count_steps(c, 2);
       i += 2;
     }
   }
-  const bool batch = batch_moments_ok(c);
-  for (; i < nsteps; ++i) {
-    c.skip_moments = batch && i < nsteps - 1;  // only the call's LAST step can be looked at
-    int rc = one_step(ctx);
-    c.skip_moments = false;
-    if (rc) return rc;
-  }
+  while (i < nsteps)
+    if (int rc = eager_step()) return rc;
   return EKPNP_OK;
 }
 

@@ -219,6 +219,20 @@ void snapshot_pop(Ctx&, bool newest);
 void snapshot_release(Ctx&);  // ekpnp_destroy: pending ones are discarded, buffers, events and the side stream freed
 int snapshot_write_header(FILE* f, const ekpnp_params& p, const ekpnp_snapshot_spec& s, double time, int k0, int kn);
 int snapshot_write_field_header(FILE* f, int field_id);
+// monitor.hip: the per-step scalar time series (MonState: made by the first ekpnp_monitor_sample / ekpnp_monitor_arm)
+struct MonState;
+int monitor_check_spec(const ekpnp_monitor_spec* s, std::string& err);
+int monitor_last_every(const Ctx&);        // `every` of the last arm (0: never armed), for the file header
+int monitor_every(const Ctx&);             // the armed monitor's `every`, 0 when none is armed
+int monitor_steps_to_sample(const Ctx&);   // 1: the next step through ekpnp_step is a sampled one (a huge number when none is armed)
+int monitor_step_done(Ctx&);               // a step through ekpnp_step / team_step has been enqueued and Ctx::t advanced: count it, append a row if it is due
+int monitor_enqueue_row(Ctx&);             // the launches of one row alone (what a captured step holds) ...
+void monitor_note_row(Ctx&, int64_t step, double time);  // ... and the host's side of it: the row's labels
+void monitor_replayed_row(Ctx&, double time);  // a replayed step has appended a row: count the step and label the row with it
+void monitor_count_steps(Ctx&, int n);     // steps that went by in a replayed graph without a row
+void monitor_release(Ctx&);                // ekpnp_destroy
+int monitor_write_file(const char* path, const ekpnp_params& p, int every, int64_t recorded, int64_t dropped, int n, const int64_t* steps,
+                       const double* times, const double* values, std::string& err);
 
 struct Ctx {
   ekpnp_params p{};
@@ -310,6 +324,7 @@ struct Ctx {
   double* stats_acc = nullptr;
   int stats_samples = 0;           // ekpnp_stats_accumulate calls since the last reset (host side: the calls only enqueue)
   SnapState* snap = nullptr;       // snapshot pipeline (snapshot.hip), made by the first snapshot call
+  MonState* mon = nullptr;         // scalar time series (monitor.hip), made by the first monitor call
   int collide_phase = 0;           // 0 idle, 1 boundary planes done
   // slab edge planes without pack / unpack copies (KArgs::halo_*): knob, and where the current halos are
   bool halo_direct = true;         // EKPNP_HALO_DIRECT=0: k_halo_pack / k_halo_unpack as in rounds 1-3 (the A/B partner)
@@ -352,6 +367,8 @@ struct Ctx {
   PArgs pargs() const;
 };
 
+// capi.hip: forget the captured 2-step graph (whatever changes what a step launches)
+void drop_step_graph(Ctx& c);
 // capi.hip: may an intermediate step of a batch leave the moment arrays alone (knob on, all seven arrays the library's own, unexposed)?
 bool batch_moments_ok(const Ctx& c);
 // capi.hip: may this context leave E in phi (every one of phi, Ex, Ey, Ez is the library's own, unexposed array)?

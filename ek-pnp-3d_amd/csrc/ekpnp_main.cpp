@@ -62,6 +62,8 @@ int main(int argc, char* argv[]) {
   unsigned profiles_every = 0;  // > 0: ekpnp_stats_accumulate after every that many iterations, profiles.dat at the end
   unsigned snap_every = 0;      // > 0: a coarsened FP32 snapshot snap_<step>.vtk after every that many iterations (ekpnp_snapshot_begin / _finish)
   ekpnp_snapshot_spec snap_spec = {0u, 1, 1, 1};
+  unsigned monitor_every = 0;   // > 0: the scalar time series (ekpnp_monitor_*) with a row after every that many iterations, monitor.dat at the end
+  ekpnp_monitor_spec mon_spec = {0u, 1, 1};
   int batch = 0;  // 1: ekpnp_step(n) from one output mark to the next instead of one stream_collide_save + fast_Poisson pair per iteration
   std::vector<std::pair<std::string, int>> tunes;  // --tune knob=value: ekpnp_tune / ekpnp_group_tune right after creation
   for (int i = 1; i < argc; ++i) {
@@ -116,6 +118,27 @@ int main(int argc, char* argv[]) {
         q = *e ? e + 1 : e;
       }
     }
+    else if ((v = val("--monitor-every"))) monitor_every = (unsigned)std::atoi(v);
+    else if ((v = val("--monitor-quantities"))) {
+      mon_spec.quantities = 0u;
+      for (const char* q = v; *q;) {
+        const char* e = q;
+        while (*e && *e != ',') ++e;
+        int id = -1;
+        for (int k = 0; k < EKPNP_NMONITORS; ++k) {
+          const char* name = ekpnp_monitor_name(k);
+          if (std::strlen(name) == (size_t)(e - q) && std::strncmp(name, q, (size_t)(e - q)) == 0) id = k;
+        }
+        if (id < 0) {
+          std::fprintf(stderr, "--monitor-quantities wants names out of");
+          for (int k = 0; k < EKPNP_NMONITORS; ++k) std::fprintf(stderr, "%s%s", k ? "," : " ", ekpnp_monitor_name(k));
+          std::fprintf(stderr, ", got %s\n", v);
+          return 2;
+        }
+        mon_spec.quantities |= 1u << id;
+        q = *e ? e + 1 : e;
+      }
+    }
     else if ((v = val("--tune"))) {
       const char* eq = std::strchr(v, '=');
       if (!eq || eq == v) { std::fprintf(stderr, "--tune wants knob=value, got %s\n", v); return 2; }
@@ -128,6 +151,13 @@ int main(int argc, char* argv[]) {
                    "                  [--lattices 1|3|4] [--exf F --uw U --chargeinf C --Ra R --TH T] [--out DIR] [--converged-init TOL]\n"
                    "                  [--tune knob=value ...] [--batch 0|1] [--profiles-every N]\n"
                    "                  [--snap-every N [--snap-coarsen cx,cy,cz] [--snap-fields rho,uz,...]]\n"
+                   "                  [--monitor-every N [--monitor-quantities current_top,uz_max,...]]\n"
+                   "  --monitor-every N: after every N-th iteration eleven scalars - the current through either plate, the wall gradients of\n"
+                   "  T, max uz, the sums of u.u, c - cn, (c - cn)^2 and uz*T, max |rho - rho0| and the number of non-finite nodes - are reduced\n"
+                   "  on the device and appended to a ring in device memory (ekpnp_monitor_arm / ekpnp_monitor_record: enqueued only, nothing\n"
+                   "  waits); monitor.dat is written at the end (ekpnp_monitor_save: one row per sample, %%.17g).  With --batch 1 the batches\n"
+                   "  are NOT cut at these marks: the rows are appended from inside ekpnp_step.  Both loops write the same bytes, and every\n"
+                   "  other file is unchanged.  --monitor-quantities: only those columns (the others hold 0 and cost nothing).\n"
                    "  --snap-every N: after every N-th iteration a coarsened FP32 snapshot of the fields goes to snap_<step, 7 digits>.vtk (legacy\n"
                    "  VTK, big-endian floats: ParaView and VisIt read it as is).  z is sampled every cz-th plane (cz divides nz - 1: both plates are\n"
                    "  kept), x and y are means over cx x cy blocks (each 1, 2, 4 or 8); default 1,1,1 and all eleven fields.  The snapshot is\n"
@@ -222,6 +252,12 @@ int main(int argc, char* argv[]) {
   CK(RUN(save_data_tecplot, f_data.c_str(), 0, t, 1));   // main.cu:178-179 ("wb+")
   { FILE* f = std::fopen(f_umax.c_str(), "wb"); if (f) std::fclose(f); }  // main.cu:180
 
+  if (monitor_every) {  // a ring that holds the whole run
+    mon_spec.every = (int32_t)monitor_every;
+    mon_spec.capacity = (int32_t)((nsteps + monitor_every - 1) / monitor_every);
+    if (mon_spec.capacity < 1) mon_spec.capacity = 1;
+    CK(RUN(monitor_arm, &mon_spec));
+  }
   CK(RUN(synchronize));
   const auto begin = std::chrono::steady_clock::now();  // main.cu:185-186
   for (unsigned i = 0; i < nsteps; i++) {               // main.cu:189-224
@@ -248,6 +284,7 @@ int main(int argc, char* argv[]) {
       std::printf("Iteration: %u, physical time: %g, Current = %g\n", i, t, I);
       CK(RUN(record_umax, f_umax.c_str(), 1, t));
     }
+    if (monitor_every && !batch && (i + 1) % monitor_every == 0) CK(RUN(monitor_record, (int64_t)(i + 1), t));  // enqueues only (--batch 1: ekpnp_step has done it)
     if (profiles_every && (i + 1) % profiles_every == 0) CK(RUN(stats_accumulate));  // enqueues only: the loop runs on
     if (snap_every && (i + 1) % snap_every == 0) {
       char name[32];
@@ -271,6 +308,7 @@ int main(int argc, char* argv[]) {
   CK(RUN(save_data_end, f_end.c_str(), 0, t));          // main.cu:256-257
   if (binary_state) CK(RUN(save_state, f_bin.c_str(), t));
   if (profiles_every) CK(RUN(save_profiles, (out + "/profiles.dat").c_str(), t));
+  if (monitor_every) CK(RUN(monitor_save, (out + "/monitor.dat").c_str()));
   CK(grp ? ekpnp_group_destroy(grp) : ekpnp_destroy(ctx));    // main.cu:264-290
   return 0;
 }

@@ -418,12 +418,20 @@ static int team_step(Team& T, int nsteps) {  // main.cu:189-200
   if (nsteps < 0) { T.err = "nsteps < 0"; return EKPNP_ERR_INVALID; }
   for (int s = 0; s < nsteps; ++s) {
     // opt-in "batch_moments": only the call's last step stores the moment arrays of the interior planes (capi.hip: ekpnp_step)
-    for (size_t i = 0; i < T.m.size(); ++i) S(T, (int)i).skip_moments = s < nsteps - 1 && batch_moments_ok(S(T, (int)i));
+    // (a step an armed monitor samples stores them too)
+    for (size_t i = 0; i < T.m.size(); ++i)
+      S(T, (int)i).skip_moments = s < nsteps - 1 && batch_moments_ok(S(T, (int)i)) && monitor_steps_to_sample(S(T, (int)i)) != 1;
     int rc = team_stream_collide_save(T);
     for (size_t i = 0; i < T.m.size(); ++i) S(T, (int)i).skip_moments = false;
     if (rc == EKPNP_OK) rc = team_fast_poisson(T);
     if (rc) return rc;
     for (size_t i = 0; i < T.m.size(); ++i) TSLAB(T, (int)i, ekpnp_advance_time(T.m[i]));
+    // armed monitors (monitor.hip): every slab appends its own row on its own compute stream - no wait, no exchange
+    for (size_t i = 0; i < T.m.size(); ++i) {
+      if (!S(T, (int)i).mon) continue;
+      if ((rc = use(T, (int)i))) return rc;
+      TSLAB(T, (int)i, monitor_step_done(S(T, (int)i)));
+    }
   }
   return EKPNP_OK;
 }
@@ -1534,3 +1542,79 @@ extern "C" int ekpnp_group_snapshot_finish(ekpnp_group* g) {
   return first;
 }
 extern "C" int ekpnp_group_snapshot_pending(const ekpnp_group* g) { return g ? (int)g->t.snaps.size() : 0; }
+
+// ---- scalar time series (monitor.hip) over the slabs: every slab records on its own device; the host combines the slabs' rows -
+// sums in ascending slab order, maxima with max.  Only the plate-holding slab is non-zero in a plate column, so current_top is
+// ekpnp_group_current and uz_max is ekpnp_group_umax bit for bit (team_reduce adds and compares in the same order).
+static inline bool monitor_is_max(int q) { return q == 4 || q == 9; }
+static void monitor_combine(double* acc, const double* v, int rows, bool first) {
+  for (int r = 0; r < rows; ++r)
+    for (int q = 0; q < EKPNP_NMONITORS; ++q) {
+      double& a = acc[(size_t)r * EKPNP_NMONITORS + q];
+      const double b = v[(size_t)r * EKPNP_NMONITORS + q];
+      a = first ? b : (monitor_is_max(q) ? std::fmax(a, b) : a + b);
+    }
+}
+template <class Fn>
+static int team_monitor_each(Team& T, Fn&& fn) {
+  for (size_t i = 0; i < T.m.size(); ++i) {
+    int rc = use(T, (int)i);
+    if (rc) return rc;
+    TSLAB(T, (int)i, fn(T.m[i]));
+  }
+  return EKPNP_OK;
+}
+extern "C" int ekpnp_group_monitor_sample(ekpnp_group* g, uint32_t quantities, double* out) {
+  NEEDLIVEGROUP(g);
+  if (!out) { T.err = "NULL pointer"; return EKPNP_ERR_INVALID; }
+  if (quantities >> EKPNP_NMONITORS) {  // refused before any slab has launched anything: the group stays usable
+    T.err = "monitor: quantities = " + std::to_string(quantities) + " selects an id above " + std::to_string(EKPNP_NMONITORS - 1);
+    return EKPNP_ERR_INVALID;
+  }
+  double v[EKPNP_NMONITORS];
+  bool first = true;
+  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) {
+    const int rc = ekpnp_monitor_sample(m, quantities, v);
+    if (rc == EKPNP_OK) { monitor_combine(out, v, 1, first); first = false; }
+    return rc;
+  }));
+}
+extern "C" int ekpnp_group_monitor_arm(ekpnp_group* g, const ekpnp_monitor_spec* spec) {
+  NEEDLIVEGROUP(g);
+  if (int rc = monitor_check_spec(spec, T.err)) return rc;
+  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) { return ekpnp_monitor_arm(m, spec); }));
+}
+extern "C" int ekpnp_group_monitor_disarm(ekpnp_group* g) {
+  NEEDLIVEGROUP(g);
+  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) { return ekpnp_monitor_disarm(m); }));
+}
+// enqueues only, on every slab's compute stream (as ekpnp_group_stats_accumulate)
+extern "C" int ekpnp_group_monitor_record(ekpnp_group* g, int64_t step, double time) {
+  NEEDLIVEGROUP(g);
+  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) { return ekpnp_monitor_record(m, step, time); }));
+}
+extern "C" int ekpnp_group_monitor_count(const ekpnp_group* g, int64_t* recorded, int64_t* dropped) {
+  if (!g || g->t.m.empty()) return EKPNP_ERR_INVALID;
+  return ekpnp_monitor_count(g->t.m[0], recorded, dropped);  // the slabs record in step
+}
+extern "C" int ekpnp_group_monitor_read(ekpnp_group* g, int64_t first, int count, int64_t* steps, double* times, double* values) {
+  NEEDLIVEGROUP(g);
+  std::vector<double> v((size_t)(count > 0 ? count : 0) * EKPNP_NMONITORS);
+  bool head = true;
+  return team_monitor_each(T, [&](ekpnp_ctx* m) {
+    const int rc = ekpnp_monitor_read(m, first, count, steps, times, v.data());
+    if (rc == EKPNP_OK && count > 0) { monitor_combine(values, v.data(), count, head); head = false; }
+    return rc;
+  });
+}
+extern "C" int ekpnp_group_monitor_save(ekpnp_group* g, const char* path) {
+  NEEDLIVEGROUP(g);
+  if (!path) { T.err = "NULL path"; return EKPNP_ERR_INVALID; }
+  int64_t rec = 0, dropped = 0;
+  (void)ekpnp_group_monitor_count(g, &rec, &dropped);
+  const int n = (int)(rec - dropped);
+  std::vector<int64_t> steps((size_t)n);
+  std::vector<double> times((size_t)n), values((size_t)n * EKPNP_NMONITORS);
+  if (int rc = ekpnp_group_monitor_read(g, 0, n, steps.data(), times.data(), values.data())) return rc;
+  return monitor_write_file(path, S(T, 0).p, monitor_last_every(S(T, 0)), rec, dropped, n, steps.data(), times.data(), values.data(), T.err);
+}

@@ -29,6 +29,9 @@ FIELD_ID = {n: i for i, n in enumerate(FIELDS)}
 # the EKPNP_NPROFILES plane sums of ekpnp_plane_sums, in id order (include/ekpnp.h: EKPNP_PROF_*); q stands for c - cn
 PROFILE_NAMES = FIELDS + ["ux_ux", "uy_uy", "uz_uz", "c_c", "cn_cn", "T_T", "uz_T", "uz_c", "uz_cn", "q_Ex", "q_Ez", "ux_uz", "q_q"]
 PROFILE_ID = {n: i for i, n in enumerate(PROFILE_NAMES)}
+# the EKPNP_NMONITORS scalars of a monitor row, in id order (include/ekpnp.h: EKPNP_MON_*); q stands for c - cn
+MONITOR_NAMES = ["current_top", "current_bottom", "dTdz_bottom", "dTdz_top", "uz_max", "u_u", "q", "q_q", "uz_T", "rho_dev", "nonfinite"]
+MONITOR_ID = {n: i for i, n in enumerate(MONITOR_NAMES)}
 
 
 class EkpnpError(RuntimeError):
@@ -55,6 +58,44 @@ def snapshot_spec(fields=None, coarsen=(1, 1, 1)) -> SnapshotSpec:
             raise ValueError("snapshot: no field selected")
     cx, cy, cz = (int(v) for v in coarsen)
     return SnapshotSpec(mask, cx, cy, cz)
+
+
+class MonitorSpec(C.Structure):
+    """Mirror of `ekpnp_monitor_spec` (include/ekpnp.h): quantity bit mask (0 = all eleven), a row every `every` steps, ring rows."""
+
+    _fields_ = [("quantities", C.c_uint32), ("every", C.c_int32), ("capacity", C.c_int32)]
+
+
+def monitor_mask(quantities=None) -> int:
+    """None (all eleven), a bit mask over the monitor ids, or names"""
+    if quantities is None:
+        return 0
+    if isinstance(quantities, int):
+        return quantities
+    mask = 0
+    for n in quantities:
+        mask |= 1 << (MONITOR_ID[n] if isinstance(n, str) else int(n))
+    if mask == 0:
+        raise ValueError("monitor: no quantity selected")
+    return mask
+
+
+def monitor_spec_check(quantities=None, every: int = 1, capacity: int = 1) -> MonitorSpec:
+    """the spec, or EkpnpError with the library's message (ekpnp_monitor_spec_check: host arithmetic, no device)"""
+    L = load_library()
+    spec = MonitorSpec(monitor_mask(quantities), int(every), int(capacity))
+    rc = L.ekpnp_monitor_spec_check(C.byref(spec))
+    if rc:
+        raise EkpnpError(f"ekpnp_monitor_spec_check -> status {rc}: {L.ekpnp_last_error(None).decode()}")
+    return spec
+
+
+def _monitor_read(L, fn, handle, ck, first: int, count: int):
+    steps = np.zeros(max(count, 0), dtype=np.int64)
+    times = np.zeros(max(count, 0), dtype=np.float64)
+    values = np.zeros((max(count, 0), len(MONITOR_NAMES)), dtype=np.float64)
+    ck(fn(handle, int(first), int(count), steps.ctypes.data_as(C.c_void_p), times.ctypes.data_as(C.c_void_p), values.ctypes.data_as(C.c_void_p)))
+    return steps, times, values
 
 
 def _snapshot_names(spec: SnapshotSpec) -> list:
@@ -233,6 +274,23 @@ def load_library():
         "ekpnp_group_snapshot_begin": (i32, [ctx, C.POINTER(SnapshotSpec), C.c_char_p, dbl]),
         "ekpnp_group_snapshot_finish": (i32, [ctx]),
         "ekpnp_group_snapshot_pending": (i32, [ctx]),
+        # per-step scalar time series
+        "ekpnp_monitor_name": (C.c_char_p, [i32]),
+        "ekpnp_monitor_spec_check": (i32, [C.POINTER(MonitorSpec)]),
+        "ekpnp_monitor_sample": (i32, [ctx, C.c_uint32, C.c_void_p]),
+        "ekpnp_monitor_arm": (i32, [ctx, C.POINTER(MonitorSpec)]),
+        "ekpnp_monitor_disarm": (i32, [ctx]),
+        "ekpnp_monitor_record": (i32, [ctx, C.c_int64, dbl]),
+        "ekpnp_monitor_count": (i32, [ctx, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+        "ekpnp_monitor_read": (i32, [ctx, C.c_int64, i32, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "ekpnp_monitor_save": (i32, [ctx, C.c_char_p]),
+        "ekpnp_group_monitor_sample": (i32, [ctx, C.c_uint32, C.c_void_p]),
+        "ekpnp_group_monitor_arm": (i32, [ctx, C.POINTER(MonitorSpec)]),
+        "ekpnp_group_monitor_disarm": (i32, [ctx]),
+        "ekpnp_group_monitor_record": (i32, [ctx, C.c_int64, dbl]),
+        "ekpnp_group_monitor_count": (i32, [ctx, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+        "ekpnp_group_monitor_read": (i32, [ctx, C.c_int64, i32, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "ekpnp_group_monitor_save": (i32, [ctx, C.c_char_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError if the library does not export it
@@ -541,6 +599,43 @@ class Solver:
     def snapshot_pending(self) -> int:
         return int(self._L.ekpnp_snapshot_pending(self._h))
 
+    # -- per-step scalar time series kept on the device (no reference counterpart) --------------
+    def monitor_sample(self, quantities=None) -> np.ndarray:
+        """the len(MONITOR_NAMES) scalars of the current fields, now (ekpnp_monitor_sample: complete on return; columns
+        that are not selected hold 0.0).  Needs no armed monitor and does not touch the ring."""
+        out = np.zeros(len(MONITOR_NAMES), dtype=np.float64)
+        self._ck(self._L.ekpnp_monitor_sample(self._h, monitor_mask(quantities), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def monitor_arm(self, quantities=None, every: int = 1, capacity: int = 1024):
+        """from now on step() appends a row to a ring of `capacity` rows in device memory after every `every`-th step:
+        enqueued only, nothing waits.  Arming again resets the ring and the step count."""
+        spec = MonitorSpec(monitor_mask(quantities), int(every), int(capacity))
+        self._ck(self._L.ekpnp_monitor_arm(self._h, C.byref(spec)))
+
+    def monitor_disarm(self):
+        self._ck(self._L.ekpnp_monitor_disarm(self._h))
+
+    def monitor_record(self, step: int, time: float):
+        """append a row with the caller's labels (hosts that drive stream_collide_save / fast_Poisson themselves); enqueues only"""
+        self._ck(self._L.ekpnp_monitor_record(self._h, int(step), float(time)))
+
+    def monitor_count(self):
+        """(rows recorded since arming, rows lost to overflow); host-known, never synchronises"""
+        r, d = C.c_int64(), C.c_int64()
+        self._ck(self._L.ekpnp_monitor_count(self._h, C.byref(r), C.byref(d)))
+        return int(r.value), int(d.value)
+
+    def monitor_read(self, first: int = 0, count: int = None):
+        """(steps[n], times[n], values[n][len(MONITOR_NAMES)]) of the rows still held, oldest first; count None: all from `first` on"""
+        if count is None:
+            r, d = self.monitor_count()
+            count = r - d - first
+        return _monitor_read(self._L, self._L.ekpnp_monitor_read, self._h, self._ck, first, count)
+
+    def monitor_save(self, path: str):
+        self._ck(self._L.ekpnp_monitor_save(self._h, os.fsencode(path)))
+
     def tune(self, knob: str, value: int):
         self._ck(self._L.ekpnp_tune(self._h, knob.encode(), int(value)))
 
@@ -820,6 +915,43 @@ class Group:
     @property
     def snapshot_pending(self) -> int:
         return int(self._L.ekpnp_group_snapshot_pending(self._g))
+
+    # -- per-step scalar time series kept on the device (no reference counterpart) --------------
+    def monitor_sample(self, quantities=None) -> np.ndarray:
+        """the len(MONITOR_NAMES) scalars of the current fields, now (ekpnp_group_monitor_sample: complete on return; columns
+        that are not selected hold 0.0).  Needs no armed monitor and does not touch the ring."""
+        out = np.zeros(len(MONITOR_NAMES), dtype=np.float64)
+        self._ck(self._L.ekpnp_group_monitor_sample(self._g, monitor_mask(quantities), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def monitor_arm(self, quantities=None, every: int = 1, capacity: int = 1024):
+        """from now on step() appends a row to a ring of `capacity` rows in device memory after every `every`-th step:
+        enqueued only, nothing waits.  Arming again resets the ring and the step count."""
+        spec = MonitorSpec(monitor_mask(quantities), int(every), int(capacity))
+        self._ck(self._L.ekpnp_group_monitor_arm(self._g, C.byref(spec)))
+
+    def monitor_disarm(self):
+        self._ck(self._L.ekpnp_group_monitor_disarm(self._g))
+
+    def monitor_record(self, step: int, time: float):
+        """append a row with the caller's labels (hosts that drive stream_collide_save / fast_Poisson themselves); enqueues only"""
+        self._ck(self._L.ekpnp_group_monitor_record(self._g, int(step), float(time)))
+
+    def monitor_count(self):
+        """(rows recorded since arming, rows lost to overflow); host-known, never synchronises"""
+        r, d = C.c_int64(), C.c_int64()
+        self._ck(self._L.ekpnp_group_monitor_count(self._g, C.byref(r), C.byref(d)))
+        return int(r.value), int(d.value)
+
+    def monitor_read(self, first: int = 0, count: int = None):
+        """(steps[n], times[n], values[n][len(MONITOR_NAMES)]) of the rows still held, oldest first; count None: all from `first` on"""
+        if count is None:
+            r, d = self.monitor_count()
+            count = r - d - first
+        return _monitor_read(self._L, self._L.ekpnp_group_monitor_read, self._g, self._ck, first, count)
+
+    def monitor_save(self, path: str):
+        self._ck(self._L.ekpnp_group_monitor_save(self._g, os.fsencode(path)))
 
     def save_checkpoint(self, path: str):
         self._ck(self._L.ekpnp_group_save_checkpoint(self._g, os.fsencode(path)))

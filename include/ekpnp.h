@@ -350,6 +350,74 @@ int ekpnp_snapshot_begin(ekpnp_ctx* ctx, const ekpnp_snapshot_spec* spec, const 
 int ekpnp_snapshot_finish(ekpnp_ctx* ctx);
 int ekpnp_snapshot_pending(const ekpnp_ctx* ctx);
 
+/* ---- per-step scalar time series kept on the device (no reference counterpart) ---------------------------
+ * What a run is plotted by FIRST: the current through the plates against time, the maximum velocity, the kinetic energy, the
+ * convective heat flux - and whether the run is still healthy.  The reference takes them every 50 steps because each costs
+ * three full-field copies (main.cu:211-222); ekpnp_current / ekpnp_umax reduce on the device but are complete on return (a
+ * stream synchronise, a host round trip, under lazy E a pass that writes the three E arrays), so a host that wants them at
+ * every step gives up the step graph, "batch_moments" and lazy E.  A monitor reduces EKPNP_NMONITORS scalars on the device
+ * after a step and appends them to a ring in device memory: no wait, no host read, no collective; the ring is read out
+ * whenever the host likes.  Ids and names (ekpnp_monitor_name), each taken from the field arrays as ekpnp_get_field would
+ * return them at that moment: */
+enum {
+  EKPNP_MON_CURRENT_TOP = 0,     /* the number ekpnp_current returns (LBM.cu:2674-2710): same expression, same order of
+                                    additions, same launch shape - the same bits                                          */
+  EKPNP_MON_CURRENT_BOTTOM = 1,  /* its mirror image at the lower plate: planes 1 and 2, Ez(0)                            */
+  EKPNP_MON_DTDZ_BOTTOM = 2,     /* sum_xy (4 T(1) - 3 T(0) - T(2)); unnormalised: / (2 dz nx ny) is the mean wall gradient */
+  EKPNP_MON_DTDZ_TOP = 3,        /* sum_xy (3 T(NZ-1) - 4 T(NZ-2) + T(NZ-3)); same division                               */
+  EKPNP_MON_UZ_MAX = 4,          /* max(0, max uz), the number ekpnp_umax returns                                         */
+  EKPNP_MON_U_U = 5,             /* sum (ux^2 + uy^2 + uz^2)                                                              */
+  EKPNP_MON_Q = 6,               /* sum (c - cn)                                                                          */
+  EKPNP_MON_Q_Q = 7,             /* sum (c - cn)^2                                                                        */
+  EKPNP_MON_UZ_T = 8,            /* sum uz T                                                                              */
+  EKPNP_MON_RHO_DEV = 9,         /* max |rho - rho0| (fmax: a NaN does not show up here but in the next one)               */
+  EKPNP_MON_NONFINITE = 10,      /* nodes at which rho, c, cn or T is NaN or Inf, as an exact double                      */
+  EKPNP_NMONITORS = 11
+};
+/* Plate quantities (0-3) read at most three planes per plate; a slab that does not hold the plate contributes +0.0.  Under
+ * lazy E (ekpnp_fast_poisson) the plate's Ez is formed from phi the way the collide and the E pass form it - 0.5*(a - b)/dz
+ * of the neighbouring interior plane, the plate's own phi taken from voltage / voltage2 (poisson.cu:40-69) -: a monitor never
+ * brings the E arrays up to date.  Volume quantities (5-8, 10) are added in a fixed order: within a plane it depends on nx*ny
+ * alone (fixed runs of nodes per workgroup, fixed trees inside, the workgroups' partial sums in ascending order: the scheme of
+ * ekpnp_plane_sums), the plane sums are added in ascending z within the context; no atomics.  A value is therefore the same
+ * bits in a two-buffer and an in-place context, under graph replay and eagerly, with "batch_moments" on or off.  One pass
+ * reads only the arrays its selected quantities need, at most seven (56 B per node).
+ * Spec: quantities is a bit mask over the ids (0 = all); every >= 1; capacity >= 1.  Anything else, a bit above 10 included,
+ * is EKPNP_ERR_INVALID with a message that names the offending number.  Columns that are not selected hold 0.0 and cost
+ * nothing. */
+typedef struct ekpnp_monitor_spec {
+  uint32_t quantities;
+  int32_t every;
+  int32_t capacity;
+} ekpnp_monitor_spec;
+const char* ekpnp_monitor_name(int id);                        /* host only; NULL outside 0 .. EKPNP_NMONITORS - 1 */
+/* Host only, needs no device.  The message of a refused spec is ekpnp_last_error of NULL. */
+int ekpnp_monitor_spec_check(const ekpnp_monitor_spec* spec);
+/* Synchronous and one-off: the values now, into out[EKPNP_NMONITORS].  Needs no armed monitor, does not touch the ring. */
+int ekpnp_monitor_sample(ekpnp_ctx* ctx, uint32_t quantities, double* out);
+/* arm allocates the device ring [capacity][EKPNP_NMONITORS], the partial-sum scratch and a device-side cursor - once, counted
+ * by ekpnp_device_bytes; arming again resets the ring and the step count.  Arming and disarming drop a captured step graph.
+ * While a monitor is armed, ekpnp_step and ekpnp_group_step (and ekpnp_step of an attached slab) append a row after every
+ * `every`-th step completed through them since arming: taken after that step's Poisson solve, labelled with the 1-based count
+ * of such steps and the context's time after the step; it is ENQUEUED ONLY.  The row's slot comes from the device-side cursor,
+ * so a replayed step graph never reuses one; with every > 1 the steps between two samples are replayed or enqueued call by call
+ * (same bits); with "batch_moments" a sampled step stores its moments like a call's last step.  record is the same enqueue with
+ * the caller's labels, for hosts that drive the split calls (ekpnp_stream_collide_save, ekpnp_fast_poisson).  When the ring is
+ * full the oldest row is overwritten; dropped counts the rows lost.  count is host-known and never synchronises.  read
+ * synchronises the stream and returns rows first .. first + count - 1 of those still held, oldest first (values is
+ * [count][EKPNP_NMONITORS]); a range outside what is held is EKPNP_ERR_INVALID.  The ring is NOT part of checkpoint or state
+ * files.  A slab context attached over RCCL records and reads ITS OWN rank's rows (a plate column is +0.0 on a rank that does
+ * not hold the plate): no collective is added, the host adds the ranks' sums and takes the maximum of their maxima.
+ * save writes the held rows as text.  Line 1: "# ekpnp monitor nx <nx> ny <ny> nz <nz> every <e> recorded <r> dropped <d>";
+ * line 2: "# step time" and the eleven names (current_top current_bottom dTdz_bottom dTdz_top uz_max u_u q q_q uz_T rho_dev
+ * nonfinite); then one row per held sample: the label (%lld), the time and the eleven values (%.17g), single spaces. */
+int ekpnp_monitor_arm(ekpnp_ctx* ctx, const ekpnp_monitor_spec* spec);
+int ekpnp_monitor_disarm(ekpnp_ctx* ctx);
+int ekpnp_monitor_record(ekpnp_ctx* ctx, int64_t step, double time);
+int ekpnp_monitor_count(const ekpnp_ctx* ctx, int64_t* recorded, int64_t* dropped);
+int ekpnp_monitor_read(ekpnp_ctx* ctx, int64_t first, int count, int64_t* steps, double* times, double* values);
+int ekpnp_monitor_save(ekpnp_ctx* ctx, const char* path);
+
 /* ---- measurement hooks (bench.py; no reference counterpart) ------------------ */
 /* When enabled, every launch of the bulk collide/stream kernel is bracketed by
  * HIP events on the context's stream; the sum is returned by ..._get. */
@@ -613,6 +681,16 @@ int ekpnp_group_snapshot_read(ekpnp_group* g, const ekpnp_snapshot_spec* spec, f
 int ekpnp_group_snapshot_begin(ekpnp_group* g, const ekpnp_snapshot_spec* spec, const char* path, double time);  /* enqueues only */
 int ekpnp_group_snapshot_finish(ekpnp_group* g);
 int ekpnp_group_snapshot_pending(const ekpnp_group* g);
+/* the scalar time series above over the whole lattice: every slab records on its own device; read (and sample, save) combine
+ * the slabs on the host - sums in ascending slab order, maxima with max; only the plate-holding slab is non-zero in a plate
+ * column, so current_top is ekpnp_group_current and uz_max is ekpnp_group_umax bit for bit */
+int ekpnp_group_monitor_sample(ekpnp_group* g, uint32_t quantities, double* out);
+int ekpnp_group_monitor_arm(ekpnp_group* g, const ekpnp_monitor_spec* spec);
+int ekpnp_group_monitor_disarm(ekpnp_group* g);
+int ekpnp_group_monitor_record(ekpnp_group* g, int64_t step, double time);   /* enqueues only */
+int ekpnp_group_monitor_count(const ekpnp_group* g, int64_t* recorded, int64_t* dropped);
+int ekpnp_group_monitor_read(ekpnp_group* g, int64_t first, int count, int64_t* steps, double* times, double* values);
+int ekpnp_group_monitor_save(ekpnp_group* g, const char* path);
 
 #ifdef __cplusplus
 }
