@@ -12,13 +12,17 @@ from .solver import (  # noqa: F401
     FIELD_ID,
     EkpnpError,
     Group,
+    MAX_MODES,
     MONITOR_ID,
     MONITOR_NAMES,
+    ModesSpec,
     MonitorSpec,
     PROFILE_ID,
     PROFILE_NAMES,
     Params,
+    SEED_PATTERNS,
     STAGE_NAMES,
+    SeedSpec,
     SnapshotSpec,
     Solver,
     TRANSPORT_AUTO,
@@ -30,9 +34,15 @@ from .solver import (  # noqa: F401
     exported_symbols,
     library_path,
     load_library,
+    modes_spec,
+    modes_spec_check,
     monitor_mask,
     monitor_spec_check,
     rccl_available,
+    seed_host,
+    seed_spec,
+    seed_spec_check,
+    seed_uniform,
     slab_extent,
     snapshot_extent,
     snapshot_spec,

@@ -524,6 +524,8 @@ extern "C" int ekpnp_destroy(ekpnp_ctx* ctx) {
   if (c.stats_part) (void)hipFree(c.stats_part);  // (stats_out and stats_acc lie in the same allocation)
   snapshot_release(c);  // waits for the side stream's copies; pending snapshots are discarded
   monitor_release(c);
+  modes_release(c);
+  seed_release(c);
   for (int k = 0; k < 4; ++k) {
     if (c.halo[k]) (void)hipFree(c.halo[k]);
     if (c.phi_halo[k]) (void)hipFree(c.phi_halo[k]);

@@ -233,6 +233,18 @@ void monitor_count_steps(Ctx&, int n);     // steps that went by in a replayed g
 void monitor_release(Ctx&);                // ekpnp_destroy
 int monitor_write_file(const char* path, const ekpnp_params& p, int every, int64_t recorded, int64_t dropped, int n, const int64_t* steps,
                        const double* times, const double* values, std::string& err);
+// seed.hip: x-y patterns and reproducible noise added to the field arrays in one pass (the table buffer Ctx::seed_tab: made by the first ekpnp_seed)
+struct SeedState;
+int seed_check_spec(const ekpnp_params& p, const ekpnp_seed_spec* s, std::string& err);
+void seed_release(Ctx&);  // ekpnp_destroy
+// modes.hip: projection onto chosen x-y Fourier modes and its time series (ModeState: made by the first ekpnp_mode_amplitudes / ekpnp_modes_arm)
+struct ModeState;
+int modes_check_spec(const ekpnp_params& p, const ekpnp_modes_spec* s, std::string& err);
+const ekpnp_modes_spec* modes_armed_spec(const Ctx&);  // the spec of the last arm (null: never armed), for the file header
+bool modes_armed(const Ctx&);
+void modes_release(Ctx&);                              // ekpnp_destroy
+int modes_write_file(const char* path, const ekpnp_params& p, const ekpnp_modes_spec& spec, int64_t recorded, int64_t dropped, int n,
+                     const int64_t* steps, const double* times, const double* values, std::string& err);
 
 struct Ctx {
   ekpnp_params p{};
@@ -325,6 +337,8 @@ struct Ctx {
   int stats_samples = 0;           // ekpnp_stats_accumulate calls since the last reset (host side: the calls only enqueue)
   SnapState* snap = nullptr;       // snapshot pipeline (snapshot.hip), made by the first snapshot call
   MonState* mon = nullptr;         // scalar time series (monitor.hip), made by the first monitor call
+  ModeState* modes = nullptr;      // mode projection and its time series (modes.hip), made by the first modes call
+  SeedState* seed = nullptr;       // the seed's table buffer (seed.hip), made by the first ekpnp_seed
   int collide_phase = 0;           // 0 idle, 1 boundary planes done
   // slab edge planes without pack / unpack copies (KArgs::halo_*): knob, and where the current halos are
   bool halo_direct = true;         // EKPNP_HALO_DIRECT=0: k_halo_pack / k_halo_unpack as in rounds 1-3 (the A/B partner)

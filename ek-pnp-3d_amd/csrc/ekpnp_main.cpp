@@ -64,6 +64,19 @@ int main(int argc, char* argv[]) {
   ekpnp_snapshot_spec snap_spec = {0u, 1, 1, 1};
   unsigned monitor_every = 0;   // > 0: the scalar time series (ekpnp_monitor_*) with a row after every that many iterations, monitor.dat at the end
   ekpnp_monitor_spec mon_spec = {0u, 1, 1};
+  // --seed-pattern: x-y structure added to the start fields on the device (ekpnp_seed), then fast_Poisson, then init_equilibrium
+  bool seeding = false, seed_noise_given = false, seed_pattern_noise = false;
+  ekpnp_seed_spec seed_spec = {(1u << EKPNP_C) | (1u << EKPNP_CN), EKPNP_SEED_NONE, 1, 1, 1, 0, 1u, 1.0e-3, 0.0};
+  unsigned modes_every = 0;     // > 0: the energies of chosen x-y modes (ekpnp_modes_*) after every that many iterations, modes.dat at the end
+  ekpnp_modes_spec modes_spec = {};
+  modes_spec.field_id = EKPNP_UZ;
+  modes_spec.nmodes = 0;        // 0: the seed's (mx, my), (mx, -my) and (0, 0)
+  static const char* const field_names[EKPNP_NFIELDS] = {"rho", "c", "cn", "phi", "ux", "uy", "uz", "Ex", "Ey", "Ez", "T"};
+  auto field_id_of = [&](const char* q, size_t len) {
+    for (int k = 0; k < EKPNP_NFIELDS; ++k)
+      if (std::strlen(field_names[k]) == len && std::strncmp(field_names[k], q, len) == 0) return k;
+    return -1;
+  };
   int batch = 0;  // 1: ekpnp_step(n) from one output mark to the next instead of one stream_collide_save + fast_Poisson pair per iteration
   std::vector<std::pair<std::string, int>> tunes;  // --tune knob=value: ekpnp_tune / ekpnp_group_tune right after creation
   for (int i = 1; i < argc; ++i) {
@@ -139,6 +152,54 @@ int main(int argc, char* argv[]) {
         q = *e ? e + 1 : e;
       }
     }
+    else if ((v = val("--seed-pattern"))) {
+      seeding = true;
+      seed_pattern_noise = false;
+      if (!std::strcmp(v, "noise")) { seed_spec.pattern = EKPNP_SEED_NONE; seed_pattern_noise = true; }
+      else if (!std::strcmp(v, "rolls")) seed_spec.pattern = EKPNP_SEED_ROLLS;
+      else if (!std::strcmp(v, "squares")) seed_spec.pattern = EKPNP_SEED_SQUARES;
+      else if (!std::strcmp(v, "hexagons")) seed_spec.pattern = EKPNP_SEED_HEXAGONS;
+      else { std::fprintf(stderr, "--seed-pattern wants noise, rolls, squares or hexagons, got %s\n", v); return 2; }
+    }
+    else if ((v = val("--seed-modes"))) {
+      if (std::sscanf(v, "%d,%d", &seed_spec.mx, &seed_spec.my) != 2) { std::fprintf(stderr, "--seed-modes wants mx,my, got %s\n", v); return 2; }
+    }
+    else if ((v = val("--seed-amplitude"))) seed_spec.amplitude = std::atof(v);
+    else if ((v = val("--seed-noise"))) { seed_spec.noise = std::atof(v); seed_noise_given = true; }
+    else if ((v = val("--seed-relative"))) seed_spec.relative = std::atoi(v);
+    else if ((v = val("--seed"))) seed_spec.seed = std::strtoull(v, nullptr, 10);
+    else if ((v = val("--seed-fields"))) {
+      seed_spec.fields = 0u;
+      for (const char* q = v; *q;) {
+        const char* e = q;
+        while (*e && *e != ',') ++e;
+        const int id = field_id_of(q, (size_t)(e - q));
+        if (id < 0) { std::fprintf(stderr, "--seed-fields wants names out of rho,c,cn,ux,uy,uz,T, got %.*s in %s\n", (int)(e - q), q, v); return 2; }
+        seed_spec.fields |= 1u << id;
+        q = *e ? e + 1 : e;
+      }
+    }
+    else if ((v = val("--modes-every"))) modes_every = (unsigned)std::atoi(v);
+    else if ((v = val("--modes-field"))) {
+      const int id = field_id_of(v, std::strlen(v));
+      if (id < 0) { std::fprintf(stderr, "--modes-field wants one of rho,c,cn,phi,ux,uy,uz,Ex,Ey,Ez,T, got %s\n", v); return 2; }
+      modes_spec.field_id = id;
+    }
+    else if ((v = val("--modes"))) {
+      modes_spec.nmodes = 0;
+      for (const char* q = v; *q;) {
+        int m = 0, n = 0, used = 0;
+        if (std::sscanf(q, "%d,%d%n", &m, &n, &used) != 2 || modes_spec.nmodes >= EKPNP_MAX_MODES || (q[used] && q[used] != ';')) {
+          std::fprintf(stderr, "--modes wants at most %d pairs \"m,n;m,n;...\", got %s\n", EKPNP_MAX_MODES, v);
+          return 2;
+        }
+        modes_spec.m[modes_spec.nmodes] = m;
+        modes_spec.n[modes_spec.nmodes] = n;
+        ++modes_spec.nmodes;
+        q += used;
+        if (*q == ';') ++q;
+      }
+    }
     else if ((v = val("--tune"))) {
       const char* eq = std::strchr(v, '=');
       if (!eq || eq == v) { std::fprintf(stderr, "--tune wants knob=value, got %s\n", v); return 2; }
@@ -152,6 +213,21 @@ int main(int argc, char* argv[]) {
                    "                  [--tune knob=value ...] [--batch 0|1] [--profiles-every N]\n"
                    "                  [--snap-every N [--snap-coarsen cx,cy,cz] [--snap-fields rho,uz,...]]\n"
                    "                  [--monitor-every N [--monitor-quantities current_top,uz_max,...]]\n"
+                   "                  [--seed-pattern noise|rolls|squares|hexagons [--seed-modes mx,my] [--seed-amplitude A] [--seed-noise B]\n"
+                   "                   [--seed-fields c,cn,...] [--seed-relative 0|1] [--seed N]]\n"
+                   "                  [--modes-every N [--modes-field uz] [--modes \"m,n;m,n;...\"]]\n"
+                   "  --seed-pattern P: after the start-up (or the restart read) a pattern with mx,my whole periods across nx and ny (default 1,1)\n"
+                   "  and amplitude A (default 1e-3) plus white noise of amplitude B (default 0; reproducible from --seed N, default 1) is added to\n"
+                   "  the fields --seed-fields names (default c,cn; out of rho,c,cn,ux,uy,uz,T) on the interior planes, under a sin(pi z/(nz-1))\n"
+                   "  envelope, relative to the field's value (--seed-relative 1, the default: v += v*s) or absolute (0: v += s) - on the device\n"
+                   "  (ekpnp_seed: no field crosses the bus); then ekpnp_fast_poisson, then the usual init_equilibrium.  P = noise: no pattern,\n"
+                   "  B defaults to 1e-3.  A seed with A = B = 0 changes nothing and is skipped together with its solve: every file is then byte\n"
+                   "  for byte what it is without the flag.\n"
+                   "  --modes-every N: after every N-th iteration the field --modes-field names (default uz) is projected onto the x-y modes of\n"
+                   "  --modes (default: the seed's mx,my; mx,-my; and 0,0) on the device, and the energies E = sum_z |coefficient|^2 are appended\n"
+                   "  to a ring in device memory (ekpnp_modes_arm / ekpnp_modes_record: enqueued only, nothing waits); modes.dat is written at the\n"
+                   "  end (ekpnp_modes_save: one row per sample, %%.17g).  With --batch 1 the batches are cut at these marks; both loops write the\n"
+                   "  same bytes, and every other file is unchanged.\n"
                    "  --monitor-every N: after every N-th iteration eleven scalars - the current through either plate, the wall gradients of\n"
                    "  T, max uz, the sums of u.u, c - cn, (c - cn)^2 and uz*T, max |rho - rho0| and the number of non-finite nodes - are reduced\n"
                    "  on the device and appended to a ring in device memory (ekpnp_monitor_arm / ekpnp_monitor_record: enqueued only, nothing\n"
@@ -182,6 +258,25 @@ int main(int argc, char* argv[]) {
       return 2;
     }
   }
+  if (seeding) {
+    if (seed_pattern_noise) {  // noise alone: A = 0, B from --seed-noise
+      seed_spec.amplitude = 0.0;
+      if (!seed_noise_given) seed_spec.noise = 1.0e-3;
+    }
+  }
+  if (modes_every && modes_spec.nmodes == 0) {  // the seed's mode, its mirror image in y and the plane mean
+    const int mx = seed_spec.mx, my = seed_spec.my;
+    auto fold = [&](int n) { return ny % 2 == 0 && n == -(ny / 2) ? ny / 2 : n; };  // -ny/2 is the Nyquist mode ny/2
+    const int cand[3][2] = {{mx, fold(my)}, {mx, fold(-my)}, {0, 0}};
+    for (const auto& mn : cand) {
+      bool dup = false;
+      for (int j = 0; j < modes_spec.nmodes; ++j) dup = dup || (modes_spec.m[j] == mn[0] && modes_spec.n[j] == mn[1]);
+      if (dup) continue;
+      modes_spec.m[modes_spec.nmodes] = mn[0];
+      modes_spec.n[modes_spec.nmodes] = mn[1];
+      ++modes_spec.nmodes;
+    }
+  }
   if (nsave == 0) nsave = nsteps / 2 ? nsteps / 2 : 1;  // LBM.h:123
   if (print_current == 0) print_current = 1;
 
@@ -195,6 +290,9 @@ int main(int argc, char* argv[]) {
   if (chargeinf >= 0.0) P.chargeinf = chargeinf;
   if (Ra >= 0.0) P.Ra = Ra;
   if (TH >= 0.0) P.TH = TH;
+
+  if (seeding && ekpnp_seed_spec_check(&P, &seed_spec) != EKPNP_OK) { std::fprintf(stderr, "ekpnp_main: --seed-*: %s\n", ekpnp_last_error(nullptr)); return 2; }
+  if (modes_every && ekpnp_modes_spec_check(&P, &modes_spec) != EKPNP_OK) { std::fprintf(stderr, "ekpnp_main: --modes*: %s\n", ekpnp_last_error(nullptr)); return 2; }
 
   // main.cu:40-52
   std::printf("Simulating 3D electrokinetic flow with heat transfer vortices\n");
@@ -248,6 +346,10 @@ int main(int argc, char* argv[]) {
     t = 0.0;
   }
   CK(RUN(set_time, t));
+  if (seeding && (seed_spec.amplitude != 0.0 || seed_spec.noise != 0.0)) {  // (A = B = 0 adds nothing: the fields and phi stay what the start-up left)
+    CK(RUN(seed, &seed_spec));     // enqueues only: the pass runs on the device, no field moves
+    CK(RUN(fast_poisson));         // phi and E of the seeded c, cn
+  }
   CK(RUN(init_equilibrium));                             // main.cu:174
   CK(RUN(save_data_tecplot, f_data.c_str(), 0, t, 1));   // main.cu:178-179 ("wb+")
   { FILE* f = std::fopen(f_umax.c_str(), "wb"); if (f) std::fclose(f); }  // main.cu:180
@@ -258,6 +360,7 @@ int main(int argc, char* argv[]) {
     if (mon_spec.capacity < 1) mon_spec.capacity = 1;
     CK(RUN(monitor_arm, &mon_spec));
   }
+  if (modes_every) CK(RUN(modes_arm, &modes_spec, (int)((nsteps + modes_every - 1) / modes_every ? (nsteps + modes_every - 1) / modes_every : 1)));  // a ring that holds the whole run
   CK(RUN(synchronize));
   const auto begin = std::chrono::steady_clock::now();  // main.cu:185-186
   for (unsigned i = 0; i < nsteps; i++) {               // main.cu:189-224
@@ -265,7 +368,7 @@ int main(int argc, char* argv[]) {
       // iterations i .. j in one call, j = the next iteration something looks at the fields (or the last one)
       unsigned j = i;
       while (j + 1 < nsteps && !(j % nsave == 1 || j % print_current == 1 || (profiles_every && (j + 1) % profiles_every == 0) ||
-                                 (snap_every && (j + 1) % snap_every == 0))) ++j;
+                                 (snap_every && (j + 1) % snap_every == 0) || (modes_every && (j + 1) % modes_every == 0))) ++j;
       CK(RUN(step, (int)(j - i + 1)));
       for (unsigned k = i; k <= j; ++k) t = t + P.dt;  // the same additions as the loop below makes, so the files carry the same time
       i = j;
@@ -285,6 +388,7 @@ int main(int argc, char* argv[]) {
       CK(RUN(record_umax, f_umax.c_str(), 1, t));
     }
     if (monitor_every && !batch && (i + 1) % monitor_every == 0) CK(RUN(monitor_record, (int64_t)(i + 1), t));  // enqueues only (--batch 1: ekpnp_step has done it)
+    if (modes_every && (i + 1) % modes_every == 0) CK(RUN(modes_record, (int64_t)(i + 1), t));  // enqueues only
     if (profiles_every && (i + 1) % profiles_every == 0) CK(RUN(stats_accumulate));  // enqueues only: the loop runs on
     if (snap_every && (i + 1) % snap_every == 0) {
       char name[32];
@@ -309,6 +413,7 @@ int main(int argc, char* argv[]) {
   if (binary_state) CK(RUN(save_state, f_bin.c_str(), t));
   if (profiles_every) CK(RUN(save_profiles, (out + "/profiles.dat").c_str(), t));
   if (monitor_every) CK(RUN(monitor_save, (out + "/monitor.dat").c_str()));
+  if (modes_every) CK(RUN(modes_save, (out + "/modes.dat").c_str()));
   CK(grp ? ekpnp_group_destroy(grp) : ekpnp_destroy(ctx));    // main.cu:264-290
   return 0;
 }

@@ -1618,3 +1618,78 @@ extern "C" int ekpnp_group_monitor_save(ekpnp_group* g, const char* path) {
   if (int rc = ekpnp_group_monitor_read(g, 0, n, steps.data(), times.data(), values.data())) return rc;
   return monitor_write_file(path, S(T, 0).p, monitor_last_every(S(T, 0)), rec, dropped, n, steps.data(), times.data(), values.data(), T.err);
 }
+
+// ---- seeding (seed.hip) over the slabs: every slab seeds its own planes on its own device; the noise depends on the global
+// node index and the tables on the global z, so the whole lattice ends up with a single context's bits.  Enqueues only.
+extern "C" int ekpnp_group_seed(ekpnp_group* g, const ekpnp_seed_spec* spec) {
+  NEEDLIVEGROUP(g);
+  if (int rc = seed_check_spec(S(T, 0).p, spec, T.err)) return rc;  // refused before any slab has launched anything
+  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) { return ekpnp_seed(m, spec); }));
+}
+
+// ---- mode projection (modes.hip) over the slabs: slabs are cut along z, so a plane's (a, b) live on one slab; every slab
+// records its own energies and the host adds them in ascending slab order
+extern "C" int ekpnp_group_mode_amplitudes(ekpnp_group* g, const ekpnp_modes_spec* spec, double* host_out) {
+  NEEDLIVEGROUP(g);
+  if (!host_out) { T.err = "NULL pointer"; return EKPNP_ERR_INVALID; }
+  const ekpnp_params& p = S(T, 0).p;
+  if (int rc = modes_check_spec(p, spec, T.err)) return rc;
+  std::vector<double> v;
+  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) {
+    const Ctx& c = m->c;
+    v.resize((size_t)spec->nmodes * c.nzl * 2);
+    const int rc = ekpnp_mode_amplitudes(m, spec, v.data());
+    if (rc == EKPNP_OK)
+      for (int j = 0; j < spec->nmodes; ++j)
+        std::memcpy(host_out + ((size_t)j * p.nz + c.z0) * 2, v.data() + (size_t)j * c.nzl * 2, (size_t)c.nzl * 2 * sizeof(double));
+    return rc;
+  }));
+}
+extern "C" int ekpnp_group_modes_arm(ekpnp_group* g, const ekpnp_modes_spec* spec, int capacity) {
+  NEEDLIVEGROUP(g);
+  if (int rc = modes_check_spec(S(T, 0).p, spec, T.err)) return rc;
+  if (capacity < 1) { T.err = "modes: capacity = " + std::to_string(capacity) + " (must be >= 1)"; return EKPNP_ERR_INVALID; }
+  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) { return ekpnp_modes_arm(m, spec, capacity); }));
+}
+extern "C" int ekpnp_group_modes_disarm(ekpnp_group* g) {
+  NEEDLIVEGROUP(g);
+  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) { return ekpnp_modes_disarm(m); }));
+}
+// enqueues only, on every slab's compute stream (as ekpnp_group_stats_accumulate)
+extern "C" int ekpnp_group_modes_record(ekpnp_group* g, int64_t step, double time) {
+  NEEDLIVEGROUP(g);
+  if (!modes_armed(S(T, 0))) { T.err = "ekpnp_modes_record: no mode tracking armed"; return EKPNP_ERR_INVALID; }  // (refused before any slab is asked: the group stays usable)
+  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) { return ekpnp_modes_record(m, step, time); }));
+}
+extern "C" int ekpnp_group_modes_count(const ekpnp_group* g, int64_t* recorded, int64_t* dropped) {
+  if (!g || g->t.m.empty()) return EKPNP_ERR_INVALID;
+  return ekpnp_modes_count(g->t.m[0], recorded, dropped);  // the slabs record in step
+}
+extern "C" int ekpnp_group_modes_read(ekpnp_group* g, int64_t first, int count, int64_t* steps, double* times, double* values) {
+  NEEDLIVEGROUP(g);
+  const ekpnp_modes_spec* spec = modes_armed_spec(S(T, 0));
+  const size_t nm = spec ? (size_t)spec->nmodes : 0;
+  std::vector<double> v((size_t)(count > 0 ? count : 0) * nm);
+  bool head = true;
+  return team_monitor_each(T, [&](ekpnp_ctx* m) {
+    const int rc = ekpnp_modes_read(m, first, count, steps, times, v.data());
+    if (rc == EKPNP_OK && count > 0) {
+      for (size_t k = 0; k < v.size(); ++k) values[k] = head ? v[k] : values[k] + v[k];
+      head = false;
+    }
+    return rc;
+  });
+}
+extern "C" int ekpnp_group_modes_save(ekpnp_group* g, const char* path) {
+  NEEDLIVEGROUP(g);
+  if (!path) { T.err = "NULL path"; return EKPNP_ERR_INVALID; }
+  const ekpnp_modes_spec* spec = modes_armed_spec(S(T, 0));
+  if (!spec) { T.err = "ekpnp_modes_save: no mode tracking was armed"; return EKPNP_ERR_INVALID; }
+  int64_t rec = 0, dropped = 0;
+  (void)ekpnp_group_modes_count(g, &rec, &dropped);
+  const int n = (int)(rec - dropped);
+  std::vector<int64_t> steps((size_t)n);
+  std::vector<double> times((size_t)n), values((size_t)n * spec->nmodes);
+  if (int rc = ekpnp_group_modes_read(g, 0, n, steps.data(), times.data(), values.data())) return rc;
+  return modes_write_file(path, S(T, 0).p, *spec, rec, dropped, n, steps.data(), times.data(), values.data(), T.err);
+}

@@ -98,6 +98,98 @@ def _monitor_read(L, fn, handle, ck, first: int, count: int):
     return steps, times, values
 
 
+SEED_PATTERNS = {"none": 0, "noise": 0, "rolls": 1, "squares": 2, "hexagons": 3}  # include/ekpnp.h: EKPNP_SEED_*
+MAX_MODES = 16
+
+
+class SeedSpec(C.Structure):
+    """Mirror of `ekpnp_seed_spec` (include/ekpnp.h): which fields, which pattern with how many periods across nx and ny,
+    relative or absolute, the noise seed, the pattern's amplitude A and the noise's B."""
+
+    _fields_ = [("fields", C.c_uint32), ("pattern", C.c_int32), ("mx", C.c_int32), ("my", C.c_int32), ("relative", C.c_int32),
+                ("reserved", C.c_int32), ("seed", C.c_uint64), ("amplitude", C.c_double), ("noise", C.c_double)]
+
+
+def seed_spec(fields=("c", "cn"), pattern="squares", modes=(1, 1), amplitude: float = 1e-3, noise: float = 0.0, relative: bool = True,
+              seed: int = 1) -> SeedSpec:
+    """fields: a bit mask over the field ids or names out of rho, c, cn, ux, uy, uz, T; pattern: a name of SEED_PATTERNS or its id"""
+    if isinstance(fields, int):
+        mask = fields
+    else:
+        mask = 0
+        for n in fields:
+            mask |= 1 << (FIELD_ID[n] if isinstance(n, str) else int(n))
+    pat = SEED_PATTERNS[pattern] if isinstance(pattern, str) else int(pattern)
+    return SeedSpec(mask, pat, int(modes[0]), int(modes[1]), int(relative), 0, int(seed), float(amplitude), float(noise))
+
+
+class ModesSpec(C.Structure):
+    """Mirror of `ekpnp_modes_spec` (include/ekpnp.h): the field and up to MAX_MODES x-y modes (m, n) to project it onto."""
+
+    _fields_ = [("field_id", C.c_int32), ("nmodes", C.c_int32), ("m", C.c_int32 * MAX_MODES), ("n", C.c_int32 * MAX_MODES)]
+
+
+def modes_spec(field="uz", modes=((1, 1),)) -> ModesSpec:
+    """field: a name or an id; modes: pairs (m, n) with 0 <= m <= nx/2 and -(ny-1)/2 <= n <= ny/2"""
+    modes = [(int(m), int(n)) for m, n in modes]
+    spec = ModesSpec()
+    spec.field_id = FIELD_ID[field] if isinstance(field, str) else int(field)
+    spec.nmodes = len(modes)
+    for j, (m, n) in enumerate(modes[:MAX_MODES]):
+        spec.m[j], spec.n[j] = m, n
+    return spec
+
+
+def _as_modes_spec(field, modes) -> ModesSpec:
+    return field if isinstance(field, ModesSpec) else modes_spec(field, modes)
+
+
+def seed_spec_check(p: "Params", spec: SeedSpec) -> SeedSpec:
+    """the spec, or EkpnpError with the library's message (ekpnp_seed_spec_check: host arithmetic, no device)"""
+    L = load_library()
+    rc = L.ekpnp_seed_spec_check(C.byref(p), C.byref(spec))
+    if rc:
+        raise EkpnpError(f"ekpnp_seed_spec_check -> status {rc}: {L.ekpnp_last_error(None).decode()}")
+    return spec
+
+
+def modes_spec_check(p: "Params", spec: ModesSpec) -> ModesSpec:
+    """the spec, or EkpnpError with the library's message (ekpnp_modes_spec_check: host arithmetic, no device)"""
+    L = load_library()
+    rc = L.ekpnp_modes_spec_check(C.byref(p), C.byref(spec))
+    if rc:
+        raise EkpnpError(f"ekpnp_modes_spec_check -> status {rc}: {L.ekpnp_last_error(None).decode()}")
+    return spec
+
+
+def seed_uniform(seed: int, node: int, field) -> float:
+    """the noise of (seed, global node index, field): Philox4x32-10, exact in [-1, 1) (ekpnp_seed_uniform, host only)"""
+    fid = FIELD_ID[field] if isinstance(field, str) else int(field)
+    return float(load_library().ekpnp_seed_uniform(int(seed), int(node), fid))
+
+
+def seed_host(p: "Params", spec: SeedSpec, field, planes, z0: int = 0) -> np.ndarray:
+    """THE definition of a seed, on the host: a seeded copy of `planes` ([nz_local][ny][nx], the global planes z0 ..) of `field`
+    (ekpnp_seed_host; Solver.seed leaves the same bits in the device arrays)"""
+    L = load_library()
+    fid = FIELD_ID[field] if isinstance(field, str) else int(field)
+    a = np.array(planes, dtype=np.float64, order="C", copy=True)
+    if a.ndim != 3 or a.shape[1:] != (p.ny, p.nx):
+        raise ValueError(f"planes must be [nz_local][{p.ny}][{p.nx}], got {a.shape}")
+    rc = L.ekpnp_seed_host(C.byref(p), C.byref(spec), fid, int(z0), int(a.shape[0]), a.ctypes.data_as(C.c_void_p))
+    if rc:
+        raise EkpnpError(f"ekpnp_seed_host -> status {rc}: {L.ekpnp_last_error(None).decode()}")
+    return a
+
+
+def _modes_read(L, fn, handle, ck, nmodes: int, first: int, count: int):
+    steps = np.zeros(max(count, 0), dtype=np.int64)
+    times = np.zeros(max(count, 0), dtype=np.float64)
+    values = np.zeros((max(count, 0), nmodes), dtype=np.float64)
+    ck(fn(handle, int(first), int(count), steps.ctypes.data_as(C.c_void_p), times.ctypes.data_as(C.c_void_p), values.ctypes.data_as(C.c_void_p)))
+    return steps, times, values
+
+
 def _snapshot_names(spec: SnapshotSpec) -> list:
     return [n for i, n in enumerate(FIELDS) if spec.fields == 0 or (spec.fields >> i) & 1]
 
@@ -291,6 +383,28 @@ def load_library():
         "ekpnp_group_monitor_count": (i32, [ctx, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
         "ekpnp_group_monitor_read": (i32, [ctx, C.c_int64, i32, C.c_void_p, C.c_void_p, C.c_void_p]),
         "ekpnp_group_monitor_save": (i32, [ctx, C.c_char_p]),
+        # seeding x-y structure
+        "ekpnp_seed_spec_check": (i32, [C.POINTER(Params), C.POINTER(SeedSpec)]),
+        "ekpnp_seed_uniform": (dbl, [C.c_uint64, C.c_uint64, i32]),
+        "ekpnp_seed_host": (i32, [C.POINTER(Params), C.POINTER(SeedSpec), i32, i32, i32, C.c_void_p]),
+        "ekpnp_seed": (i32, [ctx, C.POINTER(SeedSpec)]),
+        "ekpnp_group_seed": (i32, [ctx, C.POINTER(SeedSpec)]),
+        # projection onto chosen x-y modes and its time series
+        "ekpnp_modes_spec_check": (i32, [C.POINTER(Params), C.POINTER(ModesSpec)]),
+        "ekpnp_mode_amplitudes": (i32, [ctx, C.POINTER(ModesSpec), C.c_void_p]),
+        "ekpnp_modes_arm": (i32, [ctx, C.POINTER(ModesSpec), i32]),
+        "ekpnp_modes_disarm": (i32, [ctx]),
+        "ekpnp_modes_record": (i32, [ctx, C.c_int64, dbl]),
+        "ekpnp_modes_count": (i32, [ctx, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+        "ekpnp_modes_read": (i32, [ctx, C.c_int64, i32, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "ekpnp_modes_save": (i32, [ctx, C.c_char_p]),
+        "ekpnp_group_mode_amplitudes": (i32, [ctx, C.POINTER(ModesSpec), C.c_void_p]),
+        "ekpnp_group_modes_arm": (i32, [ctx, C.POINTER(ModesSpec), i32]),
+        "ekpnp_group_modes_disarm": (i32, [ctx]),
+        "ekpnp_group_modes_record": (i32, [ctx, C.c_int64, dbl]),
+        "ekpnp_group_modes_count": (i32, [ctx, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+        "ekpnp_group_modes_read": (i32, [ctx, C.c_int64, i32, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "ekpnp_group_modes_save": (i32, [ctx, C.c_char_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError if the library does not export it
@@ -636,6 +750,52 @@ class Solver:
     def monitor_save(self, path: str):
         self._ck(self._L.ekpnp_monitor_save(self._h, os.fsencode(path)))
 
+    # -- seeding x-y structure and tracking chosen x-y modes (no reference counterpart) -----------
+    def seed(self, spec: SeedSpec = None, **kw):
+        """add a pattern and / or reproducible noise to the selected field arrays on the device (ekpnp_seed: enqueues only, no
+        field moves; the bits of get_field, seed_host, set_field).  Then fast_Poisson() and init_equilibrium().  spec, or the
+        keywords of seed_spec()."""
+        spec = spec if spec is not None else seed_spec(**kw)
+        self._ck(self._L.ekpnp_seed(self._h, C.byref(spec)))
+
+    def mode_amplitudes(self, field="uz", modes=((1, 1),)) -> np.ndarray:
+        """[nmodes][self.nz_local][2]: per plane a = sum v cos(theta), b = sum v sin(theta), theta = 2 pi (m x/nx + n y/ny), unnormalised
+        (ekpnp_mode_amplitudes; complete on return).  field may be a ModesSpec."""
+        spec = _as_modes_spec(field, modes)
+        out = np.zeros((max(spec.nmodes, 0), self.nz_local, 2), dtype=np.float64)
+        self._ck(self._L.ekpnp_mode_amplitudes(self._h, C.byref(spec), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def modes_arm(self, field="uz", modes=((1, 1),), capacity: int = 1024):
+        """track the energies E = sum_z (a^2 + b^2) of the modes in a ring of `capacity` rows in device memory; rows are appended by
+        modes_record() only"""
+        spec = _as_modes_spec(field, modes)
+        self._ck(self._L.ekpnp_modes_arm(self._h, C.byref(spec), int(capacity)))
+        self._modes_n = spec.nmodes
+
+    def modes_disarm(self):
+        self._ck(self._L.ekpnp_modes_disarm(self._h))
+
+    def modes_record(self, step: int, time: float):
+        """append a row with the caller's labels; enqueues only (place it between two step() calls)"""
+        self._ck(self._L.ekpnp_modes_record(self._h, int(step), float(time)))
+
+    def modes_count(self):
+        """(rows recorded since arming, rows lost to overflow); host-known, never synchronises"""
+        r, d = C.c_int64(), C.c_int64()
+        self._ck(self._L.ekpnp_modes_count(self._h, C.byref(r), C.byref(d)))
+        return int(r.value), int(d.value)
+
+    def modes_read(self, first: int = 0, count: int = None):
+        """(steps[n], times[n], energies[n][nmodes]) of the rows still held, oldest first; count None: all from `first` on"""
+        if count is None:
+            r, d = self.modes_count()
+            count = r - d - first
+        return _modes_read(self._L, self._L.ekpnp_modes_read, self._h, self._ck, getattr(self, "_modes_n", 0), first, count)
+
+    def modes_save(self, path: str):
+        self._ck(self._L.ekpnp_modes_save(self._h, os.fsencode(path)))
+
     def tune(self, knob: str, value: int):
         self._ck(self._L.ekpnp_tune(self._h, knob.encode(), int(value)))
 
@@ -952,6 +1112,52 @@ class Group:
 
     def monitor_save(self, path: str):
         self._ck(self._L.ekpnp_group_monitor_save(self._g, os.fsencode(path)))
+
+    # -- seeding x-y structure and tracking chosen x-y modes (no reference counterpart) -----------
+    def seed(self, spec: SeedSpec = None, **kw):
+        """add a pattern and / or reproducible noise to the selected field arrays on the device (ekpnp_group_seed: enqueues only, no
+        field moves; the bits of get_field, seed_host, set_field).  Then fast_Poisson() and init_equilibrium().  spec, or the
+        keywords of seed_spec()."""
+        spec = spec if spec is not None else seed_spec(**kw)
+        self._ck(self._L.ekpnp_group_seed(self._g, C.byref(spec)))
+
+    def mode_amplitudes(self, field="uz", modes=((1, 1),)) -> np.ndarray:
+        """[nmodes][self.p.nz][2]: per plane a = sum v cos(theta), b = sum v sin(theta), theta = 2 pi (m x/nx + n y/ny), unnormalised
+        (ekpnp_group_mode_amplitudes; complete on return).  field may be a ModesSpec."""
+        spec = _as_modes_spec(field, modes)
+        out = np.zeros((max(spec.nmodes, 0), self.p.nz, 2), dtype=np.float64)
+        self._ck(self._L.ekpnp_group_mode_amplitudes(self._g, C.byref(spec), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def modes_arm(self, field="uz", modes=((1, 1),), capacity: int = 1024):
+        """track the energies E = sum_z (a^2 + b^2) of the modes in a ring of `capacity` rows in device memory; rows are appended by
+        modes_record() only"""
+        spec = _as_modes_spec(field, modes)
+        self._ck(self._L.ekpnp_group_modes_arm(self._g, C.byref(spec), int(capacity)))
+        self._modes_n = spec.nmodes
+
+    def modes_disarm(self):
+        self._ck(self._L.ekpnp_group_modes_disarm(self._g))
+
+    def modes_record(self, step: int, time: float):
+        """append a row with the caller's labels; enqueues only (place it between two step() calls)"""
+        self._ck(self._L.ekpnp_group_modes_record(self._g, int(step), float(time)))
+
+    def modes_count(self):
+        """(rows recorded since arming, rows lost to overflow); host-known, never synchronises"""
+        r, d = C.c_int64(), C.c_int64()
+        self._ck(self._L.ekpnp_group_modes_count(self._g, C.byref(r), C.byref(d)))
+        return int(r.value), int(d.value)
+
+    def modes_read(self, first: int = 0, count: int = None):
+        """(steps[n], times[n], energies[n][nmodes]) of the rows still held, oldest first; count None: all from `first` on"""
+        if count is None:
+            r, d = self.modes_count()
+            count = r - d - first
+        return _modes_read(self._L, self._L.ekpnp_group_modes_read, self._g, self._ck, getattr(self, "_modes_n", 0), first, count)
+
+    def modes_save(self, path: str):
+        self._ck(self._L.ekpnp_group_modes_save(self._g, os.fsencode(path)))
 
     def save_checkpoint(self, path: str):
         self._ck(self._L.ekpnp_group_save_checkpoint(self._g, os.fsencode(path)))

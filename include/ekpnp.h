@@ -418,6 +418,93 @@ int ekpnp_monitor_count(const ekpnp_ctx* ctx, int64_t* recorded, int64_t* droppe
 int ekpnp_monitor_read(ekpnp_ctx* ctx, int64_t first, int count, int64_t* steps, double* times, double* values);
 int ekpnp_monitor_save(ekpnp_ctx* ctx, const char* path);
 
+/* ---- seeding x-y structure on the device (the reference's dead `perturb` branch, LBM.cu:646-661) ------------------------
+ * ekpnp_initialization leaves every field uniform in x and y (LBM.cu:68-109), so a run stays one-dimensional until rounding
+ * noise breaks the symmetry - after an uncontrolled time and with an uncontrolled pattern.  A seed adds a chosen pattern (rolls,
+ * the reference's squares and hexagons) and / or reproducible white noise to chosen fields, in one streaming pass on the device:
+ * no field crosses the bus.  For every node with global 1 <= z <= nz-2 (the plates z = 0 and z = nz-1 are never written), every
+ * operation rounded once, no fused multiply-add:
+ *   cX[x] = cos(2.0*M_PI*(double)((mx*x) mod nx)/(double)nx), sX[x] likewise with sin; cY[y], sY[y] likewise with my, ny;
+ *   c2Y[y] = cos(2.0*M_PI*(double)((2*my*y) mod ny)/(double)ny); env[z] = sin(M_PI*(double)z/(double)(nz-1))
+ *   (64-bit integer products, non-negative remainders, the host's <cmath>)
+ *   h = NONE: 0.0 | ROLLS: cX*cY - sX*sY | SQUARES: cX*cY (LBM.cu:651) | HEXAGONS: (2.0*(cX*cY) + c2Y)/3.0 (LBM.cu:657)
+ *   r = the uniform number of (seed, global node (z*ny + y)*nx + x, field id), below
+ *   p = A*h;  q = B*r;  t = p + q;  s = env[z]*t;  v = relative ? v + v*s : v + s
+ * The noise depends on the global node index only: a pattern plus noise is the same bits however the lattice is held or cut.
+ * Hexagons are regular when mx/Lx = sqrt(3)*my/Ly - that is the caller's business.  The divergence-free ux, uy companions of
+ * LBM.cu:652-653 are not built: a seeded uz relaxes in a few steps.
+ * The uniform number is Philox4x32-10 with counter (node & 0xffffffff, node >> 32, field_id, 0) and key (seed & 0xffffffff,
+ * seed >> 32) (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85); with output words w0..w3,
+ * k = (w0 >> 5)*2^26 + (w1 >> 6) and r = (double)k * 2^-52 - 1.0, exact, in [-1, 1). */
+enum { EKPNP_SEED_NONE = 0, EKPNP_SEED_ROLLS = 1, EKPNP_SEED_SQUARES = 2, EKPNP_SEED_HEXAGONS = 3 };
+typedef struct ekpnp_seed_spec {   /* 48 bytes, no padding surprises */
+  uint32_t fields;      /* bit mask over EKPNP_RHO, _C, _CN, _UX, _UY, _UZ, _T */
+  int32_t  pattern;     /* EKPNP_SEED_*                                        */
+  int32_t  mx, my;      /* whole periods across nx and ny                      */
+  int32_t  relative;    /* 1: v += v*s   0: v += s                             */
+  int32_t  reserved;    /* must be 0                                           */
+  uint64_t seed;
+  double   amplitude;   /* A, of the pattern                                   */
+  double   noise;       /* B, of the white noise                               */
+} ekpnp_seed_spec;
+/* Host only, needs no device.  Refused with EKPNP_ERR_INVALID and a message that names the offending number (ekpnp_last_error
+ * of NULL): fields == 0, a bit for phi, Ex, Ey or Ez or above 10, a pattern outside 0..3, mx outside 0..nx/2, my outside
+ * -ny/2..ny/2, hexagons with |2*my| > ny/2, relative outside 0..1, reserved != 0, a non-finite amplitude or noise, nz < 3. */
+int    ekpnp_seed_spec_check(const ekpnp_params* p, const ekpnp_seed_spec* spec);
+double ekpnp_seed_uniform(uint64_t seed, uint64_t node, int field_id);                 /* host only */
+/* Host only: THE definition.  In place on planes[nz_local][ny][nx], which holds the global planes z0 .. z0 + nz_local - 1 of
+ * field field_id (field_id need not be selected by spec->fields: the caller chooses). */
+int    ekpnp_seed_host(const ekpnp_params* p, const ekpnp_seed_spec* spec, int field_id, int z0, int nz_local, double* planes);
+/* The device pass: every selected field array of this context ends up exactly - bit for bit - as ekpnp_get_field,
+ * ekpnp_seed_host, ekpnp_set_field would leave it, but the call ONLY ENQUEUES on the context's stream and moves no field.  Like
+ * ekpnp_set_field it changes the field arrays, not the populations, and the collide's Poisson right-hand side is forgotten: the
+ * sequence is initialization (or a restart read), seed, ekpnp_fast_poisson, ekpnp_init_equilibrium.  Works on two-buffer and
+ * in-place contexts, on stand-alone and attached slabs (each seeds its own planes, nothing is exchanged), on groups and on
+ * caller-bound arrays (ekpnp_bind_field).  The tables (at most 2 nx + 3 ny + nz doubles) live in one small device buffer kept by
+ * the context and counted by ekpnp_device_bytes. */
+int    ekpnp_seed(ekpnp_ctx* ctx, const ekpnp_seed_spec* spec);
+
+/* ---- projection onto chosen x-y Fourier modes and its time series (no reference counterpart) ---------------------------
+ * The first thing plotted of a seeded pattern: the amplitude of its Fourier mode against time - the linear growth rate, which
+ * mode wins, when it saturates.  Per plane z and mode (m, n), with theta = 2 pi (m x/nx + n y/ny):
+ *   a = sum v cos(theta),  b = sum v sin(theta)   over the plane's nx*ny nodes, unnormalised like ekpnp_plane_sums;
+ * a - i b is the coefficient fft2(v)[n mod ny, m].  A pattern A cos(theta) gives a = A nx ny / 2 (A nx ny for (0,0) and the
+ * Nyquist modes).  No transform: one pass reads the field ONCE for all modes (8 B per node whatever nmodes is);
+ * cos(theta) = cX*cY - sX*sY and sin(theta) = sX*cY + cX*sY from per-mode tables cX, sX [nmodes][nx], cY, sY [nmodes][ny]
+ * (the expressions of the seed's tables, built on the host).  The values are those ekpnp_get_field would return; for phi or
+ * E a lazy solve's arrays are brought up to date first, so TRACKING phi OR E GIVES UP THE LAZY-E SAVING AT RECORDED STEPS.
+ * Reproducibility: the reduction scheme of ekpnp_plane_sums - no atomics, the order of the additions depends on nx*ny alone -
+ * so a plane's (a, b) are the same bits in a two-buffer, an in-place, a slab context and any group. */
+#define EKPNP_MAX_MODES 16
+typedef struct ekpnp_modes_spec {
+  int32_t field_id;                 /* any of the eleven */
+  int32_t nmodes;                   /* 1 .. 16           */
+  int32_t m[EKPNP_MAX_MODES];       /* 0 <= m <= nx/2    */
+  int32_t n[EKPNP_MAX_MODES];       /* -(ny-1)/2 <= n <= ny/2 */
+} ekpnp_modes_spec;
+/* Host only; the message of a refused spec (it names the offending number) is ekpnp_last_error of NULL. */
+int ekpnp_modes_spec_check(const ekpnp_params* p, const ekpnp_modes_spec* spec);
+/* Synchronous and one-off: (a, b) of this context's planes into host_out[nmodes][nz_local][2].  Needs nothing armed. */
+int ekpnp_mode_amplitudes(ekpnp_ctx* ctx, const ekpnp_modes_spec* spec, double* host_out);
+/* The time series.  arm uploads the tables and allocates the ring [capacity][nmodes] and the partial-sum scratch (counted by
+ * ekpnp_device_bytes, freed by ekpnp_destroy); arming again resets the ring.  record is an explicit ENQUEUE between two
+ * ekpnp_step calls, like ekpnp_stats_accumulate - nothing is appended from inside ekpnp_step, so the step graph,
+ * "batch_moments" and lazy E for the moment fields are left alone.  A row holds, per mode, the energy
+ * E = sum_z (a(z)^2 + b(z)^2) over the context's planes in ascending z, formed as e = a*a; e = e + b*b; E = E + e; the growth
+ * rate follows from E ~ exp(2 sigma t).  When the ring is full the oldest row is overwritten (dropped counts the rows lost);
+ * count is host-known and never synchronises; read synchronises and returns rows first .. first + count - 1 of those still
+ * held, oldest first (values is [count][nmodes]), a range outside what is held is EKPNP_ERR_INVALID.  An attached slab records
+ * its own rank's planes (no collective); a group's read adds the slabs' energies in ascending slab order.  The ring is NOT part
+ * of checkpoint or state files.  save writes text: line 1 "# ekpnp modes nx <nx> ny <ny> nz <nz> field <name> recorded <r>
+ * dropped <d>", line 2 "# step time E_<m>_<n> ...", then one row per held sample: the label (%lld), the time and the energies
+ * (%.17g), single spaces. */
+int ekpnp_modes_arm(ekpnp_ctx* ctx, const ekpnp_modes_spec* spec, int capacity);
+int ekpnp_modes_disarm(ekpnp_ctx* ctx);
+int ekpnp_modes_record(ekpnp_ctx* ctx, int64_t step, double time);                                /* enqueues only */
+int ekpnp_modes_count(const ekpnp_ctx* ctx, int64_t* recorded, int64_t* dropped);
+int ekpnp_modes_read(ekpnp_ctx* ctx, int64_t first, int count, int64_t* steps, double* times, double* values);
+int ekpnp_modes_save(ekpnp_ctx* ctx, const char* path);
+
 /* ---- measurement hooks (bench.py; no reference counterpart) ------------------ */
 /* When enabled, every launch of the bulk collide/stream kernel is bracketed by
  * HIP events on the context's stream; the sum is returned by ..._get. */
@@ -691,6 +778,18 @@ int ekpnp_group_monitor_record(ekpnp_group* g, int64_t step, double time);   /* 
 int ekpnp_group_monitor_count(const ekpnp_group* g, int64_t* recorded, int64_t* dropped);
 int ekpnp_group_monitor_read(ekpnp_group* g, int64_t first, int count, int64_t* steps, double* times, double* values);
 int ekpnp_group_monitor_save(ekpnp_group* g, const char* path);
+/* the seed above on every slab's own planes, each on its own device (no exchange): the whole lattice ends up with the bits of
+ * a single context */
+int ekpnp_group_seed(ekpnp_group* g, const ekpnp_seed_spec* spec);            /* enqueues only */
+/* the mode projection above over the whole lattice: host_out is [nmodes][NZ][2] with slab i's planes at its z0; every slab
+ * records its own energies and read adds them in ascending slab order */
+int ekpnp_group_mode_amplitudes(ekpnp_group* g, const ekpnp_modes_spec* spec, double* host_out);
+int ekpnp_group_modes_arm(ekpnp_group* g, const ekpnp_modes_spec* spec, int capacity);
+int ekpnp_group_modes_disarm(ekpnp_group* g);
+int ekpnp_group_modes_record(ekpnp_group* g, int64_t step, double time);     /* enqueues only */
+int ekpnp_group_modes_count(const ekpnp_group* g, int64_t* recorded, int64_t* dropped);
+int ekpnp_group_modes_read(ekpnp_group* g, int64_t first, int count, int64_t* steps, double* times, double* values);
+int ekpnp_group_modes_save(ekpnp_group* g, const char* path);
 
 #ifdef __cplusplus
 }
