@@ -13,6 +13,7 @@ from .solver import (  # noqa: F401
     EkpnpError,
     Group,
     MAX_MODES,
+    MAX_SPECTRUM_PLANES,
     MONITOR_ID,
     MONITOR_NAMES,
     ModesSpec,
@@ -25,6 +26,7 @@ from .solver import (  # noqa: F401
     SeedSpec,
     SnapshotSpec,
     Solver,
+    SpectrumSpec,
     TRANSPORT_AUTO,
     TRANSPORT_COPY,
     TRANSPORT_RCCL,
@@ -46,4 +48,7 @@ from .solver import (  # noqa: F401
     slab_extent,
     snapshot_extent,
     snapshot_spec,
+    spectrum_shells,
+    spectrum_spec,
+    spectrum_spec_check,
 )

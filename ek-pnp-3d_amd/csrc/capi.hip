@@ -526,6 +526,7 @@ extern "C" int ekpnp_destroy(ekpnp_ctx* ctx) {
   monitor_release(c);
   modes_release(c);
   seed_release(c);
+  spectrum_release(c);
   for (int k = 0; k < 4; ++k) {
     if (c.halo[k]) (void)hipFree(c.halo[k]);
     if (c.phi_halo[k]) (void)hipFree(c.phi_halo[k]);
@@ -552,6 +553,7 @@ extern "C" int ekpnp_set_stream(ekpnp_ctx* ctx, void* s) {
   c.stream = (hipStream_t)s;
   if (c.have_fwd) FFTCHK(c, hipfftSetStream(c.plan_fwd, c.stream));
   if (c.have_inv) FFTCHK(c, hipfftSetStream(c.plan_inv, c.stream));
+  if (int rc = spectrum_set_stream(c)) return rc;
   return EKPNP_OK;
 }
 

@@ -245,6 +245,16 @@ bool modes_armed(const Ctx&);
 void modes_release(Ctx&);                              // ekpnp_destroy
 int modes_write_file(const char* path, const ekpnp_params& p, const ekpnp_modes_spec& spec, int64_t recorded, int64_t dropped, int n,
                      const int64_t* steps, const double* times, const double* values, std::string& err);
+// spectrum.hip: x-y power spectra per plane - shells, peak - and their time series (SpecState: made by the first ekpnp_spectrum_plane / ekpnp_spectrum / ekpnp_spectrum_arm)
+struct SpecState;
+int spectrum_check_spec(const ekpnp_params& p, const ekpnp_spectrum_spec* s, std::string& err);
+int spectrum_shell_count(const ekpnp_params& p, int* nshell, double* L, std::string& err);  // host arithmetic: the number of shells and L = max(Lx, Ly)
+const ekpnp_spectrum_spec* spectrum_armed_spec(const Ctx&);  // the spec of the last arm (null: never armed), for the file header
+bool spectrum_armed(const Ctx&);
+int spectrum_set_stream(Ctx&);                               // ekpnp_set_stream: the plan follows the context's stream
+void spectrum_release(Ctx&);                                 // ekpnp_destroy
+int spectrum_write_file(const char* path, const ekpnp_params& p, const ekpnp_spectrum_spec& spec, int nshell, double L, int64_t recorded, int64_t dropped,
+                        int n, const int64_t* steps, const double* times, const double* shells, const double* peaks, std::string& err);
 
 struct Ctx {
   ekpnp_params p{};
@@ -339,6 +349,7 @@ struct Ctx {
   MonState* mon = nullptr;         // scalar time series (monitor.hip), made by the first monitor call
   ModeState* modes = nullptr;      // mode projection and its time series (modes.hip), made by the first modes call
   SeedState* seed = nullptr;       // the seed's table buffer (seed.hip), made by the first ekpnp_seed
+  SpecState* spectrum = nullptr;   // plane spectra, their plan and time series (spectrum.hip), made by the first spectrum call
   int collide_phase = 0;           // 0 idle, 1 boundary planes done
   // slab edge planes without pack / unpack copies (KArgs::halo_*): knob, and where the current halos are
   bool halo_direct = true;         // EKPNP_HALO_DIRECT=0: k_halo_pack / k_halo_unpack as in rounds 1-3 (the A/B partner)

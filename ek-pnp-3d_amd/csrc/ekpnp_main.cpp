@@ -71,6 +71,10 @@ int main(int argc, char* argv[]) {
   ekpnp_modes_spec modes_spec = {};
   modes_spec.field_id = EKPNP_UZ;
   modes_spec.nmodes = 0;        // 0: the seed's (mx, my), (mx, -my) and (0, 0)
+  unsigned spectrum_every = 0;  // > 0: shells and peak of chosen planes' x-y power spectra (ekpnp_spectrum_*) after every that many iterations, spectrum.dat at the end
+  ekpnp_spectrum_spec spectrum_spec = {};
+  spectrum_spec.field_id = EKPNP_UZ;
+  spectrum_spec.nplanes = 0;    // 0: the mid plane (nz - 1)/2
   static const char* const field_names[EKPNP_NFIELDS] = {"rho", "c", "cn", "phi", "ux", "uy", "uz", "Ex", "Ey", "Ez", "T"};
   auto field_id_of = [&](const char* q, size_t len) {
     for (int k = 0; k < EKPNP_NFIELDS; ++k)
@@ -200,6 +204,25 @@ int main(int argc, char* argv[]) {
         if (*q == ';') ++q;
       }
     }
+    else if ((v = val("--spectrum-every"))) spectrum_every = (unsigned)std::atoi(v);
+    else if ((v = val("--spectrum-field"))) {
+      const int id = field_id_of(v, std::strlen(v));
+      if (id < 0) { std::fprintf(stderr, "--spectrum-field wants one of rho,c,cn,phi,ux,uy,uz,Ex,Ey,Ez,T, got %s\n", v); return 2; }
+      spectrum_spec.field_id = id;
+    }
+    else if ((v = val("--spectrum-planes"))) {
+      spectrum_spec.nplanes = 0;
+      for (const char* q = v; *q;) {
+        int z = 0, used = 0;
+        if (std::sscanf(q, "%d%n", &z, &used) != 1 || spectrum_spec.nplanes >= EKPNP_MAX_SPECTRUM_PLANES || (q[used] && q[used] != ',')) {
+          std::fprintf(stderr, "--spectrum-planes wants at most %d plane indices \"z,z,...\", got %s\n", EKPNP_MAX_SPECTRUM_PLANES, v);
+          return 2;
+        }
+        spectrum_spec.z[spectrum_spec.nplanes++] = z;
+        q += used;
+        if (*q == ',') ++q;
+      }
+    }
     else if ((v = val("--tune"))) {
       const char* eq = std::strchr(v, '=');
       if (!eq || eq == v) { std::fprintf(stderr, "--tune wants knob=value, got %s\n", v); return 2; }
@@ -216,6 +239,7 @@ int main(int argc, char* argv[]) {
                    "                  [--seed-pattern noise|rolls|squares|hexagons [--seed-modes mx,my] [--seed-amplitude A] [--seed-noise B]\n"
                    "                   [--seed-fields c,cn,...] [--seed-relative 0|1] [--seed N]]\n"
                    "                  [--modes-every N [--modes-field uz] [--modes \"m,n;m,n;...\"]]\n"
+                   "                  [--spectrum-every N [--spectrum-field uz] [--spectrum-planes z,z,...]]\n"
                    "  --seed-pattern P: after the start-up (or the restart read) a pattern with mx,my whole periods across nx and ny (default 1,1)\n"
                    "  and amplitude A (default 1e-3) plus white noise of amplitude B (default 0; reproducible from --seed N, default 1) is added to\n"
                    "  the fields --seed-fields names (default c,cn; out of rho,c,cn,ux,uy,uz,T) on the interior planes, under a sin(pi z/(nz-1))\n"
@@ -228,6 +252,12 @@ int main(int argc, char* argv[]) {
                    "  to a ring in device memory (ekpnp_modes_arm / ekpnp_modes_record: enqueued only, nothing waits); modes.dat is written at the\n"
                    "  end (ekpnp_modes_save: one row per sample, %%.17g).  With --batch 1 the batches are cut at these marks; both loops write the\n"
                    "  same bytes, and every other file is unchanged.\n"
+                   "  --spectrum-every N: after every N-th iteration the x-y power spectrum of the field --spectrum-field names (default uz) on\n"
+                   "  the planes --spectrum-planes names (at most 16 global z, ascending; default the mid plane (nz-1)/2) is taken on the device:\n"
+                   "  the shell spectrum E(k) and the dominant mode of each plane are appended to a ring in device memory (ekpnp_spectrum_arm /\n"
+                   "  ekpnp_spectrum_record: enqueued only, nothing waits); spectrum.dat is written at the end (ekpnp_spectrum_save: one row per\n"
+                   "  sample and plane, %%.17g).  With --batch 1 the batches are cut at these marks; both loops write the same bytes, and every\n"
+                   "  other file is unchanged.\n"
                    "  --monitor-every N: after every N-th iteration eleven scalars - the current through either plate, the wall gradients of\n"
                    "  T, max uz, the sums of u.u, c - cn, (c - cn)^2 and uz*T, max |rho - rho0| and the number of non-finite nodes - are reduced\n"
                    "  on the device and appended to a ring in device memory (ekpnp_monitor_arm / ekpnp_monitor_record: enqueued only, nothing\n"
@@ -277,6 +307,10 @@ int main(int argc, char* argv[]) {
       ++modes_spec.nmodes;
     }
   }
+  if (spectrum_every && spectrum_spec.nplanes == 0) {
+    spectrum_spec.nplanes = 1;
+    spectrum_spec.z[0] = (nz - 1) / 2;
+  }
   if (nsave == 0) nsave = nsteps / 2 ? nsteps / 2 : 1;  // LBM.h:123
   if (print_current == 0) print_current = 1;
 
@@ -293,6 +327,8 @@ int main(int argc, char* argv[]) {
 
   if (seeding && ekpnp_seed_spec_check(&P, &seed_spec) != EKPNP_OK) { std::fprintf(stderr, "ekpnp_main: --seed-*: %s\n", ekpnp_last_error(nullptr)); return 2; }
   if (modes_every && ekpnp_modes_spec_check(&P, &modes_spec) != EKPNP_OK) { std::fprintf(stderr, "ekpnp_main: --modes*: %s\n", ekpnp_last_error(nullptr)); return 2; }
+
+  if (spectrum_every && ekpnp_spectrum_spec_check(&P, &spectrum_spec) != EKPNP_OK) { std::fprintf(stderr, "ekpnp_main: --spectrum*: %s\n", ekpnp_last_error(nullptr)); return 2; }
 
   // main.cu:40-52
   std::printf("Simulating 3D electrokinetic flow with heat transfer vortices\n");
@@ -361,6 +397,7 @@ int main(int argc, char* argv[]) {
     CK(RUN(monitor_arm, &mon_spec));
   }
   if (modes_every) CK(RUN(modes_arm, &modes_spec, (int)((nsteps + modes_every - 1) / modes_every ? (nsteps + modes_every - 1) / modes_every : 1)));  // a ring that holds the whole run
+  if (spectrum_every) CK(RUN(spectrum_arm, &spectrum_spec, (int)((nsteps + spectrum_every - 1) / spectrum_every ? (nsteps + spectrum_every - 1) / spectrum_every : 1)));  // a ring that holds the whole run
   CK(RUN(synchronize));
   const auto begin = std::chrono::steady_clock::now();  // main.cu:185-186
   for (unsigned i = 0; i < nsteps; i++) {               // main.cu:189-224
@@ -368,7 +405,8 @@ int main(int argc, char* argv[]) {
       // iterations i .. j in one call, j = the next iteration something looks at the fields (or the last one)
       unsigned j = i;
       while (j + 1 < nsteps && !(j % nsave == 1 || j % print_current == 1 || (profiles_every && (j + 1) % profiles_every == 0) ||
-                                 (snap_every && (j + 1) % snap_every == 0) || (modes_every && (j + 1) % modes_every == 0))) ++j;
+                                 (snap_every && (j + 1) % snap_every == 0) || (modes_every && (j + 1) % modes_every == 0) ||
+                                 (spectrum_every && (j + 1) % spectrum_every == 0))) ++j;
       CK(RUN(step, (int)(j - i + 1)));
       for (unsigned k = i; k <= j; ++k) t = t + P.dt;  // the same additions as the loop below makes, so the files carry the same time
       i = j;
@@ -389,6 +427,7 @@ int main(int argc, char* argv[]) {
     }
     if (monitor_every && !batch && (i + 1) % monitor_every == 0) CK(RUN(monitor_record, (int64_t)(i + 1), t));  // enqueues only (--batch 1: ekpnp_step has done it)
     if (modes_every && (i + 1) % modes_every == 0) CK(RUN(modes_record, (int64_t)(i + 1), t));  // enqueues only
+    if (spectrum_every && (i + 1) % spectrum_every == 0) CK(RUN(spectrum_record, (int64_t)(i + 1), t));  // enqueues only
     if (profiles_every && (i + 1) % profiles_every == 0) CK(RUN(stats_accumulate));  // enqueues only: the loop runs on
     if (snap_every && (i + 1) % snap_every == 0) {
       char name[32];
@@ -414,6 +453,7 @@ int main(int argc, char* argv[]) {
   if (profiles_every) CK(RUN(save_profiles, (out + "/profiles.dat").c_str(), t));
   if (monitor_every) CK(RUN(monitor_save, (out + "/monitor.dat").c_str()));
   if (modes_every) CK(RUN(modes_save, (out + "/modes.dat").c_str()));
+  if (spectrum_every) CK(RUN(spectrum_save, (out + "/spectrum.dat").c_str()));
   CK(grp ? ekpnp_group_destroy(grp) : ekpnp_destroy(ctx));    // main.cu:264-290
   return 0;
 }

@@ -1693,3 +1693,103 @@ extern "C" int ekpnp_group_modes_save(ekpnp_group* g, const char* path) {
   if (int rc = ekpnp_group_modes_read(g, 0, n, steps.data(), times.data(), values.data())) return rc;
   return modes_write_file(path, S(T, 0).p, *spec, rec, dropped, n, steps.data(), times.data(), values.data(), T.err);
 }
+
+// ---- plane spectra (spectrum.hip) over the slabs: slabs are cut along z, so a plane lives on one slab; every slab handles the
+// planes it owns on its own device and the host takes each row from its owner (no exchange, nothing is added)
+static int spectrum_owner(Team& T, int z) {
+  for (size_t i = 0; i < T.m.size(); ++i)
+    if (z >= S(T, (int)i).z0 && z < S(T, (int)i).z0 + S(T, (int)i).nzl) return (int)i;
+  return -1;
+}
+extern "C" int ekpnp_group_spectrum_plane(ekpnp_group* g, int field_id, int z_global, double* power) {
+  NEEDLIVEGROUP(g);
+  if (!power) { T.err = "NULL pointer"; return EKPNP_ERR_INVALID; }
+  if (field_id < 0 || field_id >= EKPNP_NFIELDS) { T.err = "spectrum: field_id = " + std::to_string(field_id) + " outside 0 .. 10"; return EKPNP_ERR_INVALID; }
+  const int i = spectrum_owner(T, z_global);
+  if (i < 0) { T.err = "spectrum: z = " + std::to_string(z_global) + " outside 0 .. " + std::to_string(S(T, 0).p.nz - 1); return EKPNP_ERR_INVALID; }
+  if (int rc = use(T, i)) return rc;
+  TSLAB(T, i, ekpnp_spectrum_plane(T.m[i], field_id, z_global, power));
+  return EKPNP_OK;
+}
+extern "C" int ekpnp_group_spectrum(ekpnp_group* g, const ekpnp_spectrum_spec* spec, double* shells, double* peaks) {
+  NEEDLIVEGROUP(g);
+  if (!shells) { T.err = "NULL pointer"; return EKPNP_ERR_INVALID; }
+  const ekpnp_params& p = S(T, 0).p;
+  if (int rc = spectrum_check_spec(p, spec, T.err)) return rc;  // refused before any slab has launched anything
+  int nshell = 0;
+  if (int rc = spectrum_shell_count(p, &nshell, nullptr, T.err)) return rc;
+  std::vector<double> sh, pk;
+  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) {
+    const Ctx& c = m->c;
+    const int np = spec->nplanes ? spec->nplanes : c.nzl;
+    sh.resize((size_t)np * nshell);
+    pk.resize((size_t)np * 3);
+    const int rc = ekpnp_spectrum(m, spec, sh.data(), pk.data());
+    if (rc) return rc;
+    for (int j = 0; j < np; ++j) {
+      const int z = spec->nplanes ? spec->z[j] : c.z0 + j, row = spec->nplanes ? j : z;
+      if (z < c.z0 || z >= c.z0 + c.nzl) continue;  // (another slab's row)
+      std::memcpy(shells + (size_t)row * nshell, sh.data() + (size_t)j * nshell, (size_t)nshell * sizeof(double));
+      if (peaks) std::memcpy(peaks + (size_t)row * 3, pk.data() + (size_t)j * 3, 3 * sizeof(double));
+    }
+    return rc;
+  }));
+}
+extern "C" int ekpnp_group_spectrum_arm(ekpnp_group* g, const ekpnp_spectrum_spec* spec, int capacity) {
+  NEEDLIVEGROUP(g);
+  if (int rc = spectrum_check_spec(S(T, 0).p, spec, T.err)) return rc;
+  if (spec->nplanes < 1) { T.err = "spectrum: nplanes = " + std::to_string(spec->nplanes) + " (a time series needs 1 .. 16 chosen planes)"; return EKPNP_ERR_INVALID; }
+  if (capacity < 1) { T.err = "spectrum: capacity = " + std::to_string(capacity) + " (must be >= 1)"; return EKPNP_ERR_INVALID; }
+  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) { return ekpnp_spectrum_arm(m, spec, capacity); }));
+}
+extern "C" int ekpnp_group_spectrum_disarm(ekpnp_group* g) {
+  NEEDLIVEGROUP(g);
+  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) { return ekpnp_spectrum_disarm(m); }));
+}
+// enqueues only, on every slab's compute stream (as ekpnp_group_stats_accumulate)
+extern "C" int ekpnp_group_spectrum_record(ekpnp_group* g, int64_t step, double time) {
+  NEEDLIVEGROUP(g);
+  if (!spectrum_armed(S(T, 0))) { T.err = "ekpnp_spectrum_record: no spectrum tracking armed"; return EKPNP_ERR_INVALID; }  // (refused before any slab is asked: the group stays usable)
+  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) { return ekpnp_spectrum_record(m, step, time); }));
+}
+extern "C" int ekpnp_group_spectrum_count(const ekpnp_group* g, int64_t* recorded, int64_t* dropped) {
+  if (!g || g->t.m.empty()) return EKPNP_ERR_INVALID;
+  return ekpnp_spectrum_count(g->t.m[0], recorded, dropped);  // the slabs record in step
+}
+extern "C" int ekpnp_group_spectrum_read(ekpnp_group* g, int64_t first, int count, int64_t* steps, double* times, double* shells, double* peaks) {
+  NEEDLIVEGROUP(g);
+  const ekpnp_spectrum_spec* spec = spectrum_armed_spec(S(T, 0));
+  int nshell = 0;
+  if (spec)
+    if (int rc = spectrum_shell_count(S(T, 0).p, &nshell, nullptr, T.err)) return rc;
+  const size_t np = spec ? (size_t)spec->nplanes : 0, rows = (size_t)(count > 0 ? count : 0);
+  std::vector<double> sh(rows * np * nshell), pk(rows * np * 3);
+  return team_monitor_each(T, [&](ekpnp_ctx* m) {
+    const Ctx& c = m->c;
+    const int rc = ekpnp_spectrum_read(m, first, count, steps, times, sh.data(), pk.data());
+    if (rc == EKPNP_OK && count > 0)
+      for (size_t r = 0; r < rows; ++r)
+        for (size_t j = 0; j < np; ++j) {
+          if (spec->z[j] < c.z0 || spec->z[j] >= c.z0 + c.nzl) continue;  // (another slab's row)
+          std::memcpy(shells + (r * np + j) * nshell, sh.data() + (r * np + j) * nshell, (size_t)nshell * sizeof(double));
+          if (peaks) std::memcpy(peaks + (r * np + j) * 3, pk.data() + (r * np + j) * 3, 3 * sizeof(double));
+        }
+    return rc;
+  });
+}
+extern "C" int ekpnp_group_spectrum_save(ekpnp_group* g, const char* path) {
+  NEEDLIVEGROUP(g);
+  if (!path) { T.err = "NULL path"; return EKPNP_ERR_INVALID; }
+  const ekpnp_spectrum_spec* spec = spectrum_armed_spec(S(T, 0));
+  if (!spec) { T.err = "ekpnp_spectrum_save: no spectrum tracking was armed"; return EKPNP_ERR_INVALID; }
+  int nshell = 0;
+  double L = 0.0;
+  if (int rc = spectrum_shell_count(S(T, 0).p, &nshell, &L, T.err)) return rc;
+  int64_t rec = 0, dropped = 0;
+  (void)ekpnp_group_spectrum_count(g, &rec, &dropped);
+  const int n = (int)(rec - dropped);
+  std::vector<int64_t> steps((size_t)n);
+  std::vector<double> times((size_t)n), shells((size_t)n * spec->nplanes * nshell), peaks((size_t)n * spec->nplanes * 3);
+  if (int rc = ekpnp_group_spectrum_read(g, 0, n, steps.data(), times.data(), shells.data(), peaks.data())) return rc;
+  return spectrum_write_file(path, S(T, 0).p, *spec, nshell, L, rec, dropped, n, steps.data(), times.data(), shells.data(), peaks.data(), T.err);
+}

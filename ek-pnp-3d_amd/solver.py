@@ -190,6 +190,65 @@ def _modes_read(L, fn, handle, ck, nmodes: int, first: int, count: int):
     return steps, times, values
 
 
+MAX_SPECTRUM_PLANES = 16
+
+
+class SpectrumSpec(C.Structure):
+    """Mirror of `ekpnp_spectrum_spec` (include/ekpnp.h): the field and up to MAX_SPECTRUM_PLANES global z planes (0: every plane)."""
+
+    _fields_ = [("field_id", C.c_int32), ("nplanes", C.c_int32), ("z", C.c_int32 * MAX_SPECTRUM_PLANES)]
+
+
+def spectrum_spec(field="uz", planes=None) -> SpectrumSpec:
+    """field: a name or an id; planes: None (every plane of the context, synchronous calls only) or global z indices, strictly ascending"""
+    spec = SpectrumSpec()
+    spec.field_id = FIELD_ID[field] if isinstance(field, str) else int(field)
+    planes = [] if planes is None else [int(z) for z in planes]
+    spec.nplanes = len(planes)
+    for j, z in enumerate(planes[:MAX_SPECTRUM_PLANES]):
+        spec.z[j] = z
+    return spec
+
+
+def _as_spectrum_spec(field, planes) -> SpectrumSpec:
+    return field if isinstance(field, SpectrumSpec) else spectrum_spec(field, planes)
+
+
+def spectrum_spec_check(p: "Params", spec: SpectrumSpec) -> SpectrumSpec:
+    """the spec, or EkpnpError with the library's message (ekpnp_spectrum_spec_check: host arithmetic, no device)"""
+    L = load_library()
+    rc = L.ekpnp_spectrum_spec_check(C.byref(p), C.byref(spec))
+    if rc:
+        raise EkpnpError(f"ekpnp_spectrum_spec_check -> status {rc}: {L.ekpnp_last_error(None).decode()}")
+    return spec
+
+
+def spectrum_shells(p: "Params"):
+    """(shell_of[ny][nx/2 + 1], count[nshell]): the shell of every mode of rfft2's layout and the number of modes per shell - THE
+    binning of the shell spectra (ekpnp_spectrum_shells: host arithmetic, no device)"""
+    L = load_library()
+    n = C.c_int()
+    rc = L.ekpnp_spectrum_shell_count(C.byref(p), C.byref(n))
+    if rc:
+        raise EkpnpError(f"ekpnp_spectrum_shell_count -> status {rc}: {L.ekpnp_last_error(None).decode()}")
+    shell_of = np.zeros((p.ny, p.nx // 2 + 1), dtype=np.int32)
+    count = np.zeros(n.value, dtype=np.int32)
+    rc = L.ekpnp_spectrum_shells(C.byref(p), shell_of.ctypes.data_as(C.c_void_p), count.ctypes.data_as(C.c_void_p))
+    if rc:
+        raise EkpnpError(f"ekpnp_spectrum_shells -> status {rc}: {L.ekpnp_last_error(None).decode()}")
+    return shell_of, count
+
+
+def _spectrum_read(L, fn, handle, ck, nplanes: int, nshell: int, first: int, count: int):
+    steps = np.zeros(max(count, 0), dtype=np.int64)
+    times = np.zeros(max(count, 0), dtype=np.float64)
+    shells = np.zeros((max(count, 0), nplanes, nshell), dtype=np.float64)
+    peaks = np.zeros((max(count, 0), nplanes, 3), dtype=np.float64)
+    ck(fn(handle, int(first), int(count), steps.ctypes.data_as(C.c_void_p), times.ctypes.data_as(C.c_void_p), shells.ctypes.data_as(C.c_void_p),
+          peaks.ctypes.data_as(C.c_void_p)))
+    return steps, times, shells, peaks
+
+
 def _snapshot_names(spec: SnapshotSpec) -> list:
     return [n for i, n in enumerate(FIELDS) if spec.fields == 0 or (spec.fields >> i) & 1]
 
@@ -405,6 +464,26 @@ def load_library():
         "ekpnp_group_modes_count": (i32, [ctx, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
         "ekpnp_group_modes_read": (i32, [ctx, C.c_int64, i32, C.c_void_p, C.c_void_p, C.c_void_p]),
         "ekpnp_group_modes_save": (i32, [ctx, C.c_char_p]),
+        # x-y power spectra per plane: shells, peak and their time series
+        "ekpnp_spectrum_spec_check": (i32, [C.POINTER(Params), C.POINTER(SpectrumSpec)]),
+        "ekpnp_spectrum_shell_count": (i32, [C.POINTER(Params), C.POINTER(i32)]),
+        "ekpnp_spectrum_shells": (i32, [C.POINTER(Params), C.c_void_p, C.c_void_p]),
+        "ekpnp_spectrum_plane": (i32, [ctx, i32, i32, C.c_void_p]),
+        "ekpnp_spectrum": (i32, [ctx, C.POINTER(SpectrumSpec), C.c_void_p, C.c_void_p]),
+        "ekpnp_spectrum_arm": (i32, [ctx, C.POINTER(SpectrumSpec), i32]),
+        "ekpnp_spectrum_disarm": (i32, [ctx]),
+        "ekpnp_spectrum_record": (i32, [ctx, C.c_int64, dbl]),
+        "ekpnp_spectrum_count": (i32, [ctx, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+        "ekpnp_spectrum_read": (i32, [ctx, C.c_int64, i32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "ekpnp_spectrum_save": (i32, [ctx, C.c_char_p]),
+        "ekpnp_group_spectrum_plane": (i32, [ctx, i32, i32, C.c_void_p]),
+        "ekpnp_group_spectrum": (i32, [ctx, C.POINTER(SpectrumSpec), C.c_void_p, C.c_void_p]),
+        "ekpnp_group_spectrum_arm": (i32, [ctx, C.POINTER(SpectrumSpec), i32]),
+        "ekpnp_group_spectrum_disarm": (i32, [ctx]),
+        "ekpnp_group_spectrum_record": (i32, [ctx, C.c_int64, dbl]),
+        "ekpnp_group_spectrum_count": (i32, [ctx, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+        "ekpnp_group_spectrum_read": (i32, [ctx, C.c_int64, i32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "ekpnp_group_spectrum_save": (i32, [ctx, C.c_char_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError if the library does not export it
@@ -796,6 +875,63 @@ class Solver:
     def modes_save(self, path: str):
         self._ck(self._L.ekpnp_modes_save(self._h, os.fsencode(path)))
 
+    # -- x-y power spectra per plane: shells, peak and their time series (no reference counterpart) --
+    def spectrum_shells(self):
+        """(shell_of[ny][nx/2 + 1], count[nshell]) of this lattice: the library's own binning (ekpnp_spectrum_shells, host only)"""
+        return spectrum_shells(self.p)
+
+    def spectrum_plane(self, field, z: int) -> np.ndarray:
+        """P[ny][nx/2 + 1] of the global plane z in rfft2's layout: w (re^2 + im^2), w = 1 for m = 0 and the even Nyquist column, 2
+        otherwise, unnormalised (ekpnp_spectrum_plane; complete on return)"""
+        fid = FIELD_ID[field] if isinstance(field, str) else int(field)
+        out = np.zeros((self.p.ny, self.p.nx // 2 + 1), dtype=np.float64)
+        self._ck(self._L.ekpnp_spectrum_plane(self._h, fid, int(z), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def spectrum(self, field="uz", planes=None):
+        """(shells[np][nshell], peaks[np][3]): per plane the shell spectrum E(s) and the dominant mode (m, n signed, P); planes None:
+        every plane (self.nz_local), else the chosen global z (ekpnp_spectrum; complete on return).  field may be a SpectrumSpec."""
+        spec = _as_spectrum_spec(field, planes)
+        rows = spec.nplanes if spec.nplanes else self.nz_local
+        nshell = self._spectrum_nshell = getattr(self, "_spectrum_nshell", None) or len(self.spectrum_shells()[1])
+        shells = np.zeros((max(rows, 0), nshell), dtype=np.float64)
+        peaks = np.zeros((max(rows, 0), 3), dtype=np.float64)
+        self._ck(self._L.ekpnp_spectrum(self._h, C.byref(spec), shells.ctypes.data_as(C.c_void_p), peaks.ctypes.data_as(C.c_void_p)))
+        return shells, peaks
+
+    def spectrum_arm(self, field="uz", planes=(0,), capacity: int = 1024):
+        """track shells and peak of the chosen planes in a ring of `capacity` rows in device memory; rows are appended by
+        spectrum_record() only"""
+        spec = _as_spectrum_spec(field, planes)
+        self._ck(self._L.ekpnp_spectrum_arm(self._h, C.byref(spec), int(capacity)))
+        self._spectrum_np = spec.nplanes
+        self._spectrum_nshell = len(self.spectrum_shells()[1])
+
+    def spectrum_disarm(self):
+        self._ck(self._L.ekpnp_spectrum_disarm(self._h))
+
+    def spectrum_record(self, step: int, time: float):
+        """enqueue one row labelled (step, time): nothing waits, the step graph is left alone"""
+        self._ck(self._L.ekpnp_spectrum_record(self._h, int(step), float(time)))
+
+    def spectrum_count(self):
+        """(recorded, dropped); host-known, never synchronises"""
+        r, d = C.c_int64(), C.c_int64()
+        self._ck(self._L.ekpnp_spectrum_count(self._h, C.byref(r), C.byref(d)))
+        return r.value, d.value
+
+    def spectrum_read(self, first: int = 0, count: int = None):
+        """(steps[n], times[n], shells[n][nplanes][nshell], peaks[n][nplanes][3]) of the rows still held, oldest first; count None: all
+        from `first` on"""
+        if count is None:
+            r, d = self.spectrum_count()
+            count = max(r - d - first, 0)
+        return _spectrum_read(self._L, self._L.ekpnp_spectrum_read, self._h, self._ck, getattr(self, "_spectrum_np", 0),
+                              getattr(self, "_spectrum_nshell", 0), first, count)
+
+    def spectrum_save(self, path: str):
+        self._ck(self._L.ekpnp_spectrum_save(self._h, os.fsencode(path)))
+
     def tune(self, knob: str, value: int):
         self._ck(self._L.ekpnp_tune(self._h, knob.encode(), int(value)))
 
@@ -1158,6 +1294,63 @@ class Group:
 
     def modes_save(self, path: str):
         self._ck(self._L.ekpnp_group_modes_save(self._g, os.fsencode(path)))
+
+    # -- x-y power spectra per plane: shells, peak and their time series (no reference counterpart) --
+    def spectrum_shells(self):
+        """(shell_of[ny][nx/2 + 1], count[nshell]) of this lattice: the library's own binning (ekpnp_spectrum_shells, host only)"""
+        return spectrum_shells(self.p)
+
+    def spectrum_plane(self, field, z: int) -> np.ndarray:
+        """P[ny][nx/2 + 1] of the global plane z in rfft2's layout: w (re^2 + im^2), w = 1 for m = 0 and the even Nyquist column, 2
+        otherwise, unnormalised (ekpnp_group_spectrum_plane; complete on return)"""
+        fid = FIELD_ID[field] if isinstance(field, str) else int(field)
+        out = np.zeros((self.p.ny, self.p.nx // 2 + 1), dtype=np.float64)
+        self._ck(self._L.ekpnp_group_spectrum_plane(self._g, fid, int(z), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def spectrum(self, field="uz", planes=None):
+        """(shells[np][nshell], peaks[np][3]): per plane the shell spectrum E(s) and the dominant mode (m, n signed, P); planes None:
+        every plane (self.p.nz), else the chosen global z (ekpnp_group_spectrum; complete on return).  field may be a SpectrumSpec."""
+        spec = _as_spectrum_spec(field, planes)
+        rows = spec.nplanes if spec.nplanes else self.p.nz
+        nshell = self._spectrum_nshell = getattr(self, "_spectrum_nshell", None) or len(self.spectrum_shells()[1])
+        shells = np.zeros((max(rows, 0), nshell), dtype=np.float64)
+        peaks = np.zeros((max(rows, 0), 3), dtype=np.float64)
+        self._ck(self._L.ekpnp_group_spectrum(self._g, C.byref(spec), shells.ctypes.data_as(C.c_void_p), peaks.ctypes.data_as(C.c_void_p)))
+        return shells, peaks
+
+    def spectrum_arm(self, field="uz", planes=(0,), capacity: int = 1024):
+        """track shells and peak of the chosen planes in a ring of `capacity` rows in device memory; rows are appended by
+        spectrum_record() only"""
+        spec = _as_spectrum_spec(field, planes)
+        self._ck(self._L.ekpnp_group_spectrum_arm(self._g, C.byref(spec), int(capacity)))
+        self._spectrum_np = spec.nplanes
+        self._spectrum_nshell = len(self.spectrum_shells()[1])
+
+    def spectrum_disarm(self):
+        self._ck(self._L.ekpnp_group_spectrum_disarm(self._g))
+
+    def spectrum_record(self, step: int, time: float):
+        """enqueue one row labelled (step, time): nothing waits, the step graph is left alone"""
+        self._ck(self._L.ekpnp_group_spectrum_record(self._g, int(step), float(time)))
+
+    def spectrum_count(self):
+        """(recorded, dropped); host-known, never synchronises"""
+        r, d = C.c_int64(), C.c_int64()
+        self._ck(self._L.ekpnp_group_spectrum_count(self._g, C.byref(r), C.byref(d)))
+        return r.value, d.value
+
+    def spectrum_read(self, first: int = 0, count: int = None):
+        """(steps[n], times[n], shells[n][nplanes][nshell], peaks[n][nplanes][3]) of the rows still held, oldest first; count None: all
+        from `first` on"""
+        if count is None:
+            r, d = self.spectrum_count()
+            count = max(r - d - first, 0)
+        return _spectrum_read(self._L, self._L.ekpnp_group_spectrum_read, self._g, self._ck, getattr(self, "_spectrum_np", 0),
+                              getattr(self, "_spectrum_nshell", 0), first, count)
+
+    def spectrum_save(self, path: str):
+        self._ck(self._L.ekpnp_group_spectrum_save(self._g, os.fsencode(path)))
 
     def save_checkpoint(self, path: str):
         self._ck(self._L.ekpnp_group_save_checkpoint(self._g, os.fsencode(path)))

@@ -505,6 +505,70 @@ int ekpnp_modes_count(const ekpnp_ctx* ctx, int64_t* recorded, int64_t* dropped)
 int ekpnp_modes_read(ekpnp_ctx* ctx, int64_t first, int count, int64_t* steps, double* times, double* values);
 int ekpnp_modes_save(ekpnp_ctx* ctx, const char* path);
 
+/* ---- x-y power spectra per z plane: shells, peak and their time series (no reference counterpart) ----------------------
+ * The projection above answers how fast a mode the caller names grows; which wavelength the instability SELECTS - after white
+ * noise (ekpnp_seed with noise > 0), after a voltage change, when rolls give way to squares or hexagons (LBM.cu:646-661) - needs
+ * the whole spectrum.  For a plane v[ny][nx] and nxh = nx/2 + 1:
+ *   F(n, m) = sum_y sum_x v exp(-2 pi i (m x/nx + n y/ny)),  0 <= m < nxh, 0 <= n < ny            (numpy's rfft2);
+ *   n is REPORTED signed: n > ny/2 means n - ny, the range of ekpnp_modes_spec;
+ *   P(n, m) = w_m (re*re + im*im), formed as e = re*re; e = e + im*im; P = w*e, with w_m = 1 for m = 0 and for m = nx/2 when nx
+ *   is even, 2 otherwise - so that sum P = nx ny sum v^2 (Parseval over the full spectrum).  Nothing is normalised, like
+ *   ekpnp_plane_sums.
+ * Shells, all in double, every operation rounded once, no fused multiply-add: L = max(Lx, Ly), rx = L/Lx, ry = L/Ly;
+ *   a = (double)m*rx; b = (double)n_signed*ry; k2 = a*a + b*b; s = (int)floor(sqrt(k2) + 0.5); nshell = 1 + max s.
+ * Shell s holds the wavenumbers within half a fundamental of 2 pi s / L.  The table is built on the host, once per context, as
+ * a list of the modes of each shell in ascending linear index n*nxh + m (n unsigned here); ekpnp_spectrum_shells returns it and
+ * IS part of the definition: ties at .5 do occur (at 50 x 8, n*ry = 12.5 exactly) and go up, so bin with the library's table.
+ *   E(s) = sum of P over the shell's list: one workgroup of 256 threads per (plane, shell), thread t adds entries t, t + 256, ...
+ *   in ascending order, then a fixed tree over the lanes of a wavefront, then the four wavefronts in ascending order.  No
+ *   atomics: the order of the additions depends on the table alone, that is on nx, ny, Lx, Ly.
+ *   Peak: among all modes except (0, 0) whose P is positive - neither NaN nor zero - the largest P wins, among equals the
+ *   smallest linear index; the result is (m, n_signed, P) as three doubles, (0, 0, 0.0) when there is no candidate: a plane
+ *   of zeros (a plate that was never seeded) and a plane that holds a NaN have no peak.
+ * A NaN or Inf in a plane makes that plane's powers and shells NaN or Inf: nothing is filtered.
+ * One transform path: every plane is first gathered into a real staging buffer [B][ny][nx] of the feature's own and transformed
+ * by ONE hipFFT D2Z plan of batch B into its own complex buffer [B][ny][nxh] - a field array is never handed to hipFFT, the
+ * solve's buffers and plans are not touched.  B depends on nx and ny only: the planes that fit in about 64 MiB of spectrum, at
+ * least 1, at most 16; a short last batch runs the same plan with the unused slots zeroed.  The plan runs on the context's
+ * stream and follows ekpnp_set_stream.  The buffers, the plan's work area, the table and the ring are allocated on first use,
+ * counted by ekpnp_device_bytes and freed by ekpnp_destroy.  A plane's numbers are the same bits in a two-buffer, an in-place, a
+ * slab context and any group, and whichever planes are transformed beside it.
+ * The values are those ekpnp_get_field would return; for phi or E a lazy solve's arrays are brought up to date first, so
+ * TRACKING phi OR E GIVES UP THE LAZY-E SAVING AT RECORDED STEPS; "batch_moments": as for ekpnp_stats_accumulate. */
+#define EKPNP_MAX_SPECTRUM_PLANES 16
+typedef struct ekpnp_spectrum_spec {
+  int32_t field_id;                          /* any of the eleven                                   */
+  int32_t nplanes;                           /* 0: every plane of the context (synchronous call only); 1..16 chosen */
+  int32_t z[EKPNP_MAX_SPECTRUM_PLANES];      /* global plane indices, strictly ascending, 0 <= z < nz */
+} ekpnp_spectrum_spec;
+/* Host only, no device needed; a refused spec is EKPNP_ERR_INVALID with a message that names the offending number
+ * (ekpnp_last_error of NULL).  shells: shell_of is [ny][nxh], count [nshell] (may be NULL) is the number of modes per shell. */
+int ekpnp_spectrum_spec_check(const ekpnp_params* p, const ekpnp_spectrum_spec* spec);
+int ekpnp_spectrum_shell_count(const ekpnp_params* p, int* nshell);
+int ekpnp_spectrum_shells(const ekpnp_params* p, int32_t* shell_of, int32_t* count);
+/* Synchronous, nothing armed needed.  plane: P of one plane into power[ny][nxh] - the picture that tells squares from hexagons;
+ * a context that does not hold z_global answers EKPNP_ERR_INVALID.  spectrum: shells[np][nshell] and peaks[np][3] (may be
+ * NULL), np = nplanes, or nz_local when nplanes == 0, rows in ascending z; a chosen plane the context does not hold gives a row
+ * of +0.0 and the peak (0, 0, 0.0), so a host can add the ranks. */
+int ekpnp_spectrum_plane(ekpnp_ctx* ctx, int field_id, int z_global, double* power);
+int ekpnp_spectrum(ekpnp_ctx* ctx, const ekpnp_spectrum_spec* spec, double* shells, double* peaks);
+/* The time series, shaped like ekpnp_modes_*.  arm (nplanes >= 1) allocates the ring [capacity] of rows [nplanes][nshell] +
+ * [nplanes][3]; arming again resets it.  record is an explicit ENQUEUE between two ekpnp_step calls - nothing is appended from
+ * inside ekpnp_step, so the step graph, "batch_moments" and lazy E for the moment fields are left alone; the slot is host-known.
+ * When the ring is full the oldest row is overwritten (dropped counts the rows lost); count never synchronises; read
+ * synchronises and returns rows first .. first + count - 1 of those still held, oldest first (shells is
+ * [count][nplanes][nshell], peaks [count][nplanes][3] and may be NULL), a range outside what is held is EKPNP_ERR_INVALID.  An
+ * attached slab records its own rank's planes (no collective).  The ring is NOT part of checkpoint or state files.
+ * save writes text.  Line 1: "# ekpnp spectrum nx <nx> ny <ny> nz <nz> field <name> planes <z ...> nshell <S> L <%.17g> recorded <r>
+ * dropped <d>"; line 2: "# step time z peak_m peak_n peak_P E_0 ... E_<S-1>"; then one row per held sample and chosen plane:
+ * integers as %lld, the time, peak_P and the shells as %.17g, single spaces. */
+int ekpnp_spectrum_arm(ekpnp_ctx* ctx, const ekpnp_spectrum_spec* spec, int capacity);
+int ekpnp_spectrum_disarm(ekpnp_ctx* ctx);
+int ekpnp_spectrum_record(ekpnp_ctx* ctx, int64_t step, double time);                             /* enqueues only */
+int ekpnp_spectrum_count(const ekpnp_ctx* ctx, int64_t* recorded, int64_t* dropped);
+int ekpnp_spectrum_read(ekpnp_ctx* ctx, int64_t first, int count, int64_t* steps, double* times, double* shells, double* peaks);
+int ekpnp_spectrum_save(ekpnp_ctx* ctx, const char* path);
+
 /* ---- measurement hooks (bench.py; no reference counterpart) ------------------ */
 /* When enabled, every launch of the bulk collide/stream kernel is bracketed by
  * HIP events on the context's stream; the sum is returned by ..._get. */
@@ -790,6 +854,16 @@ int ekpnp_group_modes_record(ekpnp_group* g, int64_t step, double time);     /* 
 int ekpnp_group_modes_count(const ekpnp_group* g, int64_t* recorded, int64_t* dropped);
 int ekpnp_group_modes_read(ekpnp_group* g, int64_t first, int count, int64_t* steps, double* times, double* values);
 int ekpnp_group_modes_save(ekpnp_group* g, const char* path);
+/* the plane spectra above over the whole lattice: every slab handles the planes it owns on its own device, nothing is exchanged; a
+ * plane lives on one slab, so a group's rows are the owner's rows - the bits a single context gives.  nplanes == 0: np = NZ */
+int ekpnp_group_spectrum_plane(ekpnp_group* g, int field_id, int z_global, double* power);
+int ekpnp_group_spectrum(ekpnp_group* g, const ekpnp_spectrum_spec* spec, double* shells, double* peaks);
+int ekpnp_group_spectrum_arm(ekpnp_group* g, const ekpnp_spectrum_spec* spec, int capacity);
+int ekpnp_group_spectrum_disarm(ekpnp_group* g);
+int ekpnp_group_spectrum_record(ekpnp_group* g, int64_t step, double time);   /* enqueues only */
+int ekpnp_group_spectrum_count(const ekpnp_group* g, int64_t* recorded, int64_t* dropped);
+int ekpnp_group_spectrum_read(ekpnp_group* g, int64_t first, int count, int64_t* steps, double* times, double* shells, double* peaks);
+int ekpnp_group_spectrum_save(ekpnp_group* g, const char* path);
 
 #ifdef __cplusplus
 }
