@@ -255,6 +255,16 @@ int spectrum_set_stream(Ctx&);                               // ekpnp_set_stream
 void spectrum_release(Ctx&);                                 // ekpnp_destroy
 int spectrum_write_file(const char* path, const ekpnp_params& p, const ekpnp_spectrum_spec& spec, int nshell, double L, int64_t recorded, int64_t dropped,
                         int n, const int64_t* steps, const double* times, const double* shells, const double* peaks, std::string& err);
+// hist.hip: histograms and joint histograms per plane, value ranges and a time series of histograms (HistState: made by the first ekpnp_hist_planes / ekpnp_value_range / ekpnp_hist_arm)
+struct HistState;
+int hist_check_spec(const ekpnp_params& p, const ekpnp_hist_spec* s, std::string& err);
+int hist_check_range(const ekpnp_params& p, int z_lo, int z_hi, int capacity, std::string& err);  // the planes and the ring of ekpnp_hist_arm
+int hist_cells(const ekpnp_hist_spec& s);                                      // (a.n + 2) * (b.n ? b.n + 2 : 1)
+const ekpnp_hist_spec* hist_armed_spec(const Ctx&, int* z_lo, int* z_hi);      // the spec and planes of the last arm (null: never armed), for the file header
+bool hist_armed(const Ctx&);
+void hist_release(Ctx&);                                                       // ekpnp_destroy
+int hist_write_file(const char* path, const ekpnp_params& p, const ekpnp_hist_spec& spec, int z_lo, int z_hi, int64_t recorded, int64_t dropped, int n,
+                    const int64_t* steps, const double* times, const int64_t* counts, std::string& err);
 
 struct Ctx {
   ekpnp_params p{};
@@ -350,6 +360,7 @@ struct Ctx {
   ModeState* modes = nullptr;      // mode projection and its time series (modes.hip), made by the first modes call
   SeedState* seed = nullptr;       // the seed's table buffer (seed.hip), made by the first ekpnp_seed
   SpecState* spectrum = nullptr;   // plane spectra, their plan and time series (spectrum.hip), made by the first spectrum call
+  HistState* hist = nullptr;       // histograms, value ranges and their time series (hist.hip), made by the first hist call
   int collide_phase = 0;           // 0 idle, 1 boundary planes done
   // slab edge planes without pack / unpack copies (KArgs::halo_*): knob, and where the current halos are
   bool halo_direct = true;         // EKPNP_HALO_DIRECT=0: k_halo_pack / k_halo_unpack as in rounds 1-3 (the A/B partner)

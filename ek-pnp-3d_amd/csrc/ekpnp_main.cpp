@@ -75,12 +75,21 @@ int main(int argc, char* argv[]) {
   ekpnp_spectrum_spec spectrum_spec = {};
   spectrum_spec.field_id = EKPNP_UZ;
   spectrum_spec.nplanes = 0;    // 0: the mid plane (nz - 1)/2
+  unsigned hist_every = 0;      // > 0: a histogram (ekpnp_hist_*) of the planes --hist-planes names after every that many iterations, hist.dat at the end
+  ekpnp_hist_spec hist_spec = {};
+  hist_spec.a.value = EKPNP_HIST_Q;
+  hist_spec.a.n = 128;
+  hist_spec.b.value = EKPNP_UZ;
+  hist_spec.b.n = 0;            // 0: no second axis
+  bool hist_bins2_given = false, hist_axis2 = false;
+  int hist_z_lo = -1, hist_z_hi = -1;  // -1: the interior planes 1 .. nz - 2
   static const char* const field_names[EKPNP_NFIELDS] = {"rho", "c", "cn", "phi", "ux", "uy", "uz", "Ex", "Ey", "Ez", "T"};
   auto field_id_of = [&](const char* q, size_t len) {
     for (int k = 0; k < EKPNP_NFIELDS; ++k)
       if (std::strlen(field_names[k]) == len && std::strncmp(field_names[k], q, len) == 0) return k;
     return -1;
   };
+  auto value_id_of = [&](const char* q) { return std::strcmp(q, "q") == 0 ? (int)EKPNP_HIST_Q : field_id_of(q, std::strlen(q)); };
   int batch = 0;  // 1: ekpnp_step(n) from one output mark to the next instead of one stream_collide_save + fast_Poisson pair per iteration
   std::vector<std::pair<std::string, int>> tunes;  // --tune knob=value: ekpnp_tune / ekpnp_group_tune right after creation
   for (int i = 1; i < argc; ++i) {
@@ -223,6 +232,25 @@ int main(int argc, char* argv[]) {
         if (*q == ',') ++q;
       }
     }
+    else if ((v = val("--hist-every"))) hist_every = (unsigned)std::atoi(v);
+    else if ((v = val("--hist-value")) || (v = val("--hist-value2"))) {
+      const bool second = std::strcmp(argv[i - 1], "--hist-value2") == 0;
+      const int id = value_id_of(v);
+      if (id < 0) { std::fprintf(stderr, "%s wants one of rho,c,cn,phi,ux,uy,uz,Ex,Ey,Ez,T,q, got %s\n", argv[i - 1], v); return 2; }
+      (second ? hist_spec.b : hist_spec.a).value = id;
+      hist_axis2 = hist_axis2 || second;
+    }
+    else if ((v = val("--hist-bins"))) hist_spec.a.n = std::atoi(v);
+    else if ((v = val("--hist-bins2"))) { hist_spec.b.n = std::atoi(v); hist_bins2_given = hist_axis2 = true; }
+    else if ((v = val("--hist-range")) || (v = val("--hist-range2"))) {
+      const bool second = std::strcmp(argv[i - 1], "--hist-range2") == 0;
+      ekpnp_hist_axis& ax = second ? hist_spec.b : hist_spec.a;
+      if (std::sscanf(v, "%lf,%lf", &ax.lo, &ax.hi) != 2) { std::fprintf(stderr, "%s wants lo,hi, got %s\n", argv[i - 1], v); return 2; }
+      hist_axis2 = hist_axis2 || second;
+    }
+    else if ((v = val("--hist-planes"))) {
+      if (std::sscanf(v, "%d,%d", &hist_z_lo, &hist_z_hi) != 2) { std::fprintf(stderr, "--hist-planes wants zlo,zhi, got %s\n", v); return 2; }
+    }
     else if ((v = val("--tune"))) {
       const char* eq = std::strchr(v, '=');
       if (!eq || eq == v) { std::fprintf(stderr, "--tune wants knob=value, got %s\n", v); return 2; }
@@ -240,6 +268,8 @@ int main(int argc, char* argv[]) {
                    "                   [--seed-fields c,cn,...] [--seed-relative 0|1] [--seed N]]\n"
                    "                  [--modes-every N [--modes-field uz] [--modes \"m,n;m,n;...\"]]\n"
                    "                  [--spectrum-every N [--spectrum-field uz] [--spectrum-planes z,z,...]]\n"
+                   "                  [--hist-every N --hist-value q --hist-bins 128 --hist-range lo,hi\n"
+                   "                   [--hist-value2 uz --hist-bins2 64 --hist-range2 lo,hi] [--hist-planes zlo,zhi]]\n"
                    "  --seed-pattern P: after the start-up (or the restart read) a pattern with mx,my whole periods across nx and ny (default 1,1)\n"
                    "  and amplitude A (default 1e-3) plus white noise of amplitude B (default 0; reproducible from --seed N, default 1) is added to\n"
                    "  the fields --seed-fields names (default c,cn; out of rho,c,cn,ux,uy,uz,T) on the interior planes, under a sin(pi z/(nz-1))\n"
@@ -257,6 +287,13 @@ int main(int argc, char* argv[]) {
                    "  the shell spectrum E(k) and the dominant mode of each plane are appended to a ring in device memory (ekpnp_spectrum_arm /\n"
                    "  ekpnp_spectrum_record: enqueued only, nothing waits); spectrum.dat is written at the end (ekpnp_spectrum_save: one row per\n"
                    "  sample and plane, %%.17g).  With --batch 1 the batches are cut at these marks; both loops write the same bytes, and every\n"
+                   "  other file is unchanged.\n"
+                   "  --hist-every N: after every N-th iteration the histogram of --hist-value (a field or q = c - cn; default q) with --hist-bins\n"
+                   "  bins (default 128) between --hist-range lo,hi - or, with any of --hist-value2 / --hist-bins2 (default 64) / --hist-range2, its\n"
+                   "  joint histogram with that second value - summed over the planes --hist-planes zlo,zhi (global z, inclusive; default the\n"
+                   "  interior 1,nz-2) is counted on the device and appended to a ring in device memory (ekpnp_hist_arm / ekpnp_hist_record:\n"
+                   "  enqueued only, nothing waits); hist.dat is written at the end (ekpnp_hist_save: one row of integer counts per sample, under-\n"
+                   "  and overflow cells included).  With --batch 1 the batches are cut at these marks; both loops write the same bytes, and every\n"
                    "  other file is unchanged.\n"
                    "  --monitor-every N: after every N-th iteration eleven scalars - the current through either plate, the wall gradients of\n"
                    "  T, max uz, the sums of u.u, c - cn, (c - cn)^2 and uz*T, max |rho - rho0| and the number of non-finite nodes - are reduced\n"
@@ -311,6 +348,10 @@ int main(int argc, char* argv[]) {
     spectrum_spec.nplanes = 1;
     spectrum_spec.z[0] = (nz - 1) / 2;
   }
+  if (hist_every) {
+    if (hist_axis2 && !hist_bins2_given) hist_spec.b.n = 64;
+    if (hist_z_lo < 0 && hist_z_hi < 0) { hist_z_lo = nz > 2 ? 1 : 0; hist_z_hi = nz > 2 ? nz - 2 : nz - 1; }
+  }
   if (nsave == 0) nsave = nsteps / 2 ? nsteps / 2 : 1;  // LBM.h:123
   if (print_current == 0) print_current = 1;
 
@@ -329,6 +370,11 @@ int main(int argc, char* argv[]) {
   if (modes_every && ekpnp_modes_spec_check(&P, &modes_spec) != EKPNP_OK) { std::fprintf(stderr, "ekpnp_main: --modes*: %s\n", ekpnp_last_error(nullptr)); return 2; }
 
   if (spectrum_every && ekpnp_spectrum_spec_check(&P, &spectrum_spec) != EKPNP_OK) { std::fprintf(stderr, "ekpnp_main: --spectrum*: %s\n", ekpnp_last_error(nullptr)); return 2; }
+  if (hist_every && (ekpnp_hist_spec_check(&P, &hist_spec) != EKPNP_OK ||
+                     ekpnp_hist_range_check(&P, hist_z_lo, hist_z_hi, (int)((nsteps + hist_every - 1) / hist_every ? (nsteps + hist_every - 1) / hist_every : 1)) != EKPNP_OK)) {
+    std::fprintf(stderr, "ekpnp_main: --hist*: %s\n", ekpnp_last_error(nullptr));
+    return 2;
+  }
 
   // main.cu:40-52
   std::printf("Simulating 3D electrokinetic flow with heat transfer vortices\n");
@@ -398,6 +444,7 @@ int main(int argc, char* argv[]) {
   }
   if (modes_every) CK(RUN(modes_arm, &modes_spec, (int)((nsteps + modes_every - 1) / modes_every ? (nsteps + modes_every - 1) / modes_every : 1)));  // a ring that holds the whole run
   if (spectrum_every) CK(RUN(spectrum_arm, &spectrum_spec, (int)((nsteps + spectrum_every - 1) / spectrum_every ? (nsteps + spectrum_every - 1) / spectrum_every : 1)));  // a ring that holds the whole run
+  if (hist_every) CK(RUN(hist_arm, &hist_spec, hist_z_lo, hist_z_hi, (int)((nsteps + hist_every - 1) / hist_every ? (nsteps + hist_every - 1) / hist_every : 1)));  // a ring that holds the whole run
   CK(RUN(synchronize));
   const auto begin = std::chrono::steady_clock::now();  // main.cu:185-186
   for (unsigned i = 0; i < nsteps; i++) {               // main.cu:189-224
@@ -406,7 +453,7 @@ int main(int argc, char* argv[]) {
       unsigned j = i;
       while (j + 1 < nsteps && !(j % nsave == 1 || j % print_current == 1 || (profiles_every && (j + 1) % profiles_every == 0) ||
                                  (snap_every && (j + 1) % snap_every == 0) || (modes_every && (j + 1) % modes_every == 0) ||
-                                 (spectrum_every && (j + 1) % spectrum_every == 0))) ++j;
+                                 (spectrum_every && (j + 1) % spectrum_every == 0) || (hist_every && (j + 1) % hist_every == 0))) ++j;
       CK(RUN(step, (int)(j - i + 1)));
       for (unsigned k = i; k <= j; ++k) t = t + P.dt;  // the same additions as the loop below makes, so the files carry the same time
       i = j;
@@ -428,6 +475,7 @@ int main(int argc, char* argv[]) {
     if (monitor_every && !batch && (i + 1) % monitor_every == 0) CK(RUN(monitor_record, (int64_t)(i + 1), t));  // enqueues only (--batch 1: ekpnp_step has done it)
     if (modes_every && (i + 1) % modes_every == 0) CK(RUN(modes_record, (int64_t)(i + 1), t));  // enqueues only
     if (spectrum_every && (i + 1) % spectrum_every == 0) CK(RUN(spectrum_record, (int64_t)(i + 1), t));  // enqueues only
+    if (hist_every && (i + 1) % hist_every == 0) CK(RUN(hist_record, (int64_t)(i + 1), t));  // enqueues only
     if (profiles_every && (i + 1) % profiles_every == 0) CK(RUN(stats_accumulate));  // enqueues only: the loop runs on
     if (snap_every && (i + 1) % snap_every == 0) {
       char name[32];
@@ -454,6 +502,7 @@ int main(int argc, char* argv[]) {
   if (monitor_every) CK(RUN(monitor_save, (out + "/monitor.dat").c_str()));
   if (modes_every) CK(RUN(modes_save, (out + "/modes.dat").c_str()));
   if (spectrum_every) CK(RUN(spectrum_save, (out + "/spectrum.dat").c_str()));
+  if (hist_every) CK(RUN(hist_save, (out + "/hist.dat").c_str()));
   CK(grp ? ekpnp_group_destroy(grp) : ekpnp_destroy(ctx));    // main.cu:264-290
   return 0;
 }

@@ -1793,3 +1793,68 @@ extern "C" int ekpnp_group_spectrum_save(ekpnp_group* g, const char* path) {
   if (int rc = ekpnp_group_spectrum_read(g, 0, n, steps.data(), times.data(), shells.data(), peaks.data())) return rc;
   return spectrum_write_file(path, S(T, 0).p, *spec, nshell, L, rec, dropped, n, steps.data(), times.data(), shells.data(), peaks.data(), T.err);
 }
+
+// ---- histograms (hist.hip) over the slabs: slabs are cut along z, so a plane's counts live on one slab and the synchronous calls
+// write each slab's planes at its z0; every slab records the planes of the armed range it owns and the host adds the rows (integers)
+extern "C" int ekpnp_group_hist_planes(ekpnp_group* g, const ekpnp_hist_spec* spec, int64_t* counts, int64_t* nonfinite) {
+  NEEDLIVEGROUP(g);
+  if (!counts || !nonfinite) { T.err = "NULL pointer"; return EKPNP_ERR_INVALID; }
+  if (int rc = hist_check_spec(S(T, 0).p, spec, T.err)) return rc;  // refused before any slab has launched anything
+  const size_t cells = (size_t)hist_cells(*spec);
+  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) { return ekpnp_hist_planes(m, spec, counts + (size_t)m->c.z0 * cells, nonfinite + m->c.z0); }));
+}
+extern "C" int ekpnp_group_value_range(ekpnp_group* g, int value, double* vmin, double* vmax) {
+  NEEDLIVEGROUP(g);
+  if (!vmin || !vmax) { T.err = "NULL pointer"; return EKPNP_ERR_INVALID; }
+  if (value < 0 || value > EKPNP_HIST_Q) { T.err = "hist: value = " + std::to_string(value) + " outside 0 .. 11"; return EKPNP_ERR_INVALID; }
+  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) { return ekpnp_value_range(m, value, vmin + m->c.z0, vmax + m->c.z0); }));
+}
+extern "C" int ekpnp_group_hist_arm(ekpnp_group* g, const ekpnp_hist_spec* spec, int z_lo, int z_hi, int capacity) {
+  NEEDLIVEGROUP(g);
+  if (int rc = hist_check_spec(S(T, 0).p, spec, T.err)) return rc;
+  if (int rc = hist_check_range(S(T, 0).p, z_lo, z_hi, capacity, T.err)) return rc;
+  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) { return ekpnp_hist_arm(m, spec, z_lo, z_hi, capacity); }));
+}
+extern "C" int ekpnp_group_hist_disarm(ekpnp_group* g) {
+  NEEDLIVEGROUP(g);
+  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) { return ekpnp_hist_disarm(m); }));
+}
+// enqueues only, on every slab's compute stream (as ekpnp_group_stats_accumulate)
+extern "C" int ekpnp_group_hist_record(ekpnp_group* g, int64_t step, double time) {
+  NEEDLIVEGROUP(g);
+  if (!hist_armed(S(T, 0))) { T.err = "ekpnp_hist_record: no histogram armed"; return EKPNP_ERR_INVALID; }  // (refused before any slab is asked: the group stays usable)
+  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) { return ekpnp_hist_record(m, step, time); }));
+}
+extern "C" int ekpnp_group_hist_count(const ekpnp_group* g, int64_t* recorded, int64_t* dropped) {
+  if (!g || g->t.m.empty()) return EKPNP_ERR_INVALID;
+  return ekpnp_hist_count(g->t.m[0], recorded, dropped);  // the slabs record in step
+}
+extern "C" int ekpnp_group_hist_read(ekpnp_group* g, int64_t first, int count, int64_t* steps, double* times, int64_t* counts) {
+  NEEDLIVEGROUP(g);
+  const ekpnp_hist_spec* spec = hist_armed_spec(S(T, 0), nullptr, nullptr);
+  const size_t stride = spec ? (size_t)hist_cells(*spec) + 1 : 0;
+  std::vector<int64_t> v((size_t)(count > 0 ? count : 0) * stride);
+  bool head = true;
+  return team_monitor_each(T, [&](ekpnp_ctx* m) {
+    const int rc = ekpnp_hist_read(m, first, count, steps, times, v.data());
+    if (rc == EKPNP_OK && count > 0) {
+      for (size_t k = 0; k < v.size(); ++k) counts[k] = head ? v[k] : counts[k] + v[k];
+      head = false;
+    }
+    return rc;
+  });
+}
+extern "C" int ekpnp_group_hist_save(ekpnp_group* g, const char* path) {
+  NEEDLIVEGROUP(g);
+  if (!path) { T.err = "NULL path"; return EKPNP_ERR_INVALID; }
+  int z_lo = 0, z_hi = 0;
+  const ekpnp_hist_spec* spec = hist_armed_spec(S(T, 0), &z_lo, &z_hi);
+  if (!spec) { T.err = "ekpnp_hist_save: no histogram was armed"; return EKPNP_ERR_INVALID; }
+  int64_t rec = 0, dropped = 0;
+  (void)ekpnp_group_hist_count(g, &rec, &dropped);
+  const int n = (int)(rec - dropped);
+  std::vector<int64_t> steps((size_t)n), counts((size_t)n * ((size_t)hist_cells(*spec) + 1));
+  std::vector<double> times((size_t)n);
+  if (int rc = ekpnp_group_hist_read(g, 0, n, steps.data(), times.data(), counts.data())) return rc;
+  return hist_write_file(path, S(T, 0).p, *spec, z_lo, z_hi, rec, dropped, n, steps.data(), times.data(), counts.data(), T.err);
+}

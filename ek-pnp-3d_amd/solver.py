@@ -249,6 +249,92 @@ def _spectrum_read(L, fn, handle, ck, nplanes: int, nshell: int, first: int, cou
     return steps, times, shells, peaks
 
 
+HIST_Q = 11  # include/ekpnp.h: EKPNP_HIST_Q, the charge density c - cn as a histogram value
+HIST_MAX_BINS = 4096
+HIST_VALUES = FIELDS + ["q"]
+HIST_VALUE_ID = {n: i for i, n in enumerate(HIST_VALUES)}
+
+
+class HistAxis(C.Structure):
+    """Mirror of `ekpnp_hist_axis` (include/ekpnp.h): the value (a field id or HIST_Q), n bins between lo and hi."""
+
+    _fields_ = [("value", C.c_int32), ("n", C.c_int32), ("lo", C.c_double), ("hi", C.c_double)]
+
+
+class HistSpec(C.Structure):
+    """Mirror of `ekpnp_hist_spec` (include/ekpnp.h): axis a and an optional axis b (b.n == 0: a 1-D histogram)."""
+
+    _fields_ = [("a", HistAxis), ("b", HistAxis)]
+
+    @property
+    def cells(self) -> int:
+        return (self.a.n + 2) * (self.b.n + 2 if self.b.n else 1)
+
+    @property
+    def cell_shape(self) -> tuple:
+        return (self.a.n + 2, self.b.n + 2) if self.b.n else (self.a.n + 2,)
+
+
+def _hist_axis(axis) -> HistAxis:
+    if isinstance(axis, HistAxis):
+        return axis
+    value, n, lo, hi = axis
+    return HistAxis(HIST_VALUE_ID[value] if isinstance(value, str) else int(value), int(n), float(lo), float(hi))
+
+
+def hist_spec(a, b=None) -> HistSpec:
+    """axes as (value name or id, n, lo, hi); value: a field or "q" (c - cn); b None: a 1-D histogram"""
+    spec = HistSpec()
+    spec.a = _hist_axis(a)
+    if b is not None:
+        spec.b = _hist_axis(b)
+    return spec
+
+
+def _as_hist_spec(a, b=None) -> HistSpec:
+    return a if isinstance(a, HistSpec) else hist_spec(a, b)
+
+
+def hist_spec_check(p: "Params", spec: HistSpec, planes=None, capacity: int = 1) -> HistSpec:
+    """the spec, or EkpnpError with the library's message (ekpnp_hist_spec_check and, when planes = (z_lo, z_hi) is given, the ring's
+    ekpnp_hist_range_check: host arithmetic, no device)"""
+    L = load_library()
+    rc = L.ekpnp_hist_spec_check(C.byref(p), C.byref(spec))
+    if rc:
+        raise EkpnpError(f"ekpnp_hist_spec_check -> status {rc}: {L.ekpnp_last_error(None).decode()}")
+    if planes is not None:
+        rc = L.ekpnp_hist_range_check(C.byref(p), int(planes[0]), int(planes[1]), int(capacity))
+        if rc:
+            raise EkpnpError(f"ekpnp_hist_range_check -> status {rc}: {L.ekpnp_last_error(None).decode()}")
+    return spec
+
+
+def hist_bin(lo: float, hi: float, n: int, v):
+    """THE index of v on the axis (lo, hi, n): -1 NaN, 0 below lo, n + 1 at or above hi, else 1 + min(int((v - lo) * (n / (hi - lo))), n - 1)
+    (ekpnp_hist_bin, host only; -2 for an axis the spec check refuses).  A scalar gives an int, an array an int32 array."""
+    fn = load_library().ekpnp_hist_bin
+    if np.ndim(v) == 0:
+        return int(fn(float(lo), float(hi), int(n), float(v)))
+    a = np.asarray(v, dtype=np.float64)
+    return np.fromiter((fn(float(lo), float(hi), int(n), float(x)) for x in a.ravel()), dtype=np.int32, count=a.size).reshape(a.shape)
+
+
+def hist_edges(axis) -> np.ndarray:
+    """the n + 1 edges lo + k (hi - lo) / n of an axis, FOR PLOTTING ONLY: hist_bin is the definition of a bin"""
+    ax = _hist_axis(axis)
+    return ax.lo + np.arange(ax.n + 1, dtype=np.float64) * (ax.hi - ax.lo) / ax.n
+
+
+def _hist_read(L, fn, handle, ck, spec, first: int, count: int):
+    cells = spec.cells if spec is not None else 0
+    steps = np.zeros(max(count, 0), dtype=np.int64)
+    times = np.zeros(max(count, 0), dtype=np.float64)
+    rows = np.zeros((max(count, 0), cells + 1), dtype=np.int64)
+    ck(fn(handle, int(first), int(count), steps.ctypes.data_as(C.c_void_p), times.ctypes.data_as(C.c_void_p), rows.ctypes.data_as(C.c_void_p)))
+    shape = spec.cell_shape if spec is not None else (0,)
+    return steps, times, rows[:, :cells].reshape((len(steps),) + shape).copy(), rows[:, cells].copy()
+
+
 def _snapshot_names(spec: SnapshotSpec) -> list:
     return [n for i, n in enumerate(FIELDS) if spec.fields == 0 or (spec.fields >> i) & 1]
 
@@ -484,6 +570,26 @@ def load_library():
         "ekpnp_group_spectrum_count": (i32, [ctx, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
         "ekpnp_group_spectrum_read": (i32, [ctx, C.c_int64, i32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
         "ekpnp_group_spectrum_save": (i32, [ctx, C.c_char_p]),
+        # histograms, value ranges and their time series
+        "ekpnp_hist_bin": (i32, [dbl, dbl, i32, dbl]),
+        "ekpnp_hist_spec_check": (i32, [C.POINTER(Params), C.POINTER(HistSpec)]),
+        "ekpnp_hist_range_check": (i32, [C.POINTER(Params), i32, i32, i32]),
+        "ekpnp_hist_planes": (i32, [ctx, C.POINTER(HistSpec), C.c_void_p, C.c_void_p]),
+        "ekpnp_value_range": (i32, [ctx, i32, C.c_void_p, C.c_void_p]),
+        "ekpnp_hist_arm": (i32, [ctx, C.POINTER(HistSpec), i32, i32, i32]),
+        "ekpnp_hist_disarm": (i32, [ctx]),
+        "ekpnp_hist_record": (i32, [ctx, C.c_int64, dbl]),
+        "ekpnp_hist_count": (i32, [ctx, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+        "ekpnp_hist_read": (i32, [ctx, C.c_int64, i32, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "ekpnp_hist_save": (i32, [ctx, C.c_char_p]),
+        "ekpnp_group_hist_planes": (i32, [ctx, C.POINTER(HistSpec), C.c_void_p, C.c_void_p]),
+        "ekpnp_group_value_range": (i32, [ctx, i32, C.c_void_p, C.c_void_p]),
+        "ekpnp_group_hist_arm": (i32, [ctx, C.POINTER(HistSpec), i32, i32, i32]),
+        "ekpnp_group_hist_disarm": (i32, [ctx]),
+        "ekpnp_group_hist_record": (i32, [ctx, C.c_int64, dbl]),
+        "ekpnp_group_hist_count": (i32, [ctx, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+        "ekpnp_group_hist_read": (i32, [ctx, C.c_int64, i32, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "ekpnp_group_hist_save": (i32, [ctx, C.c_char_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError if the library does not export it
@@ -932,6 +1038,55 @@ class Solver:
     def spectrum_save(self, path: str):
         self._ck(self._L.ekpnp_spectrum_save(self._h, os.fsencode(path)))
 
+    # ---- histograms, value ranges and their time series (hist.hip) ----
+    def hist_planes(self, a, b=None):
+        """(counts[nz_local, a.n + 2(, b.n + 2)] int64, nonfinite[nz_local] int64) of every owned plane: cell 0 is the underflow, n + 1 the overflow,
+        a node with a NaN in either value goes to nonfinite and to no cell (ekpnp_hist_planes; complete on return).  a may be a HistSpec."""
+        spec = _as_hist_spec(a, b)
+        counts = np.zeros((self.nz_local,) + spec.cell_shape, dtype=np.int64)
+        nonfinite = np.zeros(self.nz_local, dtype=np.int64)
+        self._ck(self._L.ekpnp_hist_planes(self._h, C.byref(spec), counts.ctypes.data_as(C.c_void_p), nonfinite.ctypes.data_as(C.c_void_p)))
+        return counts, nonfinite
+
+    def value_range(self, value):
+        """(vmin[nz_local], vmax[nz_local]): per owned plane the smallest and largest value that is not NaN (+Inf, -Inf for a plane of NaNs);
+        value: a field or "q" (ekpnp_value_range; complete on return)"""
+        vid = HIST_VALUE_ID[value] if isinstance(value, str) else int(value)
+        vmin, vmax = np.zeros(self.nz_local, dtype=np.float64), np.zeros(self.nz_local, dtype=np.float64)
+        self._ck(self._L.ekpnp_value_range(self._h, vid, vmin.ctypes.data_as(C.c_void_p), vmax.ctypes.data_as(C.c_void_p)))
+        return vmin, vmax
+
+    def hist_arm(self, a, b=None, planes=None, capacity: int = 1024):
+        """allocate the ring; a row is ONE histogram summed over the global planes planes = (z_lo, z_hi) inclusive (None: the interior
+        1 .. nz - 2); from then on rows are appended by hist_record() only"""
+        spec = _as_hist_spec(a, b)
+        z_lo, z_hi = (1, self.p.nz - 2) if planes is None else (int(planes[0]), int(planes[1]))
+        self._ck(self._L.ekpnp_hist_arm(self._h, C.byref(spec), z_lo, z_hi, int(capacity)))
+        self._hist_spec = spec
+
+    def hist_disarm(self):
+        self._ck(self._L.ekpnp_hist_disarm(self._h))
+
+    def hist_record(self, step: int, time: float):
+        """append a row labelled (step, time) (enqueues only)"""
+        self._ck(self._L.ekpnp_hist_record(self._h, int(step), float(time)))
+
+    def hist_count(self):
+        """(rows recorded since the arm, rows dropped because the ring was full); never synchronises"""
+        r, d = C.c_int64(), C.c_int64()
+        self._ck(self._L.ekpnp_hist_count(self._h, C.byref(r), C.byref(d)))
+        return r.value, d.value
+
+    def hist_read(self, first: int = 0, count: int = None):
+        """(steps, times, counts[count, a.n + 2(, b.n + 2)], nonfinite[count]) of the rows still held, oldest first"""
+        if count is None:
+            r, d = self.hist_count()
+            count = max(r - d - first, 0)
+        return _hist_read(self._L, self._L.ekpnp_hist_read, self._h, self._ck, getattr(self, "_hist_spec", None), first, count)
+
+    def hist_save(self, path: str):
+        self._ck(self._L.ekpnp_hist_save(self._h, os.fsencode(path)))
+
     def tune(self, knob: str, value: int):
         self._ck(self._L.ekpnp_tune(self._h, knob.encode(), int(value)))
 
@@ -1351,6 +1506,55 @@ class Group:
 
     def spectrum_save(self, path: str):
         self._ck(self._L.ekpnp_group_spectrum_save(self._g, os.fsencode(path)))
+
+    # ---- histograms, value ranges and their time series (hist.hip) ----
+    def hist_planes(self, a, b=None):
+        """(counts[nz, a.n + 2(, b.n + 2)] int64, nonfinite[nz] int64) of every plane of the lattice: cell 0 is the underflow, n + 1 the overflow,
+        a node with a NaN in either value goes to nonfinite and to no cell (ekpnp_group_hist_planes; complete on return).  a may be a HistSpec."""
+        spec = _as_hist_spec(a, b)
+        counts = np.zeros((self.p.nz,) + spec.cell_shape, dtype=np.int64)
+        nonfinite = np.zeros(self.p.nz, dtype=np.int64)
+        self._ck(self._L.ekpnp_group_hist_planes(self._g, C.byref(spec), counts.ctypes.data_as(C.c_void_p), nonfinite.ctypes.data_as(C.c_void_p)))
+        return counts, nonfinite
+
+    def value_range(self, value):
+        """(vmin[nz], vmax[nz]): per plane of the lattice the smallest and largest value that is not NaN (+Inf, -Inf for a plane of NaNs);
+        value: a field or "q" (ekpnp_group_value_range; complete on return)"""
+        vid = HIST_VALUE_ID[value] if isinstance(value, str) else int(value)
+        vmin, vmax = np.zeros(self.p.nz, dtype=np.float64), np.zeros(self.p.nz, dtype=np.float64)
+        self._ck(self._L.ekpnp_group_value_range(self._g, vid, vmin.ctypes.data_as(C.c_void_p), vmax.ctypes.data_as(C.c_void_p)))
+        return vmin, vmax
+
+    def hist_arm(self, a, b=None, planes=None, capacity: int = 1024):
+        """allocate the ring; a row is ONE histogram summed over the global planes planes = (z_lo, z_hi) inclusive (None: the interior
+        1 .. nz - 2); from then on rows are appended by hist_record() only"""
+        spec = _as_hist_spec(a, b)
+        z_lo, z_hi = (1, self.p.nz - 2) if planes is None else (int(planes[0]), int(planes[1]))
+        self._ck(self._L.ekpnp_group_hist_arm(self._g, C.byref(spec), z_lo, z_hi, int(capacity)))
+        self._hist_spec = spec
+
+    def hist_disarm(self):
+        self._ck(self._L.ekpnp_group_hist_disarm(self._g))
+
+    def hist_record(self, step: int, time: float):
+        """append a row labelled (step, time) (enqueues only)"""
+        self._ck(self._L.ekpnp_group_hist_record(self._g, int(step), float(time)))
+
+    def hist_count(self):
+        """(rows recorded since the arm, rows dropped because the ring was full); never synchronises"""
+        r, d = C.c_int64(), C.c_int64()
+        self._ck(self._L.ekpnp_group_hist_count(self._g, C.byref(r), C.byref(d)))
+        return r.value, d.value
+
+    def hist_read(self, first: int = 0, count: int = None):
+        """(steps, times, counts[count, a.n + 2(, b.n + 2)], nonfinite[count]) of the rows still held, oldest first"""
+        if count is None:
+            r, d = self.hist_count()
+            count = max(r - d - first, 0)
+        return _hist_read(self._L, self._L.ekpnp_group_hist_read, self._g, self._ck, getattr(self, "_hist_spec", None), first, count)
+
+    def hist_save(self, path: str):
+        self._ck(self._L.ekpnp_group_hist_save(self._g, os.fsencode(path)))
 
     def save_checkpoint(self, path: str):
         self._ck(self._L.ekpnp_group_save_checkpoint(self._g, os.fsencode(path)))

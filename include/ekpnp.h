@@ -569,6 +569,68 @@ int ekpnp_spectrum_count(const ekpnp_ctx* ctx, int64_t* recorded, int64_t* dropp
 int ekpnp_spectrum_read(ekpnp_ctx* ctx, int64_t first, int count, int64_t* steps, double* times, double* shells, double* peaks);
 int ekpnp_spectrum_save(ekpnp_ctx* ctx, const char* path);
 
+/* ---- histograms and joint histograms of the fields per z plane, value ranges and a time series (no reference counterpart) ----
+ * What none of the reductions above returns is a distribution: the PDF of q = c - cn or of uz on a plane or over the volume,
+ * whether its tails are Gaussian, how uz and T are jointly distributed (quadrant analysis of the flux of which the profiles give
+ * one number, uz_T), the range a field spans on each plane.
+ * Values: a field id 0 .. 10, or EKPNP_HIST_Q = 11, the charge density c - cn (one FP64 subtraction per node).
+ * An axis is {value, n, lo, hi} with n >= 1, lo and hi finite, hi > lo, and hi - lo and scale = (double)n / (hi - lo) finite.
+ * THE INDEX of a value v on an axis - this function IS the definition, bin edges exist for plotting only; every operation is
+ * rounded once, no fused multiply-add, host (ekpnp_hist_bin) and device share one function, scale is formed once per axis:
+ *   -1      if v != v (NaN);
+ *   0       if v < lo          (underflow; -Inf lands here);
+ *   n + 1   if v >= hi         (overflow; +Inf lands here);
+ *   1 + min((int)((v - lo) * scale), n - 1)   otherwise.
+ * A spec holds an axis a and an optional axis b (b.n == 0: a 1-D histogram).  cells = (a.n + 2) * (b.n ? b.n + 2 : 1), laid out
+ * counts[ia][ib] with ib fastest; a.n * max(b.n, 1) <= EKPNP_HIST_MAX_BINS.  A node at which either value is NaN is counted in a
+ * separate counter, nonfinite, and in no cell: for every plane sum(cells) + nonfinite == nx * ny.  Counts are int64_t.
+ * Counts are integers: they do not depend on the order of the additions, so a plane's counts are the same in a two-buffer, an
+ * in-place, a slab context and any group.  The pass reads only the arrays the spec names (8 B per node for a field, 16 B for q,
+ * at most 32 B); workgroups count in LDS with integer atomics and store partial counts that a small kernel adds - no float
+ * atomic anywhere.  The values are those ekpnp_get_field would return; for phi or E a lazy solve's arrays are brought up to date
+ * first, so A HISTOGRAM OF phi OR E GIVES UP THE LAZY-E SAVING AT RECORDED STEPS; "batch_moments": as for
+ * ekpnp_stats_accumulate.  The scratch (partial counts, plane counts) and the ring are allocated on first use, counted by
+ * ekpnp_device_bytes and freed by ekpnp_destroy. */
+#define EKPNP_HIST_Q 11
+#define EKPNP_HIST_MAX_BINS 4096
+typedef struct ekpnp_hist_axis {
+  int32_t value;                    /* a field id 0 .. 10, or EKPNP_HIST_Q */
+  int32_t n;                        /* bins between lo and hi, >= 1 (axis b: 0 = no second axis) */
+  double  lo, hi;                   /* finite, hi > lo */
+} ekpnp_hist_axis;
+typedef struct ekpnp_hist_spec {
+  ekpnp_hist_axis a, b;
+} ekpnp_hist_spec;
+/* Host only, no device needed.  bin: the index above (-2 for an axis the spec check would refuse).  spec_check and range_check
+ * (the planes and the ring of ekpnp_hist_arm: 0 <= z_lo <= z_hi < nz, capacity >= 1): a refusal is EKPNP_ERR_INVALID with a
+ * message that names the offending number (ekpnp_last_error of NULL). */
+int ekpnp_hist_bin(double lo, double hi, int n, double v);
+int ekpnp_hist_spec_check(const ekpnp_params* p, const ekpnp_hist_spec* spec);
+int ekpnp_hist_range_check(const ekpnp_params* p, int z_lo, int z_hi, int capacity);
+/* Synchronous, complete on return, nothing armed needed.  hist_planes: counts[nz_local][cells] and nonfinite[nz_local] of every
+ * owned plane.  value_range: per owned plane the smallest and the largest value that is not NaN, to choose lo and hi from
+ * (+-Inf count as values; a plane of NaNs only gives +Inf / -Inf; a zero may come back with either sign). */
+int ekpnp_hist_planes(ekpnp_ctx* ctx, const ekpnp_hist_spec* spec, int64_t* counts, int64_t* nonfinite);
+int ekpnp_value_range(ekpnp_ctx* ctx, int value, double* vmin, double* vmax);
+/* The time series, shaped like ekpnp_modes_*.  A row is ONE histogram: the sum over the global planes z_lo .. z_hi inclusive
+ * (1 .. nz-2: the interior volume; z, z: one plane), cells + 1 int64 values, the last being nonfinite.  arm allocates the ring
+ * [capacity][cells + 1]; arming again resets it.  record is an explicit ENQUEUE between two ekpnp_step calls - nothing is
+ * appended from inside ekpnp_step, so the step graph, "batch_moments" and lazy E for the moment fields are left alone; the slot
+ * is host-known.  When the ring is full the oldest row is overwritten (dropped counts the rows lost); count never synchronises;
+ * read synchronises and returns rows first .. first + count - 1 of those still held, oldest first (counts is
+ * [count][cells + 1]), a range outside what is held is EKPNP_ERR_INVALID.  A slab or attached slab counts the planes of the range
+ * it owns (no collective); when it owns none its rows are zeros and no kernel reads a field.  The ring is NOT part of checkpoint
+ * or state files.  save writes text.  Line 1: "# ekpnp hist nx <nx> ny <ny> nz <nz> a <name> <n> <lo> <hi> [b <name> <n> <lo>
+ * <hi>] z_lo <z> z_hi <z> recorded <r> dropped <d>" (names: the fields' and q; lo, hi as %.17g; the b group only for a joint
+ * histogram); then one row per held sample: "step time nonfinite cell cell ..." - the label and the counts as %lld, the time as
+ * %.17g, the cells in the order counts[ia][ib], single spaces. */
+int ekpnp_hist_arm(ekpnp_ctx* ctx, const ekpnp_hist_spec* spec, int z_lo, int z_hi, int capacity);
+int ekpnp_hist_disarm(ekpnp_ctx* ctx);
+int ekpnp_hist_record(ekpnp_ctx* ctx, int64_t step, double time);                                 /* enqueues only */
+int ekpnp_hist_count(const ekpnp_ctx* ctx, int64_t* recorded, int64_t* dropped);
+int ekpnp_hist_read(ekpnp_ctx* ctx, int64_t first, int count, int64_t* steps, double* times, int64_t* counts);
+int ekpnp_hist_save(ekpnp_ctx* ctx, const char* path);
+
 /* ---- measurement hooks (bench.py; no reference counterpart) ------------------ */
 /* When enabled, every launch of the bulk collide/stream kernel is bracketed by
  * HIP events on the context's stream; the sum is returned by ..._get. */
@@ -864,6 +926,17 @@ int ekpnp_group_spectrum_record(ekpnp_group* g, int64_t step, double time);   /*
 int ekpnp_group_spectrum_count(const ekpnp_group* g, int64_t* recorded, int64_t* dropped);
 int ekpnp_group_spectrum_read(ekpnp_group* g, int64_t first, int count, int64_t* steps, double* times, double* shells, double* peaks);
 int ekpnp_group_spectrum_save(ekpnp_group* g, const char* path);
+/* the histograms above over the whole lattice: slabs are cut along z, so hist_planes and value_range write the whole lattice's
+ * planes in z order (counts[NZ][cells], nonfinite[NZ], vmin[NZ], vmax[NZ]); every slab records the planes of the armed range it
+ * owns and read / save add the slabs' rows on the host - integers, so the sum is exact */
+int ekpnp_group_hist_planes(ekpnp_group* g, const ekpnp_hist_spec* spec, int64_t* counts, int64_t* nonfinite);
+int ekpnp_group_value_range(ekpnp_group* g, int value, double* vmin, double* vmax);
+int ekpnp_group_hist_arm(ekpnp_group* g, const ekpnp_hist_spec* spec, int z_lo, int z_hi, int capacity);
+int ekpnp_group_hist_disarm(ekpnp_group* g);
+int ekpnp_group_hist_record(ekpnp_group* g, int64_t step, double time);       /* enqueues only */
+int ekpnp_group_hist_count(const ekpnp_group* g, int64_t* recorded, int64_t* dropped);
+int ekpnp_group_hist_read(ekpnp_group* g, int64_t first, int count, int64_t* steps, double* times, int64_t* counts);
+int ekpnp_group_hist_save(ekpnp_group* g, const char* path);
 
 #ifdef __cplusplus
 }
