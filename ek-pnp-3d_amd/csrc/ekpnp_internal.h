@@ -265,6 +265,20 @@ bool hist_armed(const Ctx&);
 void hist_release(Ctx&);                                                       // ekpnp_destroy
 int hist_write_file(const char* path, const ekpnp_params& p, const ekpnp_hist_spec& spec, int z_lo, int z_hi, int64_t recorded, int64_t dropped, int n,
                     const int64_t* steps, const double* times, const int64_t* counts, std::string& err);
+// section.hip: a value summed along one horizontal axis per plane, and its time series (SectionState: made by the first ekpnp_section / ekpnp_section_save / ekpnp_section_arm)
+struct SectionState;
+int section_check_spec(const ekpnp_params& p, const ekpnp_section_spec* s, std::string& err);
+int section_check_ring(const ekpnp_section_spec& s, int capacity, std::string& err);  // ekpnp_section_arm: nplanes >= 1, capacity >= 1
+int section_nvalues(const ekpnp_section_spec& s);
+int section_nkeep(const ekpnp_params& p, const ekpnp_section_spec& s);
+const ekpnp_section_spec* section_armed_spec(const Ctx&);  // the spec of the last arm (null: never armed), for the file header
+bool section_armed(const Ctx&);
+void section_release(Ctx&);                                // ekpnp_destroy
+// values is [nvalues][np][nkeep], z the global index of each of the np planes
+int section_write_file(const char* path, const ekpnp_params& p, const ekpnp_section_spec& spec, int np, const int* z, double time, const double* values,
+                       std::string& err);
+int section_write_ring_file(const char* path, const ekpnp_params& p, const ekpnp_section_spec& spec, int64_t recorded, int64_t dropped, int n,
+                            const int64_t* steps, const double* times, const double* values, std::string& err);
 
 struct Ctx {
   ekpnp_params p{};
@@ -361,6 +375,7 @@ struct Ctx {
   SeedState* seed = nullptr;       // the seed's table buffer (seed.hip), made by the first ekpnp_seed
   SpecState* spectrum = nullptr;   // plane spectra, their plan and time series (spectrum.hip), made by the first spectrum call
   HistState* hist = nullptr;       // histograms, value ranges and their time series (hist.hip), made by the first hist call
+  SectionState* section = nullptr; // sections and their time series (section.hip), made by the first section call
   int collide_phase = 0;           // 0 idle, 1 boundary planes done
   // slab edge planes without pack / unpack copies (KArgs::halo_*): knob, and where the current halos are
   bool halo_direct = true;         // EKPNP_HALO_DIRECT=0: k_halo_pack / k_halo_unpack as in rounds 1-3 (the A/B partner)

@@ -83,6 +83,12 @@ int main(int argc, char* argv[]) {
   hist_spec.b.n = 0;            // 0: no second axis
   bool hist_bins2_given = false, hist_axis2 = false;
   int hist_z_lo = -1, hist_z_hi = -1;  // -1: the interior planes 1 .. nz - 2
+  unsigned section_every = 0;       // > 0: a section (ekpnp_section_arm / _record) of the planes --section-planes names after every that many iterations, section.dat at the end
+  unsigned section_full_every = 0;  // > 0: a section of EVERY plane (ekpnp_section_save) after every that many iterations, section_<step>.dat each time
+  ekpnp_section_spec section_spec = {};
+  section_spec.values = (1u << EKPNP_SECTION_Q) | (1u << EKPNP_UZ);
+  section_spec.across = EKPNP_ACROSS_Y;
+  section_spec.lo = section_spec.hi = -1;  // -1: the whole axis
   static const char* const field_names[EKPNP_NFIELDS] = {"rho", "c", "cn", "phi", "ux", "uy", "uz", "Ex", "Ey", "Ez", "T"};
   auto field_id_of = [&](const char* q, size_t len) {
     for (int k = 0; k < EKPNP_NFIELDS; ++k)
@@ -251,6 +257,40 @@ int main(int argc, char* argv[]) {
     else if ((v = val("--hist-planes"))) {
       if (std::sscanf(v, "%d,%d", &hist_z_lo, &hist_z_hi) != 2) { std::fprintf(stderr, "--hist-planes wants zlo,zhi, got %s\n", v); return 2; }
     }
+    else if ((v = val("--section-every"))) section_every = (unsigned)std::atoi(v);
+    else if ((v = val("--section-full-every"))) section_full_every = (unsigned)std::atoi(v);
+    else if ((v = val("--section-values"))) {
+      section_spec.values = 0u;
+      for (const char* q = v; *q;) {
+        const char* e = q;
+        while (*e && *e != ',') ++e;
+        const int id = (e - q == 1 && *q == 'q') ? (int)EKPNP_SECTION_Q : field_id_of(q, (size_t)(e - q));
+        if (id < 0) { std::fprintf(stderr, "--section-values wants names out of rho,c,cn,phi,ux,uy,uz,Ex,Ey,Ez,T,q, got %.*s in %s\n", (int)(e - q), q, v); return 2; }
+        section_spec.values |= 1u << id;
+        q = *e ? e + 1 : e;
+      }
+    }
+    else if ((v = val("--section-across"))) {
+      if (!std::strcmp(v, "x")) section_spec.across = EKPNP_ACROSS_X;
+      else if (!std::strcmp(v, "y")) section_spec.across = EKPNP_ACROSS_Y;
+      else { std::fprintf(stderr, "--section-across wants x or y, got %s\n", v); return 2; }
+    }
+    else if ((v = val("--section-range"))) {
+      if (std::sscanf(v, "%d,%d", &section_spec.lo, &section_spec.hi) != 2) { std::fprintf(stderr, "--section-range wants lo,hi, got %s\n", v); return 2; }
+    }
+    else if ((v = val("--section-planes"))) {
+      section_spec.nplanes = 0;
+      for (const char* q = v; *q;) {
+        int z = 0, used = 0;
+        if (std::sscanf(q, "%d%n", &z, &used) != 1 || section_spec.nplanes >= EKPNP_MAX_SECTION_PLANES || (q[used] && q[used] != ',')) {
+          std::fprintf(stderr, "--section-planes wants at most %d plane indices \"z,z,...\", got %s\n", EKPNP_MAX_SECTION_PLANES, v);
+          return 2;
+        }
+        section_spec.z[section_spec.nplanes++] = z;
+        q += used;
+        if (*q == ',') ++q;
+      }
+    }
     else if ((v = val("--tune"))) {
       const char* eq = std::strchr(v, '=');
       if (!eq || eq == v) { std::fprintf(stderr, "--tune wants knob=value, got %s\n", v); return 2; }
@@ -270,6 +310,8 @@ int main(int argc, char* argv[]) {
                    "                  [--spectrum-every N [--spectrum-field uz] [--spectrum-planes z,z,...]]\n"
                    "                  [--hist-every N --hist-value q --hist-bins 128 --hist-range lo,hi\n"
                    "                   [--hist-value2 uz --hist-bins2 64 --hist-range2 lo,hi] [--hist-planes zlo,zhi]]\n"
+                   "                  [--section-every N | --section-full-every N  [--section-values q,uz] [--section-across y]\n"
+                   "                   [--section-range lo,hi] [--section-planes z,z,...]]\n"
                    "  --seed-pattern P: after the start-up (or the restart read) a pattern with mx,my whole periods across nx and ny (default 1,1)\n"
                    "  and amplitude A (default 1e-3) plus white noise of amplitude B (default 0; reproducible from --seed N, default 1) is added to\n"
                    "  the fields --seed-fields names (default c,cn; out of rho,c,cn,ux,uy,uz,T) on the interior planes, under a sin(pi z/(nz-1))\n"
@@ -288,6 +330,14 @@ int main(int argc, char* argv[]) {
                    "  ekpnp_spectrum_record: enqueued only, nothing waits); spectrum.dat is written at the end (ekpnp_spectrum_save: one row per\n"
                    "  sample and plane, %%.17g).  With --batch 1 the batches are cut at these marks; both loops write the same bytes, and every\n"
                    "  other file is unchanged.\n"
+                   "  --section-every N: after every N-th iteration the --section-values (names out of the fields and q = c - cn; default q,uz)\n"
+                   "  summed along --section-across (x keeps y, y keeps x; default y) over the index range --section-range lo,hi (inclusive;\n"
+                   "  default the whole axis, lo = hi: a cut) on the planes --section-planes (global z, ascending, at most 16; default the mid\n"
+                   "  plane) are appended to a ring in device memory (ekpnp_section_arm / ekpnp_section_record: enqueued only, nothing waits);\n"
+                   "  section.dat is written at the end (ekpnp_section_ring_save: one row per sample, value and plane).  --section-full-every N:\n"
+                   "  the same values, axis and range on EVERY plane, written at once to section_<step>.dat (ekpnp_section_save; --section-planes\n"
+                   "  does not apply).  With --batch 1 the batches are cut at these marks; both loops write the same bytes, and every other file\n"
+                   "  is unchanged.\n"
                    "  --hist-every N: after every N-th iteration the histogram of --hist-value (a field or q = c - cn; default q) with --hist-bins\n"
                    "  bins (default 128) between --hist-range lo,hi - or, with any of --hist-value2 / --hist-bins2 (default 64) / --hist-range2, its\n"
                    "  joint histogram with that second value - summed over the planes --hist-planes zlo,zhi (global z, inclusive; default the\n"
@@ -352,6 +402,16 @@ int main(int argc, char* argv[]) {
     if (hist_axis2 && !hist_bins2_given) hist_spec.b.n = 64;
     if (hist_z_lo < 0 && hist_z_hi < 0) { hist_z_lo = nz > 2 ? 1 : 0; hist_z_hi = nz > 2 ? nz - 2 : nz - 1; }
   }
+  ekpnp_section_spec section_full_spec = section_spec;
+  if (section_every || section_full_every) {
+    if (section_spec.lo < 0 && section_spec.hi < 0) { section_spec.lo = 0; section_spec.hi = (section_spec.across == EKPNP_ACROSS_X ? nx : ny) - 1; }
+    section_full_spec = section_spec;
+    section_full_spec.nplanes = 0;
+    if (section_spec.nplanes == 0) {
+      section_spec.nplanes = 1;
+      section_spec.z[0] = (nz - 1) / 2;
+    }
+  }
   if (nsave == 0) nsave = nsteps / 2 ? nsteps / 2 : 1;  // LBM.h:123
   if (print_current == 0) print_current = 1;
 
@@ -373,6 +433,10 @@ int main(int argc, char* argv[]) {
   if (hist_every && (ekpnp_hist_spec_check(&P, &hist_spec) != EKPNP_OK ||
                      ekpnp_hist_range_check(&P, hist_z_lo, hist_z_hi, (int)((nsteps + hist_every - 1) / hist_every ? (nsteps + hist_every - 1) / hist_every : 1)) != EKPNP_OK)) {
     std::fprintf(stderr, "ekpnp_main: --hist*: %s\n", ekpnp_last_error(nullptr));
+    return 2;
+  }
+  if ((section_every && ekpnp_section_spec_check(&P, &section_spec) != EKPNP_OK) || (section_full_every && ekpnp_section_spec_check(&P, &section_full_spec) != EKPNP_OK)) {
+    std::fprintf(stderr, "ekpnp_main: --section*: %s\n", ekpnp_last_error(nullptr));
     return 2;
   }
 
@@ -445,6 +509,7 @@ int main(int argc, char* argv[]) {
   if (modes_every) CK(RUN(modes_arm, &modes_spec, (int)((nsteps + modes_every - 1) / modes_every ? (nsteps + modes_every - 1) / modes_every : 1)));  // a ring that holds the whole run
   if (spectrum_every) CK(RUN(spectrum_arm, &spectrum_spec, (int)((nsteps + spectrum_every - 1) / spectrum_every ? (nsteps + spectrum_every - 1) / spectrum_every : 1)));  // a ring that holds the whole run
   if (hist_every) CK(RUN(hist_arm, &hist_spec, hist_z_lo, hist_z_hi, (int)((nsteps + hist_every - 1) / hist_every ? (nsteps + hist_every - 1) / hist_every : 1)));  // a ring that holds the whole run
+  if (section_every) CK(RUN(section_arm, &section_spec, (int)((nsteps + section_every - 1) / section_every ? (nsteps + section_every - 1) / section_every : 1)));  // a ring that holds the whole run
   CK(RUN(synchronize));
   const auto begin = std::chrono::steady_clock::now();  // main.cu:185-186
   for (unsigned i = 0; i < nsteps; i++) {               // main.cu:189-224
@@ -453,7 +518,8 @@ int main(int argc, char* argv[]) {
       unsigned j = i;
       while (j + 1 < nsteps && !(j % nsave == 1 || j % print_current == 1 || (profiles_every && (j + 1) % profiles_every == 0) ||
                                  (snap_every && (j + 1) % snap_every == 0) || (modes_every && (j + 1) % modes_every == 0) ||
-                                 (spectrum_every && (j + 1) % spectrum_every == 0) || (hist_every && (j + 1) % hist_every == 0))) ++j;
+                                 (spectrum_every && (j + 1) % spectrum_every == 0) || (hist_every && (j + 1) % hist_every == 0) ||
+                                 (section_every && (j + 1) % section_every == 0) || (section_full_every && (j + 1) % section_full_every == 0))) ++j;
       CK(RUN(step, (int)(j - i + 1)));
       for (unsigned k = i; k <= j; ++k) t = t + P.dt;  // the same additions as the loop below makes, so the files carry the same time
       i = j;
@@ -476,6 +542,12 @@ int main(int argc, char* argv[]) {
     if (modes_every && (i + 1) % modes_every == 0) CK(RUN(modes_record, (int64_t)(i + 1), t));  // enqueues only
     if (spectrum_every && (i + 1) % spectrum_every == 0) CK(RUN(spectrum_record, (int64_t)(i + 1), t));  // enqueues only
     if (hist_every && (i + 1) % hist_every == 0) CK(RUN(hist_record, (int64_t)(i + 1), t));  // enqueues only
+    if (section_every && (i + 1) % section_every == 0) CK(RUN(section_record, (int64_t)(i + 1), t));  // enqueues only
+    if (section_full_every && (i + 1) % section_full_every == 0) {
+      char name[40];
+      std::snprintf(name, sizeof name, "/section_%07u.dat", i + 1);
+      CK(RUN(section_save, &section_full_spec, (out + name).c_str(), t));  // waits for this one map: [values][nz][nkeep] doubles
+    }
     if (profiles_every && (i + 1) % profiles_every == 0) CK(RUN(stats_accumulate));  // enqueues only: the loop runs on
     if (snap_every && (i + 1) % snap_every == 0) {
       char name[32];
@@ -503,6 +575,7 @@ int main(int argc, char* argv[]) {
   if (modes_every) CK(RUN(modes_save, (out + "/modes.dat").c_str()));
   if (spectrum_every) CK(RUN(spectrum_save, (out + "/spectrum.dat").c_str()));
   if (hist_every) CK(RUN(hist_save, (out + "/hist.dat").c_str()));
+  if (section_every) CK(RUN(section_ring_save, (out + "/section.dat").c_str()));
   CK(grp ? ekpnp_group_destroy(grp) : ekpnp_destroy(ctx));    // main.cu:264-290
   return 0;
 }

@@ -1858,3 +1858,90 @@ extern "C" int ekpnp_group_hist_save(ekpnp_group* g, const char* path) {
   if (int rc = ekpnp_group_hist_read(g, 0, n, steps.data(), times.data(), counts.data())) return rc;
   return hist_write_file(path, S(T, 0).p, *spec, z_lo, z_hi, rec, dropped, n, steps.data(), times.data(), counts.data(), T.err);
 }
+
+// ---- sections (section.hip) over the slabs: slabs are cut along z, so a plane's rows live on one slab; every slab reduces the
+// planes it owns on its own device and the host places the owner's rows (nothing is exchanged, nothing is added)
+static void section_place(const Ctx& c, const ekpnp_section_spec& spec, int nz, size_t samples, const double* part, double* whole) {
+  const size_t nv = (size_t)section_nvalues(spec), nkeep = (size_t)section_nkeep(c.p, spec);
+  const size_t np_part = spec.nplanes ? (size_t)spec.nplanes : (size_t)c.nzl, np_whole = spec.nplanes ? (size_t)spec.nplanes : (size_t)nz;
+  for (size_t r = 0; r < samples; ++r)
+    for (size_t v = 0; v < nv; ++v)
+      for (size_t j = 0; j < np_part; ++j) {
+        const int z = spec.nplanes ? spec.z[j] : c.z0 + (int)j;
+        if (z < c.z0 || z >= c.z0 + c.nzl) continue;  // (another slab's row)
+        const size_t row = spec.nplanes ? j : (size_t)z;
+        std::memcpy(whole + ((r * nv + v) * np_whole + row) * nkeep, part + ((r * nv + v) * np_part + j) * nkeep, nkeep * sizeof(double));
+      }
+}
+extern "C" int ekpnp_group_section(ekpnp_group* g, const ekpnp_section_spec* spec, double* host_out) {
+  NEEDLIVEGROUP(g);
+  if (!host_out) { T.err = "NULL pointer"; return EKPNP_ERR_INVALID; }
+  const ekpnp_params& p = S(T, 0).p;
+  if (int rc = section_check_spec(p, spec, T.err)) return rc;  // refused before any slab has launched anything
+  std::vector<double> part;
+  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) {
+    const Ctx& c = m->c;
+    part.resize((size_t)section_nvalues(*spec) * (size_t)(spec->nplanes ? spec->nplanes : c.nzl) * (size_t)section_nkeep(p, *spec));
+    const int rc = ekpnp_section(m, spec, part.data());
+    if (rc == EKPNP_OK) section_place(c, *spec, p.nz, 1, part.data(), host_out);
+    return rc;
+  }));
+}
+extern "C" int ekpnp_group_section_save(ekpnp_group* g, const ekpnp_section_spec* spec, const char* path, double time) {
+  NEEDLIVEGROUP(g);
+  if (!path) { T.err = "NULL path"; return EKPNP_ERR_INVALID; }
+  const ekpnp_params& p = S(T, 0).p;
+  if (int rc = section_check_spec(p, spec, T.err)) return rc;
+  const int np = spec->nplanes ? spec->nplanes : p.nz;
+  std::vector<double> v((size_t)section_nvalues(*spec) * (size_t)np * (size_t)section_nkeep(p, *spec));
+  if (int rc = ekpnp_group_section(g, spec, v.data())) return rc;
+  std::vector<int> z((size_t)np);
+  for (int j = 0; j < np; ++j) z[(size_t)j] = spec->nplanes ? spec->z[j] : j;
+  return section_write_file(path, p, *spec, np, z.data(), time, v.data(), T.err);
+}
+extern "C" int ekpnp_group_section_arm(ekpnp_group* g, const ekpnp_section_spec* spec, int capacity) {
+  NEEDLIVEGROUP(g);
+  if (int rc = section_check_spec(S(T, 0).p, spec, T.err)) return rc;
+  if (int rc = section_check_ring(*spec, capacity, T.err)) return rc;
+  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) { return ekpnp_section_arm(m, spec, capacity); }));
+}
+extern "C" int ekpnp_group_section_disarm(ekpnp_group* g) {
+  NEEDLIVEGROUP(g);
+  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) { return ekpnp_section_disarm(m); }));
+}
+// enqueues only, on every slab's compute stream (as ekpnp_group_stats_accumulate)
+extern "C" int ekpnp_group_section_record(ekpnp_group* g, int64_t step, double time) {
+  NEEDLIVEGROUP(g);
+  if (!section_armed(S(T, 0))) { T.err = "ekpnp_section_record: no section armed"; return EKPNP_ERR_INVALID; }  // (refused before any slab is asked: the group stays usable)
+  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) { return ekpnp_section_record(m, step, time); }));
+}
+extern "C" int ekpnp_group_section_count(const ekpnp_group* g, int64_t* recorded, int64_t* dropped) {
+  if (!g || g->t.m.empty()) return EKPNP_ERR_INVALID;
+  return ekpnp_section_count(g->t.m[0], recorded, dropped);  // the slabs record in step
+}
+extern "C" int ekpnp_group_section_read(ekpnp_group* g, int64_t first, int count, int64_t* steps, double* times, double* values) {
+  NEEDLIVEGROUP(g);
+  const ekpnp_section_spec* spec = section_armed_spec(S(T, 0));
+  const size_t rows = (size_t)(count > 0 ? count : 0);
+  const size_t row = spec ? (size_t)section_nvalues(*spec) * (size_t)spec->nplanes * (size_t)section_nkeep(S(T, 0).p, *spec) : 0;
+  if (rows && !values) { T.err = "NULL pointer"; return EKPNP_ERR_INVALID; }
+  std::vector<double> part(rows * row);
+  return team_monitor_each(T, [&](ekpnp_ctx* m) {
+    const int rc = ekpnp_section_read(m, first, count, steps, times, part.data());
+    if (rc == EKPNP_OK && count > 0) section_place(m->c, *spec, S(T, 0).p.nz, rows, part.data(), values);
+    return rc;
+  });
+}
+extern "C" int ekpnp_group_section_ring_save(ekpnp_group* g, const char* path) {
+  NEEDLIVEGROUP(g);
+  if (!path) { T.err = "NULL path"; return EKPNP_ERR_INVALID; }
+  const ekpnp_section_spec* spec = section_armed_spec(S(T, 0));
+  if (!spec) { T.err = "ekpnp_section_ring_save: no section was armed"; return EKPNP_ERR_INVALID; }
+  int64_t rec = 0, dropped = 0;
+  (void)ekpnp_group_section_count(g, &rec, &dropped);
+  const int n = (int)(rec - dropped);
+  std::vector<int64_t> steps((size_t)n);
+  std::vector<double> times((size_t)n), values((size_t)n * section_nvalues(*spec) * spec->nplanes * section_nkeep(S(T, 0).p, *spec));
+  if (int rc = ekpnp_group_section_read(g, 0, n, steps.data(), times.data(), values.data())) return rc;
+  return section_write_ring_file(path, S(T, 0).p, *spec, rec, dropped, n, steps.data(), times.data(), values.data(), T.err);
+}

@@ -335,6 +335,164 @@ def _hist_read(L, fn, handle, ck, spec, first: int, count: int):
     return steps, times, rows[:, :cells].reshape((len(steps),) + shape).copy(), rows[:, cells].copy()
 
 
+SECTION_Q = 11  # include/ekpnp.h: EKPNP_SECTION_Q, the charge density c - cn as a section value
+ACROSS_X, ACROSS_Y = 0, 1  # EKPNP_ACROSS_X (keeps y), EKPNP_ACROSS_Y (keeps x)
+MAX_SECTION_PLANES = 16
+SECTION_VALUES = FIELDS + ["q"]
+SECTION_VALUE_ID = {n: i for i, n in enumerate(SECTION_VALUES)}
+
+
+class SectionSpec(C.Structure):
+    """Mirror of `ekpnp_section_spec` (include/ekpnp.h): a bit mask of values (0: all twelve), the removed axis, its inclusive index
+    range, and up to MAX_SECTION_PLANES global z planes (0: every plane of the context, synchronous calls only)."""
+
+    _fields_ = [("values", C.c_uint32), ("across", C.c_int32), ("lo", C.c_int32), ("hi", C.c_int32), ("nplanes", C.c_int32),
+                ("z", C.c_int32 * MAX_SECTION_PLANES)]
+
+    @property
+    def names(self) -> list:
+        return [n for i, n in enumerate(SECTION_VALUES) if self.values == 0 or (self.values >> i) & 1]
+
+
+def section_spec(values=None, across="x", range=None, planes=None, n=None) -> SectionSpec:
+    """values: None (all twelve), a bit mask, or names / ids out of SECTION_VALUES; across: "x" / 0 (keeps y) or "y" / 1 (keeps x);
+    range: (lo, hi) inclusive along the removed axis (None: 0 .. n - 1 with n the axis length, which must then be given);
+    planes: None (every plane of the context) or global z indices, strictly ascending"""
+    spec = SectionSpec()
+    if values is None:
+        spec.values = 0
+    elif isinstance(values, (int, np.integer)):
+        spec.values = int(values)
+    else:
+        mask = 0
+        for v in ([values] if isinstance(values, str) else values):
+            mask |= 1 << (SECTION_VALUE_ID[v] if isinstance(v, str) else int(v))
+        spec.values = mask
+    spec.across = {"x": ACROSS_X, "y": ACROSS_Y}[across] if isinstance(across, str) else int(across)
+    if range is None:
+        if n is None:
+            raise ValueError("section_spec: range=None needs the axis length n")
+        range = (0, int(n) - 1)
+    spec.lo, spec.hi = int(range[0]), int(range[1])
+    planes = [] if planes is None else [int(z) for z in planes]
+    spec.nplanes = len(planes)
+    for j, z in enumerate(planes[:MAX_SECTION_PLANES]):
+        spec.z[j] = z
+    return spec
+
+
+def section_spec_check(p: "Params", spec: SectionSpec) -> SectionSpec:
+    """the spec, or EkpnpError with the library's message (ekpnp_section_spec_check: host arithmetic, no device)"""
+    L = load_library()
+    rc = L.ekpnp_section_spec_check(C.byref(p), C.byref(spec))
+    if rc:
+        raise EkpnpError(f"ekpnp_section_spec_check -> status {rc}: {L.ekpnp_last_error(None).decode()}")
+    return spec
+
+
+def section_extent(p: "Params", spec: SectionSpec):
+    """(nvalues, nkeep) of a section (ekpnp_section_extent: host arithmetic, no device)"""
+    L = load_library()
+    nv, nk = C.c_int(), C.c_int()
+    rc = L.ekpnp_section_extent(C.byref(p), C.byref(spec), C.byref(nv), C.byref(nk))
+    if rc:
+        raise EkpnpError(f"ekpnp_section_extent -> status {rc}: {L.ekpnp_last_error(None).decode()}")
+    return nv.value, nk.value
+
+
+def section_sum(v, stride: int = 1, n: int = None) -> float:
+    """THE sum of a line: the terms v[i * stride], i < n, added in runs of 64 consecutive indices, each run in ascending i, the run
+    sums in ascending run (ekpnp_section_sum, host only).  n None: as many terms as v holds at that stride."""
+    a = np.ascontiguousarray(v, dtype=np.float64).ravel()
+    stride = int(stride)
+    if n is None:
+        n = (a.size + stride - 1) // stride
+    if n < 1 or stride < 1 or (int(n) - 1) * stride >= a.size:
+        raise ValueError(f"section_sum: n = {n}, stride = {stride} do not fit {a.size} values")
+    return float(load_library().ekpnp_section_sum(a.ctypes.data_as(C.c_void_p), stride, int(n)))
+
+
+def _section_spec_for(p: "Params", values, across, range, planes) -> SectionSpec:
+    if isinstance(values, SectionSpec):
+        return values
+    a = {"x": ACROSS_X, "y": ACROSS_Y}[across] if isinstance(across, str) else int(across)
+    return section_spec(values, a, range, planes, n=p.nx if a == ACROSS_X else p.ny)
+
+
+def _section_read(fn, handle, ck, spec, nkeep: int, first: int, count: int):
+    nv, npl = (len(spec.names), spec.nplanes) if spec is not None else (0, 0)
+    steps = np.zeros(max(count, 0), dtype=np.int64)
+    times = np.zeros(max(count, 0), dtype=np.float64)
+    values = np.zeros((max(count, 0), nv, npl, nkeep), dtype=np.float64)
+    ck(fn(handle, int(first), int(count), steps.ctypes.data_as(C.c_void_p), times.ctypes.data_as(C.c_void_p), values.ctypes.data_as(C.c_void_p)))
+    return steps, times, values
+
+
+class _Sections:
+    """The section methods of Solver and Group (section.hip): the same calls on a context (ekpnp_section*) and on a group
+    (ekpnp_group_section*), whose rows are the owning slab's."""
+
+    def _section_fn(self, verb: str):
+        group = hasattr(self, "_g")
+        return getattr(self._L, ("ekpnp_group_section" if group else "ekpnp_section") + verb), (self._g if group else self._h)
+
+    def section(self, values=None, across="x", range=None, planes=None):
+        """[nvalues, np, nkeep] float64: every selected value (None: all twelve of SECTION_VALUES, in that order) summed along the axis
+        `across` ("x" keeps y, "y" keeps x) over the inclusive index range (None: the whole axis; lo == hi: a cut), per plane - np = the
+        chosen global planes, or every plane held when planes is None.  Unnormalised; every entry is section_sum of its line
+        (ekpnp_section; complete on return).  values may be a SectionSpec."""
+        spec = _section_spec_for(self.p, values, across, range, planes)
+        rows = spec.nplanes if spec.nplanes else (self.p.nz if hasattr(self, "_g") else self.nz_local)
+        out = np.zeros((len(spec.names), max(rows, 0), self.p.ny if spec.across == ACROSS_X else self.p.nx), dtype=np.float64)
+        fn, h = self._section_fn("")
+        self._ck(fn(h, C.byref(spec), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def section_write(self, path: str, values=None, across="x", range=None, planes=None, time: float = 0.0):
+        """the same map as text: a header line, then one row "name z v ..." per value and plane (ekpnp_section_save)"""
+        spec = _section_spec_for(self.p, values, across, range, planes)
+        fn, h = self._section_fn("_save")
+        self._ck(fn(h, C.byref(spec), os.fsencode(path), float(time)))
+
+    def section_arm(self, values=None, across="x", range=None, planes=(0,), capacity: int = 1024):
+        """allocate the ring of rows [nvalues, nplanes, nkeep] for 1 .. 16 chosen planes; rows are appended by section_record() only"""
+        spec = _section_spec_for(self.p, values, across, range, planes)
+        fn, h = self._section_fn("_arm")
+        self._ck(fn(h, C.byref(spec), int(capacity)))
+        self._section_spec = spec
+
+    def section_disarm(self):
+        fn, h = self._section_fn("_disarm")
+        self._ck(fn(h))
+
+    def section_record(self, step: int, time: float):
+        """append a row labelled (step, time) (enqueues only)"""
+        fn, h = self._section_fn("_record")
+        self._ck(fn(h, int(step), float(time)))
+
+    def section_count(self):
+        """(rows recorded since the arm, rows dropped because the ring was full); never synchronises"""
+        r, d = C.c_int64(), C.c_int64()
+        fn, h = self._section_fn("_count")
+        self._ck(fn(h, C.byref(r), C.byref(d)))
+        return r.value, d.value
+
+    def section_read(self, first: int = 0, count: int = None):
+        """(steps, times, values[count, nvalues, nplanes, nkeep]) of the rows still held, oldest first"""
+        if count is None:
+            r, d = self.section_count()
+            count = max(r - d - first, 0)
+        spec = getattr(self, "_section_spec", None)
+        nkeep = 0 if spec is None else (self.p.ny if spec.across == ACROSS_X else self.p.nx)
+        fn, h = self._section_fn("_read")
+        return _section_read(fn, h, self._ck, spec, nkeep, first, count)
+
+    def section_save(self, path: str):
+        """the ring as text: a header line, then one row "step time name z v ..." per held sample, value and plane (ekpnp_section_ring_save)"""
+        fn, h = self._section_fn("_ring_save")
+        self._ck(fn(h, os.fsencode(path)))
+
+
 def _snapshot_names(spec: SnapshotSpec) -> list:
     return [n for i, n in enumerate(FIELDS) if spec.fields == 0 or (spec.fields >> i) & 1]
 
@@ -590,6 +748,26 @@ def load_library():
         "ekpnp_group_hist_count": (i32, [ctx, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
         "ekpnp_group_hist_read": (i32, [ctx, C.c_int64, i32, C.c_void_p, C.c_void_p, C.c_void_p]),
         "ekpnp_group_hist_save": (i32, [ctx, C.c_char_p]),
+        # sections and their time series
+        "ekpnp_section_sum": (dbl, [C.c_void_p, C.c_ssize_t, i32]),
+        "ekpnp_section_spec_check": (i32, [C.POINTER(Params), C.POINTER(SectionSpec)]),
+        "ekpnp_section_extent": (i32, [C.POINTER(Params), C.POINTER(SectionSpec), C.POINTER(i32), C.POINTER(i32)]),
+        "ekpnp_section": (i32, [ctx, C.POINTER(SectionSpec), C.c_void_p]),
+        "ekpnp_section_save": (i32, [ctx, C.POINTER(SectionSpec), C.c_char_p, dbl]),
+        "ekpnp_section_arm": (i32, [ctx, C.POINTER(SectionSpec), i32]),
+        "ekpnp_section_disarm": (i32, [ctx]),
+        "ekpnp_section_record": (i32, [ctx, C.c_int64, dbl]),
+        "ekpnp_section_count": (i32, [ctx, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+        "ekpnp_section_read": (i32, [ctx, C.c_int64, i32, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "ekpnp_section_ring_save": (i32, [ctx, C.c_char_p]),
+        "ekpnp_group_section": (i32, [ctx, C.POINTER(SectionSpec), C.c_void_p]),
+        "ekpnp_group_section_save": (i32, [ctx, C.POINTER(SectionSpec), C.c_char_p, dbl]),
+        "ekpnp_group_section_arm": (i32, [ctx, C.POINTER(SectionSpec), i32]),
+        "ekpnp_group_section_disarm": (i32, [ctx]),
+        "ekpnp_group_section_record": (i32, [ctx, C.c_int64, dbl]),
+        "ekpnp_group_section_count": (i32, [ctx, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+        "ekpnp_group_section_read": (i32, [ctx, C.c_int64, i32, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "ekpnp_group_section_ring_save": (i32, [ctx, C.c_char_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError if the library does not export it
@@ -672,7 +850,7 @@ def comm_timing(L, handle, check) -> dict:
     return out
 
 
-class Solver:
+class Solver(_Sections):
     """One EK-PNP simulation on the current HIP device (or one z slab of it)."""
 
     def __init__(self, params: Params, rank: int = 0, nranks: int = 1, slab: bool = False):
@@ -1164,7 +1342,7 @@ class Solver:
         return comm_timing(self._L, self._h, self._ck)
 
 
-class Group:
+class Group(_Sections):
     """nslabs z slabs driven by ONE process (ekpnp_group_*): slab i on HIP device devices[i]
     (default: i modulo the device count; devices may repeat, then the halos move by device copies).
     Same method names as Solver; fields are whole-lattice arrays [NZ][NY][NX]."""

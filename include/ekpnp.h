@@ -631,6 +631,70 @@ int ekpnp_hist_count(const ekpnp_ctx* ctx, int64_t* recorded, int64_t* dropped);
 int ekpnp_hist_read(ekpnp_ctx* ctx, int64_t first, int count, int64_t* steps, double* times, int64_t* counts);
 int ekpnp_hist_save(ekpnp_ctx* ctx, const char* path);
 
+/* ---- vertical sections and space-time lines: a value summed along ONE horizontal axis, per z plane (no reference counterpart) ----
+ * Every reduction above removes both horizontal axes, and a snapshot is a coarsened FP32 volume.  A section keeps one: the
+ * charge density q = c - cn, uz and phi over (x, z) at one y or summed along the roll axis - the picture of the vortices and of
+ * the depleted layer under them; and one horizontal line of a plane against time - rolls drifting, merging and splitting.
+ * Values: a bit mask over the ids 0 .. 11; 0 .. 10 are the field ids, EKPNP_SECTION_Q = 11 is c - cn (one FP64 subtraction per
+ * node before any addition); 0 means all twelve.  Selected values appear in ascending id order; their names are rho c cn phi
+ * ux uy uz Ex Ey Ez T q.
+ * Axes: `across` is the horizontal axis that is removed, lo .. hi an inclusive index range along it.  EKPNP_ACROSS_X = 0 keeps
+ * y: the map is [z][ny], 0 <= lo <= hi < nx.  EKPNP_ACROSS_Y = 1 keeps x: the map is [z][nx], 0 <= lo <= hi < ny.  lo == hi is a
+ * cut; a wider range is a SUM, unnormalised like ekpnp_plane_sums (the mean is the sum divided by hi - lo + 1).
+ * Planes: nplanes == 0 means every plane the context owns (synchronous calls only); 1 .. 16 chosen planes are global indices,
+ * strictly ascending, 0 <= z < nz.  A chosen plane that a slab does not own gives a row of +0.0.
+ * THE ORDER OF THE ADDITIONS - ekpnp_section_sum IS the definition, every map entry of every entry point below is this function
+ * applied to its line, and the device leaves exactly these bits: the terms t_i = v[i * stride], i = 0 .. n - 1 (n >= 1), are cut
+ * into runs of 64 consecutive indices starting at i = 0 (the last run may be short).  Within run j: r_j = t_{64 j}, then
+ * r_j = r_j + t_i for the rest of the run in ascending i.  Across runs: S = r_0, then S = S + r_j in ascending j.  Plain FP64
+ * additions: no fused multiply-add, no tree, no padding with zeros.  So a cut returns the field's own bits (-0.0 included), a NaN
+ * or Inf propagates into its own line and nowhere else, and a number depends on the field values alone - not on the launch
+ * shape, the buffer mode, the decomposition, or which planes or values are selected beside it.
+ * The pass reads only the chosen planes and only the indices lo .. hi of the arrays the mask names (c and cn once for c, cn and
+ * q together).  The values are those ekpnp_get_field would return; when phi, Ex, Ey or Ez is selected a lazy solve's arrays are
+ * brought up to date first, so A SECTION OF phi OR E GIVES UP THE LAZY-E SAVING AT RECORDED STEPS (otherwise lazy E is left
+ * alone); "batch_moments": as for ekpnp_stats_accumulate.  The output buffer and the ring are allocated on first use, counted by
+ * ekpnp_device_bytes and freed by ekpnp_destroy. */
+#define EKPNP_SECTION_Q 11
+#define EKPNP_ACROSS_X 0
+#define EKPNP_ACROSS_Y 1
+#define EKPNP_MAX_SECTION_PLANES 16
+typedef struct ekpnp_section_spec {
+  uint32_t values;                           /* bit i: value id i (0 .. 11); 0: all twelve          */
+  int32_t  across, lo, hi, nplanes;          /* the removed axis, its inclusive range; 0: every owned plane (synchronous only), 1..16 chosen */
+  int32_t  z[EKPNP_MAX_SECTION_PLANES];      /* global plane indices, strictly ascending, 0 <= z < nz */
+} ekpnp_section_spec;
+/* Host only, no device needed.  sum: the definition above.  spec_check and extent (nvalues = the number of selected values,
+ * nkeep = ny across x, nx across y): a refusal is EKPNP_ERR_INVALID with a message that names the offending number
+ * (ekpnp_last_error of NULL) - a bit above 11, across outside 0 .. 1, lo or hi out of range or lo > hi, nplanes outside
+ * 0 .. 16, a z out of range or not ascending. */
+double ekpnp_section_sum(const double* v, ptrdiff_t stride, int n);
+int ekpnp_section_spec_check(const ekpnp_params* p, const ekpnp_section_spec* spec);
+int ekpnp_section_extent(const ekpnp_params* p, const ekpnp_section_spec* spec, int* nvalues, int* nkeep);
+/* Synchronous, complete on return, nothing armed needed.  section: host_out is [nvalues][np][nkeep], np = nplanes, or nz_local
+ * when nplanes == 0, planes in ascending z.  section_save writes that map as text.  Line 1: "# ekpnp section nx <nx> ny <ny> nz
+ * <nz> across <x|y> lo <lo> hi <hi> values <names...> nkeep <n> time <%.17g>"; then one row per value and plane: "name z v_0 ...
+ * v_<nkeep-1>" (z global, the values as %.17g, single spaces). */
+int ekpnp_section(ekpnp_ctx* ctx, const ekpnp_section_spec* spec, double* host_out);
+int ekpnp_section_save(ekpnp_ctx* ctx, const ekpnp_section_spec* spec, const char* path, double time);
+/* The time series, shaped like ekpnp_hist_*.  arm (nplanes >= 1, capacity >= 1) allocates the ring [capacity] of rows
+ * [nvalues][nplanes][nkeep]; arming again resets it.  record is an explicit ENQUEUE between two ekpnp_step calls and never
+ * waits - nothing is appended from inside ekpnp_step, so the step graph, "batch_moments" and lazy E for the moment fields are
+ * left alone; the slot is host-known.  When the ring is full the oldest row is overwritten (dropped counts the rows lost); count
+ * never synchronises; read synchronises and returns rows first .. first + count - 1 of those still held, oldest first (values
+ * is [count][nvalues][nplanes][nkeep]), a range outside what is held is EKPNP_ERR_INVALID.  A slab or attached slab records the
+ * chosen planes it owns (no collective); when it owns none its rows are +0.0 and no kernel reads a field.  The ring is NOT part
+ * of checkpoint or state files.  ring_save writes text (the ring's file cannot share the name of the synchronous one: C has no
+ * overloads).  Line 1: as ekpnp_section_save, but with "planes <z ...> recorded <r> dropped <d>" in place of "time <t>"; then one
+ * row per held sample, value and plane: "step time name z v_0 ... v_<nkeep-1>" (the step as %lld, the time and the values as
+ * %.17g, single spaces). */
+int ekpnp_section_arm(ekpnp_ctx* ctx, const ekpnp_section_spec* spec, int capacity);
+int ekpnp_section_disarm(ekpnp_ctx* ctx);
+int ekpnp_section_record(ekpnp_ctx* ctx, int64_t step, double time);                              /* enqueues only */
+int ekpnp_section_count(const ekpnp_ctx* ctx, int64_t* recorded, int64_t* dropped);
+int ekpnp_section_read(ekpnp_ctx* ctx, int64_t first, int count, int64_t* steps, double* times, double* values);
+int ekpnp_section_ring_save(ekpnp_ctx* ctx, const char* path);
+
 /* ---- measurement hooks (bench.py; no reference counterpart) ------------------ */
 /* When enabled, every launch of the bulk collide/stream kernel is bracketed by
  * HIP events on the context's stream; the sum is returned by ..._get. */
@@ -937,6 +1001,17 @@ int ekpnp_group_hist_record(ekpnp_group* g, int64_t step, double time);       /*
 int ekpnp_group_hist_count(const ekpnp_group* g, int64_t* recorded, int64_t* dropped);
 int ekpnp_group_hist_read(ekpnp_group* g, int64_t first, int count, int64_t* steps, double* times, int64_t* counts);
 int ekpnp_group_hist_save(ekpnp_group* g, const char* path);
+/* the sections above over the whole lattice: slabs are cut along z, so a plane lives on one slab and a group's rows are the
+ * owner's rows - the bits a single context gives; every slab handles the planes it owns on its own device and nothing is
+ * exchanged.  For the group np = NZ when nplanes == 0; the files are those of a single context. */
+int ekpnp_group_section(ekpnp_group* g, const ekpnp_section_spec* spec, double* host_out);
+int ekpnp_group_section_save(ekpnp_group* g, const ekpnp_section_spec* spec, const char* path, double time);
+int ekpnp_group_section_arm(ekpnp_group* g, const ekpnp_section_spec* spec, int capacity);
+int ekpnp_group_section_disarm(ekpnp_group* g);
+int ekpnp_group_section_record(ekpnp_group* g, int64_t step, double time);    /* enqueues only */
+int ekpnp_group_section_count(const ekpnp_group* g, int64_t* recorded, int64_t* dropped);
+int ekpnp_group_section_read(ekpnp_group* g, int64_t first, int count, int64_t* steps, double* times, double* values);
+int ekpnp_group_section_ring_save(ekpnp_group* g, const char* path);
 
 #ifdef __cplusplus
 }
