@@ -14,14 +14,6 @@ using namespace ekpnp;
 
 static thread_local std::string g_create_err;
 
-#define HIPCHK(ctx, call)                                                                       \
-  do {                                                                                          \
-    hipError_t e_ = (call);                                                                     \
-    if (e_ != hipSuccess) {                                                                     \
-      (ctx).err = std::string(#call) + ": " + hipGetErrorString(e_);                            \
-      return e_ == hipErrorOutOfMemory ? EKPNP_ERR_NOMEM : EKPNP_ERR_HIP;                       \
-    }                                                                                           \
-  } while (0)
 // after the launches of an entry point: the first rejected launch, by kernel name
 #define LAUNCHCHK(ctx)                                                                          \
   do {                                                                                          \
@@ -39,15 +31,6 @@ static thread_local std::string g_create_err;
       return EKPNP_ERR_FFT;                                                                     \
     }                                                                                           \
   } while (0)
-
-#define NEEDCTX(ctx)                                                                            \
-  if (!(ctx)) return EKPNP_ERR_INVALID;                                                         \
-  Ctx& c = (ctx)->c
-
-static int fail(Ctx& c, const char* msg) {
-  c.err = msg;
-  return EKPNP_ERR_INVALID;
-}
 
 namespace ekpnp {
 void set_create_error(const std::string& msg) { g_create_err = msg; }

@@ -499,3 +499,23 @@ void io_ckpt_finish_load(Ctx&, const CkptHeader&);
 struct ekpnp_ctx {
   ekpnp::Ctx c;
 };
+
+// what the entry points of the C ABI open with and check their HIP calls with
+#define NEEDCTX(ctx)                    \
+  if (!(ctx)) return EKPNP_ERR_INVALID; \
+  Ctx& c = (ctx)->c
+#define HIPCHK(ctx, call)                                                  \
+  do {                                                                     \
+    hipError_t e_ = (call);                                                \
+    if (e_ != hipSuccess) {                                                \
+      (ctx).err = std::string(#call) + ": " + hipGetErrorString(e_);       \
+      return e_ == hipErrorOutOfMemory ? EKPNP_ERR_NOMEM : EKPNP_ERR_HIP;  \
+    }                                                                      \
+  } while (0)
+
+namespace ekpnp {
+inline int fail(Ctx& c, const char* msg) {
+  c.err = msg;
+  return EKPNP_ERR_INVALID;
+}
+}  // namespace ekpnp

@@ -35,6 +35,7 @@
 
 #include "ekpnp_internal.h"
 #include "reduce.h"
+#include "ring.h"
 
 using namespace ekpnp;
 
@@ -246,14 +247,9 @@ struct HistState {
   size_t part_bytes = 0;
   long long* planes = nullptr;  // [planes][cells + 1] of the last pass (or [planes][2] doubles of a range)
   size_t planes_bytes = 0;
-  long long* ring = nullptr;    // [capacity][cells + 1]
-  size_t ring_bytes = 0;
-  bool armed = false, ever_armed = false;
+  Ring ring;                    // rows of [cells + 1] long long
   ekpnp_hist_spec spec{};
-  int z_lo = 0, z_hi = 0, capacity = 0;
-  int64_t recorded = 0;
-  std::vector<int64_t> lab_step;  // the labels of the rows, [capacity], slot = row number % capacity
-  std::vector<double> lab_time;
+  int z_lo = 0, z_hi = 0;
 };
 
 static bool axis_ok(const ekpnp_hist_axis& x, const char* which, std::string& err) {
@@ -298,19 +294,19 @@ int hist_check_range(const ekpnp_params& p, int z_lo, int z_hi, int capacity, st
 int hist_cells(const ekpnp_hist_spec& s) { return (s.a.n + 2) * (s.b.n ? s.b.n + 2 : 1); }
 
 const ekpnp_hist_spec* hist_armed_spec(const Ctx& c, int* z_lo, int* z_hi) {
-  if (!c.hist || !c.hist->ever_armed) return nullptr;
+  if (!c.hist || !c.hist->ring.ever_armed) return nullptr;
   if (z_lo) *z_lo = c.hist->z_lo;
   if (z_hi) *z_hi = c.hist->z_hi;
   return &c.hist->spec;
 }
 
-bool hist_armed(const Ctx& c) { return c.hist && c.hist->armed; }
+bool hist_armed(const Ctx& c) { return c.hist && c.hist->ring.armed; }
 
 void hist_release(Ctx& c) {
   if (!c.hist) return;
   if (c.hist->part) (void)hipFree(c.hist->part);
   if (c.hist->planes) (void)hipFree(c.hist->planes);
-  if (c.hist->ring) (void)hipFree(c.hist->ring);
+  ring_release(c.hist->ring);
   delete c.hist;
   c.hist = nullptr;
 }
@@ -335,23 +331,6 @@ int hist_write_file(const char* path, const ekpnp_params& p, const ekpnp_hist_sp
 }
 
 }  // namespace ekpnp
-
-#define NEEDCTX(ctx)                    \
-  if (!(ctx)) return EKPNP_ERR_INVALID; \
-  Ctx& c = (ctx)->c
-#define HIPCHK(ctx, call)                                                  \
-  do {                                                                     \
-    hipError_t e_ = (call);                                                \
-    if (e_ != hipSuccess) {                                                \
-      (ctx).err = std::string(#call) + ": " + hipGetErrorString(e_);       \
-      return e_ == hipErrorOutOfMemory ? EKPNP_ERR_NOMEM : EKPNP_ERR_HIP;  \
-    }                                                                      \
-  } while (0)
-
-static int fail(Ctx& c, const char* msg) {
-  c.err = msg;
-  return EKPNP_ERR_INVALID;
-}
 
 static inline long long hist_chunk_nodes(int stride) { return HIST_CHUNK0 * (((long long)stride + 2047) / 2048); }
 static inline int hist_workgroups(const Ctx& c, long long chunk) { return (int)(((long long)c.plane + chunk - 1) / chunk); }
@@ -511,51 +490,30 @@ extern "C" int ekpnp_hist_arm(ekpnp_ctx* ctx, const ekpnp_hist_spec* spec, int z
   if (int rc = hist_check_range(c.p, z_lo, z_hi, capacity, c.err)) return rc;
   if (int rc = need_hist(c)) return rc;
   HistState& h = *c.hist;
-  h.armed = false;
-  HIPCHK(c, hipStreamSynchronize(c.stream));  // rows of an earlier arm may still be on their way into the ring
+  h.ring.armed = false;
   const size_t stride = (size_t)hist_cells(*spec) + 1;
   const int lo = z_lo > c.z0 ? z_lo : c.z0, hi = z_hi < c.z0 + c.nzl - 1 ? z_hi : c.z0 + c.nzl - 1;
   const int np = hi >= lo ? hi - lo + 1 : 0;  // this context's part of the range; 0: its rows are zeros
   if (np > 0)
     if (int rc = hist_scratch(c, hist_part_bytes(c, *spec, np), (size_t)np * stride * sizeof(long long))) return rc;
-  const size_t bytes = (size_t)capacity * stride * sizeof(long long);
-  if (!h.ring || h.ring_bytes != bytes) {
-    if (h.ring) {
-      (void)hipFree(h.ring);
-      c.bytes -= h.ring_bytes;
-      h.ring = nullptr;
-      h.ring_bytes = 0;
-    }
-    HIPCHK(c, hipMalloc((void**)&h.ring, bytes));
-    h.ring_bytes = bytes;
-    c.bytes += bytes;
-  }
-  HIPCHK(c, hipMemsetAsync(h.ring, 0, bytes, c.stream));
   h.spec = *spec;
   h.z_lo = z_lo;
   h.z_hi = z_hi;
-  h.capacity = capacity;
-  h.recorded = 0;
-  h.lab_step.assign((size_t)capacity, 0);
-  h.lab_time.assign((size_t)capacity, 0.0);
-  h.armed = true;
-  h.ever_armed = true;
-  return EKPNP_OK;
+  return ring_arm(c, h.ring, capacity, stride * sizeof(long long));
 }
 
 extern "C" int ekpnp_hist_disarm(ekpnp_ctx* ctx) {
   NEEDCTX(ctx);
-  if (c.hist) c.hist->armed = false;  // the ring and its rows stay readable until the next arm
+  if (c.hist) c.hist->ring.armed = false;  // the ring and its rows stay readable until the next arm
   return EKPNP_OK;
 }
 
 extern "C" int ekpnp_hist_record(ekpnp_ctx* ctx, int64_t step, double time) {
   NEEDCTX(ctx);
-  if (!c.hist || !c.hist->armed) return fail(c, "ekpnp_hist_record: no histogram armed");
+  if (!c.hist || !c.hist->ring.armed) return fail(c, "ekpnp_hist_record: no histogram armed");
   HistState& h = *c.hist;
   const size_t stride = (size_t)hist_cells(h.spec) + 1;
-  const size_t slot = (size_t)(h.recorded % h.capacity);
-  long long* row = h.ring + slot * stride;
+  long long* row = (long long*)ring_next_row(h.ring);
   const int lo = h.z_lo > c.z0 ? h.z_lo : c.z0, hi = h.z_hi < c.z0 + c.nzl - 1 ? h.z_hi : c.z0 + c.nzl - 1;
   if (hi < lo) {  // no plane of the range here: a row of zeros, no kernel reads a field
     HIPCHK(c, hipMemsetAsync(row, 0, stride * sizeof(long long), c.stream));
@@ -567,49 +525,19 @@ extern "C" int ekpnp_hist_record(ekpnp_ctx* ctx, int64_t step, double time) {
     note_launch(c, "k_hist_row");
     if (take_launch_error(c) != hipSuccess) return EKPNP_ERR_HIP;
   }
-  h.lab_step[slot] = step;
-  h.lab_time[slot] = time;
-  ++h.recorded;
+  ring_note_row(h.ring, step, time);
   return EKPNP_OK;
 }
 
 extern "C" int ekpnp_hist_count(const ekpnp_ctx* ctx, int64_t* recorded, int64_t* dropped) {
   if (!ctx) return EKPNP_ERR_INVALID;
-  const HistState* h = ctx->c.hist;
-  const int64_t rec = h && h->ring ? h->recorded : 0;
-  const int64_t held = h && h->ring && rec > h->capacity ? h->capacity : rec;
-  if (recorded) *recorded = rec;
-  if (dropped) *dropped = rec - held;
+  ring_count(ctx->c.hist ? &ctx->c.hist->ring : nullptr, recorded, dropped);
   return EKPNP_OK;
 }
 
 extern "C" int ekpnp_hist_read(ekpnp_ctx* ctx, int64_t first, int count, int64_t* steps, double* times, int64_t* counts) {
   NEEDCTX(ctx);
-  int64_t rec = 0, dropped = 0;
-  (void)ekpnp_hist_count(ctx, &rec, &dropped);
-  const int64_t held = rec - dropped;
-  if (first < 0 || count < 0 || first + (int64_t)count > held) {
-    c.err = "ekpnp_hist_read: rows " + std::to_string(first) + " .. " + std::to_string(first + (int64_t)count - 1) + " asked for, " + std::to_string(held) +
-            " held";
-    return EKPNP_ERR_INVALID;
-  }
-  if (count == 0) return EKPNP_OK;
-  if (!steps || !times || !counts) return fail(c, "NULL pointer");
-  HistState& h = *c.hist;
-  const size_t stride = (size_t)hist_cells(h.spec) + 1;
-  HIPCHK(c, hipStreamSynchronize(c.stream));
-  const int64_t seq0 = dropped + first;
-  for (int k = 0; k < count;) {  // at most two contiguous pieces of the ring
-    const size_t slot = (size_t)((seq0 + k) % h.capacity);
-    const int n = (int)((size_t)(count - k) < (size_t)h.capacity - slot ? (size_t)(count - k) : (size_t)h.capacity - slot);
-    HIPCHK(c, hipMemcpy(counts + (size_t)k * stride, h.ring + slot * stride, (size_t)n * stride * sizeof(int64_t), hipMemcpyDeviceToHost));
-    for (int j = 0; j < n; ++j) {
-      steps[k + j] = h.lab_step[slot + j];
-      times[k + j] = h.lab_time[slot + j];
-    }
-    k += n;
-  }
-  return EKPNP_OK;
+  return ring_read(c, c.hist ? &c.hist->ring : nullptr, "ekpnp_hist_read", first, count, steps, times, counts);
 }
 
 extern "C" int ekpnp_hist_save(ekpnp_ctx* ctx, const char* path) {

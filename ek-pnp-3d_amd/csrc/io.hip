@@ -17,9 +17,8 @@
 
 using namespace ekpnp;
 
-#define NEEDCTX(ctx)                    \
-  if (!(ctx)) return EKPNP_ERR_INVALID; \
-  Ctx& c = (ctx)->c
+// this file's HIPCHK reports every failed HIP call as EKPNP_ERR_HIP (the shared one tells a failed allocation apart)
+#undef HIPCHK
 #define HIPCHK(ctx, call)                                                  \
   do {                                                                     \
     hipError_t e_ = (call);                                                \
@@ -28,11 +27,6 @@ using namespace ekpnp;
       return EKPNP_ERR_HIP;                                                \
     }                                                                      \
   } while (0)
-
-static int fail(Ctx& c, const char* msg) {
-  c.err = msg;
-  return EKPNP_ERR_INVALID;
-}
 
 static int need_scratch(Ctx& c) {
   if (!c.diag) HIPCHK(c, hipMalloc((void**)&c.diag, DIAG_SCRATCH * sizeof(double)));

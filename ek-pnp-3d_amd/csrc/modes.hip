@@ -22,6 +22,7 @@
 
 #include "ekpnp_internal.h"
 #include "reduce.h"
+#include "ring.h"
 
 using namespace ekpnp;
 
@@ -151,14 +152,8 @@ struct ModeState {
   double* ab = nullptr;
   double2* tab_armed = nullptr;
   double2* tab_sync = nullptr;
-  double* ring = nullptr;     // [capacity][nmodes]
-  size_t ring_bytes = 0;
-  bool armed = false, ever_armed = false;
+  Ring ring;                  // rows of [nmodes] doubles
   ekpnp_modes_spec spec{};
-  int capacity = 0;
-  int64_t recorded = 0;
-  std::vector<int64_t> lab_step;  // the labels of the rows, [capacity], slot = row number % capacity
-  std::vector<double> lab_time;
   std::vector<double2> host_tab;  // what the last arm uploaded (kept while the copy may be in flight)
 };
 
@@ -203,14 +198,14 @@ static void mode_tables(const ekpnp_params& p, const ekpnp_modes_spec& s, int NM
   }
 }
 
-const ekpnp_modes_spec* modes_armed_spec(const Ctx& c) { return c.modes && c.modes->ever_armed ? &c.modes->spec : nullptr; }
+const ekpnp_modes_spec* modes_armed_spec(const Ctx& c) { return c.modes && c.modes->ring.ever_armed ? &c.modes->spec : nullptr; }
 
-bool modes_armed(const Ctx& c) { return c.modes && c.modes->armed; }
+bool modes_armed(const Ctx& c) { return c.modes && c.modes->ring.armed; }
 
 void modes_release(Ctx& c) {
   if (!c.modes) return;
   if (c.modes->scratch) (void)hipFree(c.modes->scratch);
-  if (c.modes->ring) (void)hipFree(c.modes->ring);
+  ring_release(c.modes->ring);
   delete c.modes;
   c.modes = nullptr;
 }
@@ -235,23 +230,6 @@ int modes_write_file(const char* path, const ekpnp_params& p, const ekpnp_modes_
 }
 
 }  // namespace ekpnp
-
-#define NEEDCTX(ctx)                    \
-  if (!(ctx)) return EKPNP_ERR_INVALID; \
-  Ctx& c = (ctx)->c
-#define HIPCHK(ctx, call)                                                  \
-  do {                                                                     \
-    hipError_t e_ = (call);                                                \
-    if (e_ != hipSuccess) {                                                \
-      (ctx).err = std::string(#call) + ": " + hipGetErrorString(e_);       \
-      return e_ == hipErrorOutOfMemory ? EKPNP_ERR_NOMEM : EKPNP_ERR_HIP;  \
-    }                                                                      \
-  } while (0)
-
-static int fail(Ctx& c, const char* msg) {
-  c.err = msg;
-  return EKPNP_ERR_INVALID;
-}
 
 // the host state, the reduction scratch and the two table slots, once
 static int need_modes(Ctx& c) {
@@ -340,91 +318,41 @@ extern "C" int ekpnp_modes_arm(ekpnp_ctx* ctx, const ekpnp_modes_spec* spec, int
   if (capacity < 1) { c.err = "modes: capacity = " + std::to_string(capacity) + " (must be >= 1)"; return EKPNP_ERR_INVALID; }
   if (int rc = need_modes(c)) return rc;
   ModeState& m = *c.modes;
-  m.armed = false;
-  HIPCHK(c, hipStreamSynchronize(c.stream));  // rows of an earlier arm may still be on their way into the ring and the tables
-  const size_t bytes = (size_t)capacity * spec->nmodes * sizeof(double);
-  if (!m.ring || m.ring_bytes != bytes) {
-    if (m.ring) {
-      (void)hipFree(m.ring);
-      c.bytes -= m.ring_bytes;
-      m.ring = nullptr;
-      m.ring_bytes = 0;
-    }
-    HIPCHK(c, hipMalloc((void**)&m.ring, bytes));
-    m.ring_bytes = bytes;
-    c.bytes += bytes;
-  }
-  HIPCHK(c, hipMemsetAsync(m.ring, 0, bytes, c.stream));
+  m.ring.armed = false;
+  HIPCHK(c, hipStreamSynchronize(c.stream));  // rows of an earlier arm may still be on their way through the tables
   mode_tables(c.p, *spec, mode_template(spec->nmodes), m.host_tab);
   HIPCHK(c, hipMemcpyAsync(m.tab_armed, m.host_tab.data(), m.host_tab.size() * sizeof(double2), hipMemcpyHostToDevice, c.stream));
   m.spec = *spec;
-  m.capacity = capacity;
-  m.recorded = 0;
-  m.lab_step.assign((size_t)capacity, 0);
-  m.lab_time.assign((size_t)capacity, 0.0);
-  m.armed = true;
-  m.ever_armed = true;
-  return EKPNP_OK;
+  return ring_arm(c, m.ring, capacity, (size_t)spec->nmodes * sizeof(double));
 }
 
 extern "C" int ekpnp_modes_disarm(ekpnp_ctx* ctx) {
   NEEDCTX(ctx);
-  if (c.modes) c.modes->armed = false;  // the ring and its rows stay readable until the next arm
+  if (c.modes) c.modes->ring.armed = false;  // the ring and its rows stay readable until the next arm
   return EKPNP_OK;
 }
 
 extern "C" int ekpnp_modes_record(ekpnp_ctx* ctx, int64_t step, double time) {
   NEEDCTX(ctx);
-  if (!c.modes || !c.modes->armed) return fail(c, "ekpnp_modes_record: no mode tracking armed");
+  if (!c.modes || !c.modes->ring.armed) return fail(c, "ekpnp_modes_record: no mode tracking armed");
   ModeState& m = *c.modes;
   if (int rc = modes_enqueue(c, m.spec, m.tab_armed)) return rc;
-  const size_t slot = (size_t)(m.recorded % m.capacity);
-  hipLaunchKernelGGL(k_mode_energy, dim3(1), dim3(64), 0, c.stream, m.ab, c.nzl, m.spec.nmodes, m.ring + slot * m.spec.nmodes);
+  hipLaunchKernelGGL(k_mode_energy, dim3(1), dim3(64), 0, c.stream, m.ab, c.nzl, m.spec.nmodes, (double*)ring_next_row(m.ring));
   note_launch(c, "k_mode_energy");
   if (take_launch_error(c) != hipSuccess) return EKPNP_ERR_HIP;
-  m.lab_step[slot] = step;
-  m.lab_time[slot] = time;
-  ++m.recorded;
+  ring_note_row(m.ring, step, time);
   return EKPNP_OK;
 }
 
 extern "C" int ekpnp_modes_count(const ekpnp_ctx* ctx, int64_t* recorded, int64_t* dropped) {
   if (!ctx) return EKPNP_ERR_INVALID;
-  const ModeState* m = ctx->c.modes;
-  const int64_t rec = m && m->ring ? m->recorded : 0;
-  const int64_t held = m && m->ring && rec > m->capacity ? m->capacity : rec;
-  if (recorded) *recorded = rec;
-  if (dropped) *dropped = rec - held;
+  ring_count(ctx->c.modes ? &ctx->c.modes->ring : nullptr, recorded, dropped);
   return EKPNP_OK;
 }
 
 extern "C" int ekpnp_modes_read(ekpnp_ctx* ctx, int64_t first, int count, int64_t* steps, double* times, double* values) {
   NEEDCTX(ctx);
-  int64_t rec = 0, dropped = 0;
-  (void)ekpnp_modes_count(ctx, &rec, &dropped);
-  const int64_t held = rec - dropped;
-  if (first < 0 || count < 0 || first + (int64_t)count > held) {
-    c.err = "ekpnp_modes_read: rows " + std::to_string(first) + " .. " + std::to_string(first + (int64_t)count - 1) + " asked for, " + std::to_string(held) +
-            " held";
-    return EKPNP_ERR_INVALID;
-  }
-  if (count == 0) return EKPNP_OK;
-  if (!steps || !times || !values) return fail(c, "NULL pointer");
-  ModeState& m = *c.modes;
-  const size_t nm = (size_t)m.spec.nmodes;
-  HIPCHK(c, hipStreamSynchronize(c.stream));
-  const int64_t seq0 = dropped + first;
-  for (int k = 0; k < count;) {  // at most two contiguous pieces of the ring
-    const size_t slot = (size_t)((seq0 + k) % m.capacity);
-    const int n = (int)((size_t)(count - k) < (size_t)m.capacity - slot ? (size_t)(count - k) : (size_t)m.capacity - slot);
-    HIPCHK(c, hipMemcpy(values + (size_t)k * nm, m.ring + slot * nm, (size_t)n * nm * sizeof(double), hipMemcpyDeviceToHost));
-    for (int j = 0; j < n; ++j) {
-      steps[k + j] = m.lab_step[slot + j];
-      times[k + j] = m.lab_time[slot + j];
-    }
-    k += n;
-  }
-  return EKPNP_OK;
+  return ring_read(c, c.modes ? &c.modes->ring : nullptr, "ekpnp_modes_read", first, count, steps, times, values);
 }
 
 extern "C" int ekpnp_modes_save(ekpnp_ctx* ctx, const char* path) {

@@ -26,6 +26,7 @@
 
 #include "ekpnp_internal.h"
 #include "reduce.h"
+#include "ring.h"
 
 using namespace ekpnp;
 
@@ -257,17 +258,10 @@ struct MonState {
   double* vpart = nullptr;
   double* vplane = nullptr;
   double* row = nullptr;
-  void* ring_alloc = nullptr;  // one allocation: [cursor (16 B) | ring [capacity][NM]]
-  size_t ring_bytes = 0;
-  unsigned long long* cursor = nullptr;
-  double* ring = nullptr;
-  bool armed = false;
+  Ring ring;  // [cursor (16 B header) | rows of [NM] doubles]; Ring::recorded is the device cursor once the stream has drained
   uint32_t mask = MON_ALL;
-  int every = 1, capacity = 0;
-  int64_t steps = 0;     // steps completed through ekpnp_step / ekpnp_group_step since arming
-  int64_t recorded = 0;  // rows enqueued since arming (the device cursor once the stream has drained)
-  std::vector<int64_t> lab_step;  // the labels of the rows, [capacity], slot = row number % capacity like the device ring
-  std::vector<double> lab_time;
+  int every = 1;
+  int64_t steps = 0;  // steps completed through ekpnp_step / ekpnp_group_step since arming
 };
 
 static inline int mon_workgroups(const Ctx& c) { return (int)(((long long)c.plane + MON_CHUNK - 1) / MON_CHUNK); }
@@ -286,17 +280,17 @@ int monitor_check_spec(const ekpnp_monitor_spec* s, std::string& err) {
   return EKPNP_OK;
 }
 
-int monitor_last_every(const Ctx& c) { return c.mon && c.mon->ring ? c.mon->every : 0; }
-int monitor_every(const Ctx& c) { return c.mon && c.mon->armed ? c.mon->every : 0; }
+int monitor_last_every(const Ctx& c) { return c.mon && c.mon->ring.alloc ? c.mon->every : 0; }
+int monitor_every(const Ctx& c) { return c.mon && c.mon->ring.armed ? c.mon->every : 0; }
 int monitor_steps_to_sample(const Ctx& c) {
-  if (!c.mon || !c.mon->armed) return 0x7fffffff;
+  if (!c.mon || !c.mon->ring.armed) return 0x7fffffff;
   return c.mon->every - (int)(c.mon->steps % c.mon->every);
 }
 
 void monitor_release(Ctx& c) {
   if (!c.mon) return;
   if (c.mon->scratch) (void)hipFree(c.mon->scratch);
-  if (c.mon->ring_alloc) (void)hipFree(c.mon->ring_alloc);
+  ring_release(c.mon->ring);
   delete c.mon;
   c.mon = nullptr;
 }
@@ -321,23 +315,6 @@ int monitor_write_file(const char* path, const ekpnp_params& p, int every, int64
 }
 
 }  // namespace ekpnp
-
-#define NEEDCTX(ctx)                    \
-  if (!(ctx)) return EKPNP_ERR_INVALID; \
-  Ctx& c = (ctx)->c
-#define HIPCHK(ctx, call)                                                  \
-  do {                                                                     \
-    hipError_t e_ = (call);                                                \
-    if (e_ != hipSuccess) {                                                \
-      (ctx).err = std::string(#call) + ": " + hipGetErrorString(e_);       \
-      return e_ == hipErrorOutOfMemory ? EKPNP_ERR_NOMEM : EKPNP_ERR_HIP;  \
-    }                                                                      \
-  } while (0)
-
-static int fail(Ctx& c, const char* msg) {
-  c.err = msg;
-  return EKPNP_ERR_INVALID;
-}
 
 // the host state and the reduction scratch, once
 static int need_monitor(Ctx& c) {
@@ -387,7 +364,7 @@ static int monitor_enqueue(Ctx& c, uint32_t mask, bool to_ring) {
     note_launch(c, "k_monitor_planes");
   }
   const MonFinishArgs f{m.ppart, m.vpart, m.vplane, nb, nwg, c.nzl, has_top ? 1 : 0, has_bot ? 1 : 0, mask, c.p.K, c.p.dz,
-                        to_ring ? m.ring : nullptr, m.cursor, m.capacity, m.row};
+                        to_ring ? (double*)m.ring.rows() : nullptr, (unsigned long long*)m.ring.alloc, m.ring.capacity, m.row};
   hipLaunchKernelGGL(k_monitor_finish, dim3(1), dim3(256), 0, c.stream, f);
   note_launch(c, "k_monitor_finish");
   if (take_launch_error(c) != hipSuccess) return EKPNP_ERR_HIP;
@@ -396,20 +373,14 @@ static int monitor_enqueue(Ctx& c, uint32_t mask, bool to_ring) {
 
 namespace ekpnp {
 int monitor_enqueue_row(Ctx& c) { return monitor_enqueue(c, c.mon->mask, true); }
-void monitor_note_row(Ctx& c, int64_t step, double time) {
-  MonState& m = *c.mon;
-  const size_t slot = (size_t)(m.recorded % m.capacity);
-  m.lab_step[slot] = step;
-  m.lab_time[slot] = time;
-  ++m.recorded;
-}
+void monitor_note_row(Ctx& c, int64_t step, double time) { ring_note_row(c.mon->ring, step, time); }
 void monitor_count_steps(Ctx& c, int n) { c.mon->steps += n; }
 void monitor_replayed_row(Ctx& c, double time) {
   ++c.mon->steps;
   monitor_note_row(c, c.mon->steps, time);
 }
 int monitor_step_done(Ctx& c) {
-  if (!c.mon || !c.mon->armed) return EKPNP_OK;
+  if (!c.mon || !c.mon->ring.armed) return EKPNP_OK;
   MonState& m = *c.mon;
   ++m.steps;
   if (m.steps % m.every != 0) return EKPNP_OK;
@@ -445,40 +416,17 @@ extern "C" int ekpnp_monitor_arm(ekpnp_ctx* ctx, const ekpnp_monitor_spec* spec)
   if (int rc = need_monitor(c)) return rc;
   MonState& m = *c.mon;
   drop_step_graph(c);  // a captured step holds (or lacks) the monitor's launches
-  const size_t bytes = 16 + (size_t)spec->capacity * NM * sizeof(double);
-  if (!m.ring_alloc || m.capacity != spec->capacity) {
-    m.armed = false;
-    if (m.ring_alloc) {
-      HIPCHK(c, hipStreamSynchronize(c.stream));
-      (void)hipFree(m.ring_alloc);
-      c.bytes -= m.ring_bytes;
-      m.ring_alloc = nullptr;
-      m.ring = nullptr;
-      m.cursor = nullptr;
-      m.ring_bytes = 0;
-    }
-    HIPCHK(c, hipMalloc(&m.ring_alloc, bytes));
-    m.ring_bytes = bytes;
-    c.bytes += bytes;
-    m.cursor = (unsigned long long*)m.ring_alloc;
-    m.ring = (double*)((char*)m.ring_alloc + 16);
-  }
-  HIPCHK(c, hipMemsetAsync(m.ring_alloc, 0, bytes, c.stream));
-  m.capacity = spec->capacity;
+  if (int rc = ring_arm(c, m.ring, spec->capacity, NM * sizeof(double), 16)) return rc;
   m.every = spec->every;
   m.mask = spec->quantities ? spec->quantities : MON_ALL;
   m.steps = 0;
-  m.recorded = 0;
-  m.lab_step.assign((size_t)m.capacity, 0);
-  m.lab_time.assign((size_t)m.capacity, 0.0);
-  m.armed = true;
   return EKPNP_OK;
 }
 
 extern "C" int ekpnp_monitor_disarm(ekpnp_ctx* ctx) {
   NEEDCTX(ctx);
-  if (c.mon && c.mon->armed) {
-    c.mon->armed = false;  // the ring and its rows stay readable until the next arm
+  if (c.mon && c.mon->ring.armed) {
+    c.mon->ring.armed = false;  // the ring and its rows stay readable until the next arm
     drop_step_graph(c);
   }
   return EKPNP_OK;
@@ -486,7 +434,7 @@ extern "C" int ekpnp_monitor_disarm(ekpnp_ctx* ctx) {
 
 extern "C" int ekpnp_monitor_record(ekpnp_ctx* ctx, int64_t step, double time) {
   NEEDCTX(ctx);
-  if (!c.mon || !c.mon->armed) return fail(c, "ekpnp_monitor_record: no monitor armed");
+  if (!c.mon || !c.mon->ring.armed) return fail(c, "ekpnp_monitor_record: no monitor armed");
   if (int rc = monitor_enqueue_row(c)) return rc;
   monitor_note_row(c, step, time);
   return EKPNP_OK;
@@ -494,40 +442,13 @@ extern "C" int ekpnp_monitor_record(ekpnp_ctx* ctx, int64_t step, double time) {
 
 extern "C" int ekpnp_monitor_count(const ekpnp_ctx* ctx, int64_t* recorded, int64_t* dropped) {
   if (!ctx) return EKPNP_ERR_INVALID;
-  const MonState* m = ctx->c.mon;
-  const int64_t rec = m && m->ring ? m->recorded : 0;
-  const int64_t held = m && m->ring && rec > m->capacity ? m->capacity : rec;
-  if (recorded) *recorded = rec;
-  if (dropped) *dropped = rec - held;
+  ring_count(ctx->c.mon ? &ctx->c.mon->ring : nullptr, recorded, dropped);
   return EKPNP_OK;
 }
 
 extern "C" int ekpnp_monitor_read(ekpnp_ctx* ctx, int64_t first, int count, int64_t* steps, double* times, double* values) {
   NEEDCTX(ctx);
-  int64_t rec = 0, dropped = 0;
-  (void)ekpnp_monitor_count(ctx, &rec, &dropped);
-  const int64_t held = rec - dropped;
-  if (first < 0 || count < 0 || first + (int64_t)count > held) {
-    c.err = "ekpnp_monitor_read: rows " + std::to_string(first) + " .. " + std::to_string(first + (int64_t)count - 1) + " asked for, " +
-            std::to_string(held) + " held";
-    return EKPNP_ERR_INVALID;
-  }
-  if (count == 0) return EKPNP_OK;
-  if (!steps || !times || !values) return fail(c, "NULL pointer");
-  MonState& m = *c.mon;
-  HIPCHK(c, hipStreamSynchronize(c.stream));
-  const int64_t seq0 = dropped + first;
-  for (int k = 0; k < count;) {  // at most two contiguous pieces of the ring
-    const size_t slot = (size_t)((seq0 + k) % m.capacity);
-    const int n = (int)((size_t)(count - k) < (size_t)m.capacity - slot ? (size_t)(count - k) : (size_t)m.capacity - slot);
-    HIPCHK(c, hipMemcpy(values + (size_t)k * NM, m.ring + slot * NM, (size_t)n * NM * sizeof(double), hipMemcpyDeviceToHost));
-    for (int j = 0; j < n; ++j) {
-      steps[k + j] = m.lab_step[slot + j];
-      times[k + j] = m.lab_time[slot + j];
-    }
-    k += n;
-  }
-  return EKPNP_OK;
+  return ring_read(c, c.mon ? &c.mon->ring : nullptr, "ekpnp_monitor_read", first, count, steps, times, values);
 }
 
 extern "C" int ekpnp_monitor_save(ekpnp_ctx* ctx, const char* path) {

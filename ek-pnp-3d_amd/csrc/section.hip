@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "ekpnp_internal.h"
+#include "ring.h"
 
 using namespace ekpnp;
 
@@ -181,14 +182,8 @@ __global__ void __launch_bounds__(64) k_section_x(SecArgs s) {
 struct SectionState {
   double* out = nullptr;   // the map of the last synchronous call; grows to the largest seen
   size_t out_bytes = 0;
-  double* ring = nullptr;  // [capacity][nvalues][nplanes][nkeep]
-  size_t ring_bytes = 0;
-  bool armed = false, ever_armed = false;
+  Ring ring;               // rows of [nvalues][nplanes][nkeep] doubles
   ekpnp_section_spec spec{};
-  int capacity = 0;
-  int64_t recorded = 0;
-  std::vector<int64_t> lab_step;  // the labels of the rows, [capacity], slot = row number % capacity
-  std::vector<double> lab_time;
 };
 
 static inline uint32_t section_mask(const ekpnp_section_spec& s) { return s.values ? s.values : (1u << SEC_NVALUES) - 1u; }
@@ -228,13 +223,13 @@ int section_check_ring(const ekpnp_section_spec& s, int capacity, std::string& e
 int section_nvalues(const ekpnp_section_spec& s) { return __builtin_popcount(section_mask(s)); }
 int section_nkeep(const ekpnp_params& p, const ekpnp_section_spec& s) { return s.across == EKPNP_ACROSS_X ? p.ny : p.nx; }
 
-const ekpnp_section_spec* section_armed_spec(const Ctx& c) { return c.section && c.section->ever_armed ? &c.section->spec : nullptr; }
-bool section_armed(const Ctx& c) { return c.section && c.section->armed; }
+const ekpnp_section_spec* section_armed_spec(const Ctx& c) { return c.section && c.section->ring.ever_armed ? &c.section->spec : nullptr; }
+bool section_armed(const Ctx& c) { return c.section && c.section->ring.armed; }
 
 void section_release(Ctx& c) {
   if (!c.section) return;
   if (c.section->out) (void)hipFree(c.section->out);
-  if (c.section->ring) (void)hipFree(c.section->ring);
+  ring_release(c.section->ring);
   delete c.section;
   c.section = nullptr;
 }
@@ -296,23 +291,6 @@ int section_write_ring_file(const char* path, const ekpnp_params& p, const ekpnp
 }
 
 }  // namespace ekpnp
-
-#define NEEDCTX(ctx)                    \
-  if (!(ctx)) return EKPNP_ERR_INVALID; \
-  Ctx& c = (ctx)->c
-#define HIPCHK(ctx, call)                                                  \
-  do {                                                                     \
-    hipError_t e_ = (call);                                                \
-    if (e_ != hipSuccess) {                                                \
-      (ctx).err = std::string(#call) + ": " + hipGetErrorString(e_);       \
-      return e_ == hipErrorOutOfMemory ? EKPNP_ERR_NOMEM : EKPNP_ERR_HIP;  \
-    }                                                                      \
-  } while (0)
-
-static int fail(Ctx& c, const char* msg) {
-  c.err = msg;
-  return EKPNP_ERR_INVALID;
-}
 
 static int need_section(Ctx& c) {
   if (c.section) return EKPNP_OK;
@@ -458,92 +436,40 @@ extern "C" int ekpnp_section_arm(ekpnp_ctx* ctx, const ekpnp_section_spec* spec,
   if (int rc = section_check_ring(*spec, capacity, c.err)) return rc;
   if (int rc = need_section(c)) return rc;
   SectionState& h = *c.section;
-  h.armed = false;
-  HIPCHK(c, hipStreamSynchronize(c.stream));  // rows of an earlier arm may still be on their way into the ring
-  const size_t bytes = (size_t)capacity * section_doubles(c, *spec) * sizeof(double);
-  if (!h.ring || h.ring_bytes != bytes) {
-    if (h.ring) {
-      (void)hipFree(h.ring);
-      c.bytes -= h.ring_bytes;
-      h.ring = nullptr;
-      h.ring_bytes = 0;
-    }
-    HIPCHK(c, hipMalloc((void**)&h.ring, bytes));
-    h.ring_bytes = bytes;
-    c.bytes += bytes;
-  }
-  HIPCHK(c, hipMemsetAsync(h.ring, 0, bytes, c.stream));
   h.spec = *spec;
-  h.capacity = capacity;
-  h.recorded = 0;
-  h.lab_step.assign((size_t)capacity, 0);
-  h.lab_time.assign((size_t)capacity, 0.0);
-  h.armed = true;
-  h.ever_armed = true;
-  return EKPNP_OK;
+  return ring_arm(c, h.ring, capacity, section_doubles(c, *spec) * sizeof(double));
 }
 
 extern "C" int ekpnp_section_disarm(ekpnp_ctx* ctx) {
   NEEDCTX(ctx);
-  if (c.section) c.section->armed = false;  // the ring and its rows stay readable until the next arm
+  if (c.section) c.section->ring.armed = false;  // the ring and its rows stay readable until the next arm
   return EKPNP_OK;
 }
 
 extern "C" int ekpnp_section_record(ekpnp_ctx* ctx, int64_t step, double time) {
   NEEDCTX(ctx);
-  if (!c.section || !c.section->armed) return fail(c, "ekpnp_section_record: no section armed");
+  if (!c.section || !c.section->ring.armed) return fail(c, "ekpnp_section_record: no section armed");
   SectionState& h = *c.section;
   const size_t row = section_doubles(c, h.spec);
-  const size_t slot = (size_t)(h.recorded % h.capacity);
-  double* out = h.ring + slot * row;
+  double* out = (double*)ring_next_row(h.ring);
   if (!section_owns_a_plane(c, h.spec)) {  // no chosen plane here: rows of +0.0, no kernel reads a field
     HIPCHK(c, hipMemsetAsync(out, 0, row * sizeof(double), c.stream));
   } else if (int rc = section_enqueue(c, h.spec, out)) {
     return rc;
   }
-  h.lab_step[slot] = step;
-  h.lab_time[slot] = time;
-  ++h.recorded;
+  ring_note_row(h.ring, step, time);
   return EKPNP_OK;
 }
 
 extern "C" int ekpnp_section_count(const ekpnp_ctx* ctx, int64_t* recorded, int64_t* dropped) {
   if (!ctx) return EKPNP_ERR_INVALID;
-  const SectionState* h = ctx->c.section;
-  const int64_t rec = h && h->ring ? h->recorded : 0;
-  const int64_t held = h && h->ring && rec > h->capacity ? h->capacity : rec;
-  if (recorded) *recorded = rec;
-  if (dropped) *dropped = rec - held;
+  ring_count(ctx->c.section ? &ctx->c.section->ring : nullptr, recorded, dropped);
   return EKPNP_OK;
 }
 
 extern "C" int ekpnp_section_read(ekpnp_ctx* ctx, int64_t first, int count, int64_t* steps, double* times, double* values) {
   NEEDCTX(ctx);
-  int64_t rec = 0, dropped = 0;
-  (void)ekpnp_section_count(ctx, &rec, &dropped);
-  const int64_t held = rec - dropped;
-  if (first < 0 || count < 0 || first + (int64_t)count > held) {
-    c.err = "ekpnp_section_read: rows " + std::to_string(first) + " .. " + std::to_string(first + (int64_t)count - 1) + " asked for, " + std::to_string(held) +
-            " held";
-    return EKPNP_ERR_INVALID;
-  }
-  if (count == 0) return EKPNP_OK;
-  if (!steps || !times || !values) return fail(c, "NULL pointer");
-  SectionState& h = *c.section;
-  const size_t row = section_doubles(c, h.spec);
-  HIPCHK(c, hipStreamSynchronize(c.stream));
-  const int64_t seq0 = dropped + first;
-  for (int k = 0; k < count;) {  // at most two contiguous pieces of the ring
-    const size_t slot = (size_t)((seq0 + k) % h.capacity);
-    const int n = (int)((size_t)(count - k) < (size_t)h.capacity - slot ? (size_t)(count - k) : (size_t)h.capacity - slot);
-    HIPCHK(c, hipMemcpy(values + (size_t)k * row, h.ring + slot * row, (size_t)n * row * sizeof(double), hipMemcpyDeviceToHost));
-    for (int j = 0; j < n; ++j) {
-      steps[k + j] = h.lab_step[slot + j];
-      times[k + j] = h.lab_time[slot + j];
-    }
-    k += n;
-  }
-  return EKPNP_OK;
+  return ring_read(c, c.section ? &c.section->ring : nullptr, "ekpnp_section_read", first, count, steps, times, values);
 }
 
 extern "C" int ekpnp_section_ring_save(ekpnp_ctx* ctx, const char* path) {

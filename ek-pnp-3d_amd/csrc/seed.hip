@@ -175,18 +175,6 @@ void seed_release(Ctx& c) {
 
 }  // namespace ekpnp
 
-#define NEEDCTX(ctx)                    \
-  if (!(ctx)) return EKPNP_ERR_INVALID; \
-  Ctx& c = (ctx)->c
-#define HIPCHK(ctx, call)                                                  \
-  do {                                                                     \
-    hipError_t e_ = (call);                                                \
-    if (e_ != hipSuccess) {                                                \
-      (ctx).err = std::string(#call) + ": " + hipGetErrorString(e_);       \
-      return e_ == hipErrorOutOfMemory ? EKPNP_ERR_NOMEM : EKPNP_ERR_HIP;  \
-    }                                                                      \
-  } while (0)
-
 extern "C" int ekpnp_seed_spec_check(const ekpnp_params* p, const ekpnp_seed_spec* spec) {
   std::string err;
   int rc = EKPNP_ERR_INVALID;

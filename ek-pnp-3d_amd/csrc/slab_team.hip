@@ -1543,9 +1543,62 @@ extern "C" int ekpnp_group_snapshot_finish(ekpnp_group* g) {
 }
 extern "C" int ekpnp_group_snapshot_pending(const ekpnp_group* g) { return g ? (int)g->t.snaps.size() : 0; }
 
-// ---- scalar time series (monitor.hip) over the slabs: every slab records on its own device; the host combines the slabs' rows -
-// sums in ascending slab order, maxima with max.  Only the plate-holding slab is non-zero in a plate column, so current_top is
-// ekpnp_group_current and uz_max is ekpnp_group_umax bit for bit (team_reduce adds and compares in the same order).
+// ---- fn on every slab in ascending slab order, each on its own device; the first failure ends the walk (T.err names the slab)
+template <class Fn>
+static int team_each_slab(Team& T, Fn&& fn) {
+  for (size_t i = 0; i < T.m.size(); ++i) {
+    int rc = use(T, (int)i);
+    if (rc) return rc;
+    TSLAB(T, (int)i, fn(T.m[i]));
+  }
+  return EKPNP_OK;
+}
+// a verb that computes or changes state on every slab: a failure leaves the slabs out of step, so it poisons the group
+template <class Fn>
+static int team_all(Team& T, Fn&& fn) { return group_fail(T, team_each_slab(T, fn)); }
+
+// ---- the group side of the five time series (monitor, modes, spectrum, hist, section; csrc/ring.h), once.  Every slab keeps a
+// ring of its own on its own device and the slabs record in step, so slab 0 answers for the count and for "armed".  Arm and the
+// synchronous calls validate on slab 0's parameters first: a refusal comes before any slab has launched anything and the group
+// stays usable.  A read asks every slab for the same rows and combines them on the host; it does not poison the group.
+static int team_series_record(Team& T, bool armed, const char* not_armed, int (*record)(ekpnp_ctx*, int64_t, double), int64_t step, double time) {
+  if (!armed) { T.err = not_armed; return EKPNP_ERR_INVALID; }  // (refused before any slab is asked)
+  return team_all(T, [&](ekpnp_ctx* m) { return record(m, step, time); });  // enqueues only, on every slab's compute stream (as ekpnp_group_stats_accumulate)
+}
+static int team_series_count(const ekpnp_group* g, int (*count)(const ekpnp_ctx*, int64_t*, int64_t*), int64_t* recorded, int64_t* dropped) {
+  if (!g || g->t.m.empty()) return EKPNP_ERR_INVALID;
+  return count(g->t.m[0], recorded, dropped);
+}
+// read(m) fills the caller's scratch with one slab's rows, combine(c, head) merges them into the result (head: the first slab)
+template <class Read, class Combine>
+static int team_series_read(Team& T, int count, Read&& read, Combine&& combine) {
+  bool head = true;
+  return team_each_slab(T, [&](ekpnp_ctx* m) {
+    const int rc = read(m);
+    if (rc == EKPNP_OK && count > 0) { combine(m->c, head); head = false; }
+    return rc;
+  });
+}
+// the held rows (`row` elements each) with their labels, then the file: read(n, steps, times, rows), write(rec, dropped, n, steps, times, rows)
+template <class Elem, class Read, class Write>
+static int team_series_save(const ekpnp_group* g, int (*count)(const ekpnp_group*, int64_t*, int64_t*), size_t row, Read&& read, Write&& write) {
+  int64_t rec = 0, dropped = 0;
+  (void)count(g, &rec, &dropped);
+  const int n = (int)(rec - dropped);
+  std::vector<int64_t> steps((size_t)n);
+  std::vector<double> times((size_t)n);
+  std::vector<Elem> rows((size_t)n * row);
+  if (int rc = read(n, steps.data(), times.data(), rows.data())) return rc;
+  return write(rec, dropped, n, steps.data(), times.data(), rows.data());
+}
+static inline size_t series_rows(int count) { return (size_t)(count > 0 ? count : 0); }
+// the combine steps: add in ascending slab order (modes, hist) ...
+template <class Elem>
+static void rows_add(Elem* acc, const Elem* v, size_t n, bool head) {
+  for (size_t k = 0; k < n; ++k) acc[k] = head ? v[k] : acc[k] + v[k];
+}
+// ... monitor's sum or max per column: only the plate-holding slab is non-zero in a plate column, so current_top is
+// ekpnp_group_current and uz_max is ekpnp_group_umax bit for bit (team_reduce adds and compares in the same order) ...
 static inline bool monitor_is_max(int q) { return q == 4 || q == 9; }
 static void monitor_combine(double* acc, const double* v, int rows, bool first) {
   for (int r = 0; r < rows; ++r)
@@ -1555,15 +1608,19 @@ static void monitor_combine(double* acc, const double* v, int rows, bool first) 
       a = first ? b : (monitor_is_max(q) ? std::fmax(a, b) : a + b);
     }
 }
-template <class Fn>
-static int team_monitor_each(Team& T, Fn&& fn) {
-  for (size_t i = 0; i < T.m.size(); ++i) {
-    int rc = use(T, (int)i);
-    if (rc) return rc;
-    TSLAB(T, (int)i, fn(T.m[i]));
-  }
-  return EKPNP_OK;
+// ... or place the rows of the planes a slab owns (spectrum, section): slabs are cut along z, so a plane lives on one slab.
+// part and whole are [outer][planes][inner]; planes == 0: all planes (a slab holds nzl of them, the whole lattice nz)
+static void rows_place(const Ctx& c, int nplanes, const int* z, size_t outer, size_t inner, const double* part, double* whole) {
+  const size_t np_part = nplanes ? (size_t)nplanes : (size_t)c.nzl, np_whole = nplanes ? (size_t)nplanes : (size_t)c.p.nz;
+  for (size_t o = 0; o < outer; ++o)
+    for (size_t j = 0; j < np_part; ++j) {
+      const int zj = nplanes ? z[j] : c.z0 + (int)j;
+      if (zj < c.z0 || zj >= c.z0 + c.nzl) continue;  // (another slab's row)
+      std::memcpy(whole + (o * np_whole + (nplanes ? j : (size_t)zj)) * inner, part + (o * np_part + j) * inner, inner * sizeof(double));
+    }
 }
+
+// ---- scalar time series (monitor.hip) over the slabs
 extern "C" int ekpnp_group_monitor_sample(ekpnp_group* g, uint32_t quantities, double* out) {
   NEEDLIVEGROUP(g);
   if (!out) { T.err = "NULL pointer"; return EKPNP_ERR_INVALID; }
@@ -1573,50 +1630,39 @@ extern "C" int ekpnp_group_monitor_sample(ekpnp_group* g, uint32_t quantities, d
   }
   double v[EKPNP_NMONITORS];
   bool first = true;
-  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) {
+  return team_all(T, [&](ekpnp_ctx* m) {
     const int rc = ekpnp_monitor_sample(m, quantities, v);
     if (rc == EKPNP_OK) { monitor_combine(out, v, 1, first); first = false; }
     return rc;
-  }));
+  });
 }
 extern "C" int ekpnp_group_monitor_arm(ekpnp_group* g, const ekpnp_monitor_spec* spec) {
   NEEDLIVEGROUP(g);
   if (int rc = monitor_check_spec(spec, T.err)) return rc;
-  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) { return ekpnp_monitor_arm(m, spec); }));
+  return team_all(T, [&](ekpnp_ctx* m) { return ekpnp_monitor_arm(m, spec); });
 }
-extern "C" int ekpnp_group_monitor_disarm(ekpnp_group* g) {
-  NEEDLIVEGROUP(g);
-  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) { return ekpnp_monitor_disarm(m); }));
-}
-// enqueues only, on every slab's compute stream (as ekpnp_group_stats_accumulate)
+extern "C" int ekpnp_group_monitor_disarm(ekpnp_group* g) { NEEDLIVEGROUP(g); return team_all(T, ekpnp_monitor_disarm); }
 extern "C" int ekpnp_group_monitor_record(ekpnp_group* g, int64_t step, double time) {
   NEEDLIVEGROUP(g);
-  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) { return ekpnp_monitor_record(m, step, time); }));
+  return team_series_record(T, true, "", ekpnp_monitor_record, step, time);  // (every slab refuses for itself when none is armed)
 }
 extern "C" int ekpnp_group_monitor_count(const ekpnp_group* g, int64_t* recorded, int64_t* dropped) {
-  if (!g || g->t.m.empty()) return EKPNP_ERR_INVALID;
-  return ekpnp_monitor_count(g->t.m[0], recorded, dropped);  // the slabs record in step
+  return team_series_count(g, ekpnp_monitor_count, recorded, dropped);
 }
 extern "C" int ekpnp_group_monitor_read(ekpnp_group* g, int64_t first, int count, int64_t* steps, double* times, double* values) {
   NEEDLIVEGROUP(g);
-  std::vector<double> v((size_t)(count > 0 ? count : 0) * EKPNP_NMONITORS);
-  bool head = true;
-  return team_monitor_each(T, [&](ekpnp_ctx* m) {
-    const int rc = ekpnp_monitor_read(m, first, count, steps, times, v.data());
-    if (rc == EKPNP_OK && count > 0) { monitor_combine(values, v.data(), count, head); head = false; }
-    return rc;
-  });
+  std::vector<double> v(series_rows(count) * EKPNP_NMONITORS);
+  return team_series_read(T, count, [&](ekpnp_ctx* m) { return ekpnp_monitor_read(m, first, count, steps, times, v.data()); },
+                          [&](const Ctx&, bool head) { monitor_combine(values, v.data(), count, head); });
 }
 extern "C" int ekpnp_group_monitor_save(ekpnp_group* g, const char* path) {
   NEEDLIVEGROUP(g);
   if (!path) { T.err = "NULL path"; return EKPNP_ERR_INVALID; }
-  int64_t rec = 0, dropped = 0;
-  (void)ekpnp_group_monitor_count(g, &rec, &dropped);
-  const int n = (int)(rec - dropped);
-  std::vector<int64_t> steps((size_t)n);
-  std::vector<double> times((size_t)n), values((size_t)n * EKPNP_NMONITORS);
-  if (int rc = ekpnp_group_monitor_read(g, 0, n, steps.data(), times.data(), values.data())) return rc;
-  return monitor_write_file(path, S(T, 0).p, monitor_last_every(S(T, 0)), rec, dropped, n, steps.data(), times.data(), values.data(), T.err);
+  return team_series_save<double>(g, ekpnp_group_monitor_count, EKPNP_NMONITORS,
+                                  [&](int n, int64_t* steps, double* times, double* v) { return ekpnp_group_monitor_read(g, 0, n, steps, times, v); },
+                                  [&](int64_t rec, int64_t dropped, int n, const int64_t* steps, const double* times, const double* v) {
+                                    return monitor_write_file(path, S(T, 0).p, monitor_last_every(S(T, 0)), rec, dropped, n, steps, times, v, T.err);
+                                  });
 }
 
 // ---- seeding (seed.hip) over the slabs: every slab seeds its own planes on its own device; the noise depends on the global
@@ -1624,18 +1670,18 @@ extern "C" int ekpnp_group_monitor_save(ekpnp_group* g, const char* path) {
 extern "C" int ekpnp_group_seed(ekpnp_group* g, const ekpnp_seed_spec* spec) {
   NEEDLIVEGROUP(g);
   if (int rc = seed_check_spec(S(T, 0).p, spec, T.err)) return rc;  // refused before any slab has launched anything
-  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) { return ekpnp_seed(m, spec); }));
+  return team_all(T, [&](ekpnp_ctx* m) { return ekpnp_seed(m, spec); });
 }
 
-// ---- mode projection (modes.hip) over the slabs: slabs are cut along z, so a plane's (a, b) live on one slab; every slab
-// records its own energies and the host adds them in ascending slab order
+// ---- mode projection (modes.hip) over the slabs: a plane's (a, b) live on one slab; every slab records its own energies and
+// the host adds them in ascending slab order
 extern "C" int ekpnp_group_mode_amplitudes(ekpnp_group* g, const ekpnp_modes_spec* spec, double* host_out) {
   NEEDLIVEGROUP(g);
   if (!host_out) { T.err = "NULL pointer"; return EKPNP_ERR_INVALID; }
   const ekpnp_params& p = S(T, 0).p;
   if (int rc = modes_check_spec(p, spec, T.err)) return rc;
   std::vector<double> v;
-  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) {
+  return team_all(T, [&](ekpnp_ctx* m) {
     const Ctx& c = m->c;
     v.resize((size_t)spec->nmodes * c.nzl * 2);
     const int rc = ekpnp_mode_amplitudes(m, spec, v.data());
@@ -1643,59 +1689,43 @@ extern "C" int ekpnp_group_mode_amplitudes(ekpnp_group* g, const ekpnp_modes_spe
       for (int j = 0; j < spec->nmodes; ++j)
         std::memcpy(host_out + ((size_t)j * p.nz + c.z0) * 2, v.data() + (size_t)j * c.nzl * 2, (size_t)c.nzl * 2 * sizeof(double));
     return rc;
-  }));
+  });
 }
 extern "C" int ekpnp_group_modes_arm(ekpnp_group* g, const ekpnp_modes_spec* spec, int capacity) {
   NEEDLIVEGROUP(g);
   if (int rc = modes_check_spec(S(T, 0).p, spec, T.err)) return rc;
   if (capacity < 1) { T.err = "modes: capacity = " + std::to_string(capacity) + " (must be >= 1)"; return EKPNP_ERR_INVALID; }
-  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) { return ekpnp_modes_arm(m, spec, capacity); }));
+  return team_all(T, [&](ekpnp_ctx* m) { return ekpnp_modes_arm(m, spec, capacity); });
 }
-extern "C" int ekpnp_group_modes_disarm(ekpnp_group* g) {
-  NEEDLIVEGROUP(g);
-  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) { return ekpnp_modes_disarm(m); }));
-}
-// enqueues only, on every slab's compute stream (as ekpnp_group_stats_accumulate)
+extern "C" int ekpnp_group_modes_disarm(ekpnp_group* g) { NEEDLIVEGROUP(g); return team_all(T, ekpnp_modes_disarm); }
 extern "C" int ekpnp_group_modes_record(ekpnp_group* g, int64_t step, double time) {
   NEEDLIVEGROUP(g);
-  if (!modes_armed(S(T, 0))) { T.err = "ekpnp_modes_record: no mode tracking armed"; return EKPNP_ERR_INVALID; }  // (refused before any slab is asked: the group stays usable)
-  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) { return ekpnp_modes_record(m, step, time); }));
+  return team_series_record(T, modes_armed(S(T, 0)), "ekpnp_modes_record: no mode tracking armed", ekpnp_modes_record, step, time);
 }
 extern "C" int ekpnp_group_modes_count(const ekpnp_group* g, int64_t* recorded, int64_t* dropped) {
-  if (!g || g->t.m.empty()) return EKPNP_ERR_INVALID;
-  return ekpnp_modes_count(g->t.m[0], recorded, dropped);  // the slabs record in step
+  return team_series_count(g, ekpnp_modes_count, recorded, dropped);
 }
 extern "C" int ekpnp_group_modes_read(ekpnp_group* g, int64_t first, int count, int64_t* steps, double* times, double* values) {
   NEEDLIVEGROUP(g);
   const ekpnp_modes_spec* spec = modes_armed_spec(S(T, 0));
-  const size_t nm = spec ? (size_t)spec->nmodes : 0;
-  std::vector<double> v((size_t)(count > 0 ? count : 0) * nm);
-  bool head = true;
-  return team_monitor_each(T, [&](ekpnp_ctx* m) {
-    const int rc = ekpnp_modes_read(m, first, count, steps, times, v.data());
-    if (rc == EKPNP_OK && count > 0) {
-      for (size_t k = 0; k < v.size(); ++k) values[k] = head ? v[k] : values[k] + v[k];
-      head = false;
-    }
-    return rc;
-  });
+  std::vector<double> v(series_rows(count) * (spec ? (size_t)spec->nmodes : 0));
+  return team_series_read(T, count, [&](ekpnp_ctx* m) { return ekpnp_modes_read(m, first, count, steps, times, v.data()); },
+                          [&](const Ctx&, bool head) { rows_add(values, v.data(), v.size(), head); });
 }
 extern "C" int ekpnp_group_modes_save(ekpnp_group* g, const char* path) {
   NEEDLIVEGROUP(g);
   if (!path) { T.err = "NULL path"; return EKPNP_ERR_INVALID; }
   const ekpnp_modes_spec* spec = modes_armed_spec(S(T, 0));
   if (!spec) { T.err = "ekpnp_modes_save: no mode tracking was armed"; return EKPNP_ERR_INVALID; }
-  int64_t rec = 0, dropped = 0;
-  (void)ekpnp_group_modes_count(g, &rec, &dropped);
-  const int n = (int)(rec - dropped);
-  std::vector<int64_t> steps((size_t)n);
-  std::vector<double> times((size_t)n), values((size_t)n * spec->nmodes);
-  if (int rc = ekpnp_group_modes_read(g, 0, n, steps.data(), times.data(), values.data())) return rc;
-  return modes_write_file(path, S(T, 0).p, *spec, rec, dropped, n, steps.data(), times.data(), values.data(), T.err);
+  return team_series_save<double>(g, ekpnp_group_modes_count, (size_t)spec->nmodes,
+                                  [&](int n, int64_t* steps, double* times, double* v) { return ekpnp_group_modes_read(g, 0, n, steps, times, v); },
+                                  [&](int64_t rec, int64_t dropped, int n, const int64_t* steps, const double* times, const double* v) {
+                                    return modes_write_file(path, S(T, 0).p, *spec, rec, dropped, n, steps, times, v, T.err);
+                                  });
 }
 
-// ---- plane spectra (spectrum.hip) over the slabs: slabs are cut along z, so a plane lives on one slab; every slab handles the
-// planes it owns on its own device and the host takes each row from its owner (no exchange, nothing is added)
+// ---- plane spectra (spectrum.hip) over the slabs: every slab handles the planes it owns on its own device and the host takes
+// each row from its owner (no exchange, nothing is added)
 static int spectrum_owner(Team& T, int z) {
   for (size_t i = 0; i < T.m.size(); ++i)
     if (z >= S(T, (int)i).z0 && z < S(T, (int)i).z0 + S(T, (int)i).nzl) return (int)i;
@@ -1719,42 +1749,32 @@ extern "C" int ekpnp_group_spectrum(ekpnp_group* g, const ekpnp_spectrum_spec* s
   int nshell = 0;
   if (int rc = spectrum_shell_count(p, &nshell, nullptr, T.err)) return rc;
   std::vector<double> sh, pk;
-  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) {
+  return team_all(T, [&](ekpnp_ctx* m) {
     const Ctx& c = m->c;
     const int np = spec->nplanes ? spec->nplanes : c.nzl;
     sh.resize((size_t)np * nshell);
     pk.resize((size_t)np * 3);
     const int rc = ekpnp_spectrum(m, spec, sh.data(), pk.data());
     if (rc) return rc;
-    for (int j = 0; j < np; ++j) {
-      const int z = spec->nplanes ? spec->z[j] : c.z0 + j, row = spec->nplanes ? j : z;
-      if (z < c.z0 || z >= c.z0 + c.nzl) continue;  // (another slab's row)
-      std::memcpy(shells + (size_t)row * nshell, sh.data() + (size_t)j * nshell, (size_t)nshell * sizeof(double));
-      if (peaks) std::memcpy(peaks + (size_t)row * 3, pk.data() + (size_t)j * 3, 3 * sizeof(double));
-    }
+    rows_place(c, spec->nplanes, spec->z, 1, (size_t)nshell, sh.data(), shells);
+    if (peaks) rows_place(c, spec->nplanes, spec->z, 1, 3, pk.data(), peaks);
     return rc;
-  }));
+  });
 }
 extern "C" int ekpnp_group_spectrum_arm(ekpnp_group* g, const ekpnp_spectrum_spec* spec, int capacity) {
   NEEDLIVEGROUP(g);
   if (int rc = spectrum_check_spec(S(T, 0).p, spec, T.err)) return rc;
   if (spec->nplanes < 1) { T.err = "spectrum: nplanes = " + std::to_string(spec->nplanes) + " (a time series needs 1 .. 16 chosen planes)"; return EKPNP_ERR_INVALID; }
   if (capacity < 1) { T.err = "spectrum: capacity = " + std::to_string(capacity) + " (must be >= 1)"; return EKPNP_ERR_INVALID; }
-  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) { return ekpnp_spectrum_arm(m, spec, capacity); }));
+  return team_all(T, [&](ekpnp_ctx* m) { return ekpnp_spectrum_arm(m, spec, capacity); });
 }
-extern "C" int ekpnp_group_spectrum_disarm(ekpnp_group* g) {
-  NEEDLIVEGROUP(g);
-  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) { return ekpnp_spectrum_disarm(m); }));
-}
-// enqueues only, on every slab's compute stream (as ekpnp_group_stats_accumulate)
+extern "C" int ekpnp_group_spectrum_disarm(ekpnp_group* g) { NEEDLIVEGROUP(g); return team_all(T, ekpnp_spectrum_disarm); }
 extern "C" int ekpnp_group_spectrum_record(ekpnp_group* g, int64_t step, double time) {
   NEEDLIVEGROUP(g);
-  if (!spectrum_armed(S(T, 0))) { T.err = "ekpnp_spectrum_record: no spectrum tracking armed"; return EKPNP_ERR_INVALID; }  // (refused before any slab is asked: the group stays usable)
-  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) { return ekpnp_spectrum_record(m, step, time); }));
+  return team_series_record(T, spectrum_armed(S(T, 0)), "ekpnp_spectrum_record: no spectrum tracking armed", ekpnp_spectrum_record, step, time);
 }
 extern "C" int ekpnp_group_spectrum_count(const ekpnp_group* g, int64_t* recorded, int64_t* dropped) {
-  if (!g || g->t.m.empty()) return EKPNP_ERR_INVALID;
-  return ekpnp_spectrum_count(g->t.m[0], recorded, dropped);  // the slabs record in step
+  return team_series_count(g, ekpnp_spectrum_count, recorded, dropped);
 }
 extern "C" int ekpnp_group_spectrum_read(ekpnp_group* g, int64_t first, int count, int64_t* steps, double* times, double* shells, double* peaks) {
   NEEDLIVEGROUP(g);
@@ -1762,20 +1782,13 @@ extern "C" int ekpnp_group_spectrum_read(ekpnp_group* g, int64_t first, int coun
   int nshell = 0;
   if (spec)
     if (int rc = spectrum_shell_count(S(T, 0).p, &nshell, nullptr, T.err)) return rc;
-  const size_t np = spec ? (size_t)spec->nplanes : 0, rows = (size_t)(count > 0 ? count : 0);
+  const size_t np = spec ? (size_t)spec->nplanes : 0, rows = series_rows(count);
   std::vector<double> sh(rows * np * nshell), pk(rows * np * 3);
-  return team_monitor_each(T, [&](ekpnp_ctx* m) {
-    const Ctx& c = m->c;
-    const int rc = ekpnp_spectrum_read(m, first, count, steps, times, sh.data(), pk.data());
-    if (rc == EKPNP_OK && count > 0)
-      for (size_t r = 0; r < rows; ++r)
-        for (size_t j = 0; j < np; ++j) {
-          if (spec->z[j] < c.z0 || spec->z[j] >= c.z0 + c.nzl) continue;  // (another slab's row)
-          std::memcpy(shells + (r * np + j) * nshell, sh.data() + (r * np + j) * nshell, (size_t)nshell * sizeof(double));
-          if (peaks) std::memcpy(peaks + (r * np + j) * 3, pk.data() + (r * np + j) * 3, 3 * sizeof(double));
-        }
-    return rc;
-  });
+  return team_series_read(T, count, [&](ekpnp_ctx* m) { return ekpnp_spectrum_read(m, first, count, steps, times, sh.data(), pk.data()); },
+                          [&](const Ctx& c, bool) {
+                            rows_place(c, spec->nplanes, spec->z, rows, (size_t)nshell, sh.data(), shells);
+                            if (peaks) rows_place(c, spec->nplanes, spec->z, rows, 3, pk.data(), peaks);
+                          });
 }
 extern "C" int ekpnp_group_spectrum_save(ekpnp_group* g, const char* path) {
   NEEDLIVEGROUP(g);
@@ -1785,64 +1798,51 @@ extern "C" int ekpnp_group_spectrum_save(ekpnp_group* g, const char* path) {
   int nshell = 0;
   double L = 0.0;
   if (int rc = spectrum_shell_count(S(T, 0).p, &nshell, &L, T.err)) return rc;
-  int64_t rec = 0, dropped = 0;
-  (void)ekpnp_group_spectrum_count(g, &rec, &dropped);
-  const int n = (int)(rec - dropped);
-  std::vector<int64_t> steps((size_t)n);
-  std::vector<double> times((size_t)n), shells((size_t)n * spec->nplanes * nshell), peaks((size_t)n * spec->nplanes * 3);
-  if (int rc = ekpnp_group_spectrum_read(g, 0, n, steps.data(), times.data(), shells.data(), peaks.data())) return rc;
-  return spectrum_write_file(path, S(T, 0).p, *spec, nshell, L, rec, dropped, n, steps.data(), times.data(), shells.data(), peaks.data(), T.err);
+  const size_t np = (size_t)spec->nplanes;  // the rows of the n samples: all shells [n][np][nshell], then all peaks [n][np][3]
+  return team_series_save<double>(g, ekpnp_group_spectrum_count, np * ((size_t)nshell + 3),
+                                  [&](int n, int64_t* steps, double* times, double* v) {
+                                    return ekpnp_group_spectrum_read(g, 0, n, steps, times, v, v + (size_t)n * np * nshell);
+                                  },
+                                  [&](int64_t rec, int64_t dropped, int n, const int64_t* steps, const double* times, const double* v) {
+                                    return spectrum_write_file(path, S(T, 0).p, *spec, nshell, L, rec, dropped, n, steps, times, v, v + (size_t)n * np * nshell, T.err);
+                                  });
 }
 
-// ---- histograms (hist.hip) over the slabs: slabs are cut along z, so a plane's counts live on one slab and the synchronous calls
-// write each slab's planes at its z0; every slab records the planes of the armed range it owns and the host adds the rows (integers)
+// ---- histograms (hist.hip) over the slabs: a plane's counts live on one slab and the synchronous calls write each slab's planes
+// at its z0; every slab records the planes of the armed range it owns and the host adds the rows (integers)
 extern "C" int ekpnp_group_hist_planes(ekpnp_group* g, const ekpnp_hist_spec* spec, int64_t* counts, int64_t* nonfinite) {
   NEEDLIVEGROUP(g);
   if (!counts || !nonfinite) { T.err = "NULL pointer"; return EKPNP_ERR_INVALID; }
   if (int rc = hist_check_spec(S(T, 0).p, spec, T.err)) return rc;  // refused before any slab has launched anything
   const size_t cells = (size_t)hist_cells(*spec);
-  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) { return ekpnp_hist_planes(m, spec, counts + (size_t)m->c.z0 * cells, nonfinite + m->c.z0); }));
+  return team_all(T, [&](ekpnp_ctx* m) { return ekpnp_hist_planes(m, spec, counts + (size_t)m->c.z0 * cells, nonfinite + m->c.z0); });
 }
 extern "C" int ekpnp_group_value_range(ekpnp_group* g, int value, double* vmin, double* vmax) {
   NEEDLIVEGROUP(g);
   if (!vmin || !vmax) { T.err = "NULL pointer"; return EKPNP_ERR_INVALID; }
   if (value < 0 || value > EKPNP_HIST_Q) { T.err = "hist: value = " + std::to_string(value) + " outside 0 .. 11"; return EKPNP_ERR_INVALID; }
-  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) { return ekpnp_value_range(m, value, vmin + m->c.z0, vmax + m->c.z0); }));
+  return team_all(T, [&](ekpnp_ctx* m) { return ekpnp_value_range(m, value, vmin + m->c.z0, vmax + m->c.z0); });
 }
 extern "C" int ekpnp_group_hist_arm(ekpnp_group* g, const ekpnp_hist_spec* spec, int z_lo, int z_hi, int capacity) {
   NEEDLIVEGROUP(g);
   if (int rc = hist_check_spec(S(T, 0).p, spec, T.err)) return rc;
   if (int rc = hist_check_range(S(T, 0).p, z_lo, z_hi, capacity, T.err)) return rc;
-  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) { return ekpnp_hist_arm(m, spec, z_lo, z_hi, capacity); }));
+  return team_all(T, [&](ekpnp_ctx* m) { return ekpnp_hist_arm(m, spec, z_lo, z_hi, capacity); });
 }
-extern "C" int ekpnp_group_hist_disarm(ekpnp_group* g) {
-  NEEDLIVEGROUP(g);
-  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) { return ekpnp_hist_disarm(m); }));
-}
-// enqueues only, on every slab's compute stream (as ekpnp_group_stats_accumulate)
+extern "C" int ekpnp_group_hist_disarm(ekpnp_group* g) { NEEDLIVEGROUP(g); return team_all(T, ekpnp_hist_disarm); }
 extern "C" int ekpnp_group_hist_record(ekpnp_group* g, int64_t step, double time) {
   NEEDLIVEGROUP(g);
-  if (!hist_armed(S(T, 0))) { T.err = "ekpnp_hist_record: no histogram armed"; return EKPNP_ERR_INVALID; }  // (refused before any slab is asked: the group stays usable)
-  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) { return ekpnp_hist_record(m, step, time); }));
+  return team_series_record(T, hist_armed(S(T, 0)), "ekpnp_hist_record: no histogram armed", ekpnp_hist_record, step, time);
 }
 extern "C" int ekpnp_group_hist_count(const ekpnp_group* g, int64_t* recorded, int64_t* dropped) {
-  if (!g || g->t.m.empty()) return EKPNP_ERR_INVALID;
-  return ekpnp_hist_count(g->t.m[0], recorded, dropped);  // the slabs record in step
+  return team_series_count(g, ekpnp_hist_count, recorded, dropped);
 }
 extern "C" int ekpnp_group_hist_read(ekpnp_group* g, int64_t first, int count, int64_t* steps, double* times, int64_t* counts) {
   NEEDLIVEGROUP(g);
   const ekpnp_hist_spec* spec = hist_armed_spec(S(T, 0), nullptr, nullptr);
-  const size_t stride = spec ? (size_t)hist_cells(*spec) + 1 : 0;
-  std::vector<int64_t> v((size_t)(count > 0 ? count : 0) * stride);
-  bool head = true;
-  return team_monitor_each(T, [&](ekpnp_ctx* m) {
-    const int rc = ekpnp_hist_read(m, first, count, steps, times, v.data());
-    if (rc == EKPNP_OK && count > 0) {
-      for (size_t k = 0; k < v.size(); ++k) counts[k] = head ? v[k] : counts[k] + v[k];
-      head = false;
-    }
-    return rc;
-  });
+  std::vector<int64_t> v(series_rows(count) * (spec ? (size_t)hist_cells(*spec) + 1 : 0));
+  return team_series_read(T, count, [&](ekpnp_ctx* m) { return ekpnp_hist_read(m, first, count, steps, times, v.data()); },
+                          [&](const Ctx&, bool head) { rows_add(counts, v.data(), v.size(), head); });
 }
 extern "C" int ekpnp_group_hist_save(ekpnp_group* g, const char* path) {
   NEEDLIVEGROUP(g);
@@ -1850,28 +1850,20 @@ extern "C" int ekpnp_group_hist_save(ekpnp_group* g, const char* path) {
   int z_lo = 0, z_hi = 0;
   const ekpnp_hist_spec* spec = hist_armed_spec(S(T, 0), &z_lo, &z_hi);
   if (!spec) { T.err = "ekpnp_hist_save: no histogram was armed"; return EKPNP_ERR_INVALID; }
-  int64_t rec = 0, dropped = 0;
-  (void)ekpnp_group_hist_count(g, &rec, &dropped);
-  const int n = (int)(rec - dropped);
-  std::vector<int64_t> steps((size_t)n), counts((size_t)n * ((size_t)hist_cells(*spec) + 1));
-  std::vector<double> times((size_t)n);
-  if (int rc = ekpnp_group_hist_read(g, 0, n, steps.data(), times.data(), counts.data())) return rc;
-  return hist_write_file(path, S(T, 0).p, *spec, z_lo, z_hi, rec, dropped, n, steps.data(), times.data(), counts.data(), T.err);
+  return team_series_save<int64_t>(g, ekpnp_group_hist_count, (size_t)hist_cells(*spec) + 1,
+                                   [&](int n, int64_t* steps, double* times, int64_t* v) { return ekpnp_group_hist_read(g, 0, n, steps, times, v); },
+                                   [&](int64_t rec, int64_t dropped, int n, const int64_t* steps, const double* times, const int64_t* v) {
+                                     return hist_write_file(path, S(T, 0).p, *spec, z_lo, z_hi, rec, dropped, n, steps, times, v, T.err);
+                                   });
 }
 
-// ---- sections (section.hip) over the slabs: slabs are cut along z, so a plane's rows live on one slab; every slab reduces the
-// planes it owns on its own device and the host places the owner's rows (nothing is exchanged, nothing is added)
-static void section_place(const Ctx& c, const ekpnp_section_spec& spec, int nz, size_t samples, const double* part, double* whole) {
-  const size_t nv = (size_t)section_nvalues(spec), nkeep = (size_t)section_nkeep(c.p, spec);
-  const size_t np_part = spec.nplanes ? (size_t)spec.nplanes : (size_t)c.nzl, np_whole = spec.nplanes ? (size_t)spec.nplanes : (size_t)nz;
-  for (size_t r = 0; r < samples; ++r)
-    for (size_t v = 0; v < nv; ++v)
-      for (size_t j = 0; j < np_part; ++j) {
-        const int z = spec.nplanes ? spec.z[j] : c.z0 + (int)j;
-        if (z < c.z0 || z >= c.z0 + c.nzl) continue;  // (another slab's row)
-        const size_t row = spec.nplanes ? j : (size_t)z;
-        std::memcpy(whole + ((r * nv + v) * np_whole + row) * nkeep, part + ((r * nv + v) * np_part + j) * nkeep, nkeep * sizeof(double));
-      }
+// ---- sections (section.hip) over the slabs: every slab reduces the planes it owns on its own device and the host places the
+// owner's rows (nothing is exchanged, nothing is added)
+static inline size_t section_row(const ekpnp_params& p, const ekpnp_section_spec& s, int np) {
+  return (size_t)section_nvalues(s) * (size_t)np * (size_t)section_nkeep(p, s);
+}
+static void section_place(const Ctx& c, const ekpnp_section_spec& spec, size_t samples, const double* part, double* whole) {
+  rows_place(c, spec.nplanes, spec.z, samples * (size_t)section_nvalues(spec), (size_t)section_nkeep(c.p, spec), part, whole);
 }
 extern "C" int ekpnp_group_section(ekpnp_group* g, const ekpnp_section_spec* spec, double* host_out) {
   NEEDLIVEGROUP(g);
@@ -1879,13 +1871,12 @@ extern "C" int ekpnp_group_section(ekpnp_group* g, const ekpnp_section_spec* spe
   const ekpnp_params& p = S(T, 0).p;
   if (int rc = section_check_spec(p, spec, T.err)) return rc;  // refused before any slab has launched anything
   std::vector<double> part;
-  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) {
-    const Ctx& c = m->c;
-    part.resize((size_t)section_nvalues(*spec) * (size_t)(spec->nplanes ? spec->nplanes : c.nzl) * (size_t)section_nkeep(p, *spec));
+  return team_all(T, [&](ekpnp_ctx* m) {
+    part.resize(section_row(p, *spec, spec->nplanes ? spec->nplanes : m->c.nzl));
     const int rc = ekpnp_section(m, spec, part.data());
-    if (rc == EKPNP_OK) section_place(c, *spec, p.nz, 1, part.data(), host_out);
+    if (rc == EKPNP_OK) section_place(m->c, *spec, 1, part.data(), host_out);
     return rc;
-  }));
+  });
 }
 extern "C" int ekpnp_group_section_save(ekpnp_group* g, const ekpnp_section_spec* spec, const char* path, double time) {
   NEEDLIVEGROUP(g);
@@ -1893,7 +1884,7 @@ extern "C" int ekpnp_group_section_save(ekpnp_group* g, const ekpnp_section_spec
   const ekpnp_params& p = S(T, 0).p;
   if (int rc = section_check_spec(p, spec, T.err)) return rc;
   const int np = spec->nplanes ? spec->nplanes : p.nz;
-  std::vector<double> v((size_t)section_nvalues(*spec) * (size_t)np * (size_t)section_nkeep(p, *spec));
+  std::vector<double> v(section_row(p, *spec, np));
   if (int rc = ekpnp_group_section(g, spec, v.data())) return rc;
   std::vector<int> z((size_t)np);
   for (int j = 0; j < np; ++j) z[(size_t)j] = spec->nplanes ? spec->z[j] : j;
@@ -1903,45 +1894,33 @@ extern "C" int ekpnp_group_section_arm(ekpnp_group* g, const ekpnp_section_spec*
   NEEDLIVEGROUP(g);
   if (int rc = section_check_spec(S(T, 0).p, spec, T.err)) return rc;
   if (int rc = section_check_ring(*spec, capacity, T.err)) return rc;
-  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) { return ekpnp_section_arm(m, spec, capacity); }));
+  return team_all(T, [&](ekpnp_ctx* m) { return ekpnp_section_arm(m, spec, capacity); });
 }
-extern "C" int ekpnp_group_section_disarm(ekpnp_group* g) {
-  NEEDLIVEGROUP(g);
-  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) { return ekpnp_section_disarm(m); }));
-}
-// enqueues only, on every slab's compute stream (as ekpnp_group_stats_accumulate)
+extern "C" int ekpnp_group_section_disarm(ekpnp_group* g) { NEEDLIVEGROUP(g); return team_all(T, ekpnp_section_disarm); }
 extern "C" int ekpnp_group_section_record(ekpnp_group* g, int64_t step, double time) {
   NEEDLIVEGROUP(g);
-  if (!section_armed(S(T, 0))) { T.err = "ekpnp_section_record: no section armed"; return EKPNP_ERR_INVALID; }  // (refused before any slab is asked: the group stays usable)
-  return group_fail(T, team_monitor_each(T, [&](ekpnp_ctx* m) { return ekpnp_section_record(m, step, time); }));
+  return team_series_record(T, section_armed(S(T, 0)), "ekpnp_section_record: no section armed", ekpnp_section_record, step, time);
 }
 extern "C" int ekpnp_group_section_count(const ekpnp_group* g, int64_t* recorded, int64_t* dropped) {
-  if (!g || g->t.m.empty()) return EKPNP_ERR_INVALID;
-  return ekpnp_section_count(g->t.m[0], recorded, dropped);  // the slabs record in step
+  return team_series_count(g, ekpnp_section_count, recorded, dropped);
 }
 extern "C" int ekpnp_group_section_read(ekpnp_group* g, int64_t first, int count, int64_t* steps, double* times, double* values) {
   NEEDLIVEGROUP(g);
   const ekpnp_section_spec* spec = section_armed_spec(S(T, 0));
-  const size_t rows = (size_t)(count > 0 ? count : 0);
-  const size_t row = spec ? (size_t)section_nvalues(*spec) * (size_t)spec->nplanes * (size_t)section_nkeep(S(T, 0).p, *spec) : 0;
+  const size_t rows = series_rows(count);
   if (rows && !values) { T.err = "NULL pointer"; return EKPNP_ERR_INVALID; }
-  std::vector<double> part(rows * row);
-  return team_monitor_each(T, [&](ekpnp_ctx* m) {
-    const int rc = ekpnp_section_read(m, first, count, steps, times, part.data());
-    if (rc == EKPNP_OK && count > 0) section_place(m->c, *spec, S(T, 0).p.nz, rows, part.data(), values);
-    return rc;
-  });
+  std::vector<double> part(rows * (spec ? section_row(S(T, 0).p, *spec, spec->nplanes) : 0));
+  return team_series_read(T, count, [&](ekpnp_ctx* m) { return ekpnp_section_read(m, first, count, steps, times, part.data()); },
+                          [&](const Ctx& c, bool) { section_place(c, *spec, rows, part.data(), values); });
 }
 extern "C" int ekpnp_group_section_ring_save(ekpnp_group* g, const char* path) {
   NEEDLIVEGROUP(g);
   if (!path) { T.err = "NULL path"; return EKPNP_ERR_INVALID; }
   const ekpnp_section_spec* spec = section_armed_spec(S(T, 0));
   if (!spec) { T.err = "ekpnp_section_ring_save: no section was armed"; return EKPNP_ERR_INVALID; }
-  int64_t rec = 0, dropped = 0;
-  (void)ekpnp_group_section_count(g, &rec, &dropped);
-  const int n = (int)(rec - dropped);
-  std::vector<int64_t> steps((size_t)n);
-  std::vector<double> times((size_t)n), values((size_t)n * section_nvalues(*spec) * spec->nplanes * section_nkeep(S(T, 0).p, *spec));
-  if (int rc = ekpnp_group_section_read(g, 0, n, steps.data(), times.data(), values.data())) return rc;
-  return section_write_ring_file(path, S(T, 0).p, *spec, rec, dropped, n, steps.data(), times.data(), values.data(), T.err);
+  return team_series_save<double>(g, ekpnp_group_section_count, section_row(S(T, 0).p, *spec, spec->nplanes),
+                                  [&](int n, int64_t* steps, double* times, double* v) { return ekpnp_group_section_read(g, 0, n, steps, times, v); },
+                                  [&](int64_t rec, int64_t dropped, int n, const int64_t* steps, const double* times, const double* v) {
+                                    return section_write_ring_file(path, S(T, 0).p, *spec, rec, dropped, n, steps, times, v, T.err);
+                                  });
 }

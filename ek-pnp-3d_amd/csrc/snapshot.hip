@@ -167,23 +167,6 @@ int snapshot_write_field_header(FILE* f, int field_id) {
 
 }  // namespace ekpnp
 
-#define NEEDCTX(ctx)                    \
-  if (!(ctx)) return EKPNP_ERR_INVALID; \
-  Ctx& c = (ctx)->c
-#define HIPCHK(ctx, call)                                                  \
-  do {                                                                     \
-    hipError_t e_ = (call);                                                \
-    if (e_ != hipSuccess) {                                                \
-      (ctx).err = std::string(#call) + ": " + hipGetErrorString(e_);       \
-      return e_ == hipErrorOutOfMemory ? EKPNP_ERR_NOMEM : EKPNP_ERR_HIP;  \
-    }                                                                      \
-  } while (0)
-
-static int fail(Ctx& c, const char* msg) {
-  c.err = msg;
-  return EKPNP_ERR_INVALID;
-}
-
 // the side stream and the events, once per context and only when a snapshot is first asked for
 static int need_state(Ctx& c) {
   if (c.snap) return EKPNP_OK;

@@ -26,6 +26,7 @@
 
 #include "ekpnp_internal.h"
 #include "reduce.h"
+#include "ring.h"
 
 using namespace ekpnp;
 
@@ -211,22 +212,16 @@ struct SpecState {
   hipfftHandle plan = 0;
   bool have_plan = false;
   size_t plan_bytes = 0;         // the plan's work area
-  double* ring = nullptr;        // [capacity] rows of [nplanes][nshell] then [nplanes][3]
-  size_t ring_bytes = 0;
-  bool armed = false, ever_armed = false;
+  Ring ring;                     // rows of [nplanes][nshell] then [nplanes][3] doubles
   ekpnp_spectrum_spec spec_armed{};
-  int capacity = 0;
-  int64_t recorded = 0;
-  std::vector<int64_t> lab_step;  // the labels of the rows, [capacity], slot = row number % capacity
-  std::vector<double> lab_time;
-  ShellTable table;               // (kept while its upload may be in flight)
+  ShellTable table;              // (kept while its upload may be in flight)
 };
 
 static inline size_t spec_row_doubles(const SpecState& m, int rows) { return (size_t)rows * ((size_t)m.nshell + 3); }
 
-const ekpnp_spectrum_spec* spectrum_armed_spec(const Ctx& c) { return c.spectrum && c.spectrum->ever_armed ? &c.spectrum->spec_armed : nullptr; }
+const ekpnp_spectrum_spec* spectrum_armed_spec(const Ctx& c) { return c.spectrum && c.spectrum->ring.ever_armed ? &c.spectrum->spec_armed : nullptr; }
 
-bool spectrum_armed(const Ctx& c) { return c.spectrum && c.spectrum->armed; }
+bool spectrum_armed(const Ctx& c) { return c.spectrum && c.spectrum->ring.armed; }
 
 int spectrum_shell_count(const ekpnp_params& p, int* nshell, double* L, std::string& err) {
   ShellTable t;
@@ -240,7 +235,7 @@ void spectrum_release(Ctx& c) {
   if (!c.spectrum) return;
   if (c.spectrum->have_plan) hipfftDestroy(c.spectrum->plan);
   if (c.spectrum->buf) (void)hipFree(c.spectrum->buf);
-  if (c.spectrum->ring) (void)hipFree(c.spectrum->ring);
+  ring_release(c.spectrum->ring);
   delete c.spectrum;
   c.spectrum = nullptr;
 }
@@ -277,23 +272,6 @@ int spectrum_write_file(const char* path, const ekpnp_params& p, const ekpnp_spe
 }
 
 }  // namespace ekpnp
-
-#define NEEDCTX(ctx)                    \
-  if (!(ctx)) return EKPNP_ERR_INVALID; \
-  Ctx& c = (ctx)->c
-#define HIPCHK(ctx, call)                                                  \
-  do {                                                                     \
-    hipError_t e_ = (call);                                                \
-    if (e_ != hipSuccess) {                                                \
-      (ctx).err = std::string(#call) + ": " + hipGetErrorString(e_);       \
-      return e_ == hipErrorOutOfMemory ? EKPNP_ERR_NOMEM : EKPNP_ERR_HIP;  \
-    }                                                                      \
-  } while (0)
-
-static int fail(Ctx& c, const char* msg) {
-  c.err = msg;
-  return EKPNP_ERR_INVALID;
-}
 
 static inline size_t even(size_t n) { return (n + 1) & ~(size_t)1; }
 
@@ -492,87 +470,45 @@ extern "C" int ekpnp_spectrum_arm(ekpnp_ctx* ctx, const ekpnp_spectrum_spec* spe
   if (capacity < 1) { c.err = "spectrum: capacity = " + std::to_string(capacity) + " (must be >= 1)"; return EKPNP_ERR_INVALID; }
   if (int rc = need_spectrum(c)) return rc;
   SpecState& m = *c.spectrum;
-  m.armed = false;
-  HIPCHK(c, hipStreamSynchronize(c.stream));  // rows of an earlier arm may still be on their way into the ring
-  const size_t bytes = (size_t)capacity * spec_row_doubles(m, spec->nplanes) * sizeof(double);
-  if (!m.ring || m.ring_bytes != bytes) {
-    if (m.ring) {
-      (void)hipFree(m.ring);
-      c.bytes -= m.ring_bytes;
-      m.ring = nullptr;
-      m.ring_bytes = 0;
-    }
-    HIPCHK(c, hipMalloc((void**)&m.ring, bytes));
-    m.ring_bytes = bytes;
-    c.bytes += bytes;
-  }
-  HIPCHK(c, hipMemsetAsync(m.ring, 0, bytes, c.stream));
   m.spec_armed = *spec;
-  m.capacity = capacity;
-  m.recorded = 0;
-  m.lab_step.assign((size_t)capacity, 0);
-  m.lab_time.assign((size_t)capacity, 0.0);
-  m.armed = true;
-  m.ever_armed = true;
-  return EKPNP_OK;
+  return ring_arm(c, m.ring, capacity, spec_row_doubles(m, spec->nplanes) * sizeof(double));
 }
 
 extern "C" int ekpnp_spectrum_disarm(ekpnp_ctx* ctx) {
   NEEDCTX(ctx);
-  if (c.spectrum) c.spectrum->armed = false;  // the ring and its rows stay readable until the next arm
+  if (c.spectrum) c.spectrum->ring.armed = false;  // the ring and its rows stay readable until the next arm
   return EKPNP_OK;
 }
 
 extern "C" int ekpnp_spectrum_record(ekpnp_ctx* ctx, int64_t step, double time) {
   NEEDCTX(ctx);
-  if (!c.spectrum || !c.spectrum->armed) return fail(c, "ekpnp_spectrum_record: no spectrum tracking armed");
+  if (!c.spectrum || !c.spectrum->ring.armed) return fail(c, "ekpnp_spectrum_record: no spectrum tracking armed");
   SpecState& m = *c.spectrum;
   std::vector<int> zl, rows;
   int nrows = 0;
   const int n = spectrum_held(c, m.spec_armed, zl, rows, &nrows);
-  const size_t slot = (size_t)(m.recorded % m.capacity);
-  if (int rc = spectrum_enqueue(c, m.spec_armed.field_id, zl.data(), rows.data(), n, nrows, m.ring + slot * spec_row_doubles(m, nrows))) return rc;
-  m.lab_step[slot] = step;
-  m.lab_time[slot] = time;
-  ++m.recorded;
+  if (int rc = spectrum_enqueue(c, m.spec_armed.field_id, zl.data(), rows.data(), n, nrows, (double*)ring_next_row(m.ring))) return rc;
+  ring_note_row(m.ring, step, time);
   return EKPNP_OK;
 }
 
 extern "C" int ekpnp_spectrum_count(const ekpnp_ctx* ctx, int64_t* recorded, int64_t* dropped) {
   if (!ctx) return EKPNP_ERR_INVALID;
-  const SpecState* m = ctx->c.spectrum;
-  const int64_t rec = m && m->ring ? m->recorded : 0;
-  const int64_t held = m && m->ring && rec > m->capacity ? m->capacity : rec;
-  if (recorded) *recorded = rec;
-  if (dropped) *dropped = rec - held;
+  ring_count(ctx->c.spectrum ? &ctx->c.spectrum->ring : nullptr, recorded, dropped);
   return EKPNP_OK;
 }
 
 extern "C" int ekpnp_spectrum_read(ekpnp_ctx* ctx, int64_t first, int count, int64_t* steps, double* times, double* shells, double* peaks) {
   NEEDCTX(ctx);
-  int64_t rec = 0, dropped = 0;
-  (void)ekpnp_spectrum_count(ctx, &rec, &dropped);
-  const int64_t held = rec - dropped;
-  if (first < 0 || count < 0 || first + (int64_t)count > held) {
-    c.err = "ekpnp_spectrum_read: rows " + std::to_string(first) + " .. " + std::to_string(first + (int64_t)count - 1) + " asked for, " + std::to_string(held) +
-            " held";
-    return EKPNP_ERR_INVALID;
-  }
-  if (count == 0) return EKPNP_OK;
-  if (!steps || !times || !shells) return fail(c, "NULL pointer");
-  SpecState& m = *c.spectrum;
-  const int np = m.spec_armed.nplanes;
-  const size_t rowd = spec_row_doubles(m, np), nsh = (size_t)np * m.nshell;
-  std::vector<double> row(rowd);
-  HIPCHK(c, hipStreamSynchronize(c.stream));
-  const int64_t seq0 = dropped + first;
-  for (int k = 0; k < count; ++k) {
-    const size_t slot = (size_t)((seq0 + k) % m.capacity);
-    HIPCHK(c, hipMemcpy(row.data(), m.ring + slot * rowd, rowd * sizeof(double), hipMemcpyDeviceToHost));
-    std::memcpy(shells + (size_t)k * nsh, row.data(), nsh * sizeof(double));
-    if (peaks) std::memcpy(peaks + (size_t)k * np * 3, row.data() + nsh, (size_t)np * 3 * sizeof(double));
-    steps[k] = m.lab_step[slot];
-    times[k] = m.lab_time[slot];
+  const SpecState* m = c.spectrum;
+  const int np = m ? m->spec_armed.nplanes : 0;
+  const size_t rowd = m ? spec_row_doubles(*m, np) : 0, nsh = m ? (size_t)np * m->nshell : 0;
+  std::vector<double> rows(m && count > 0 && count <= m->ring.capacity ? (size_t)count * rowd : 0);  // (a count no ring can hold is refused below)
+  if (int rc = ring_read(c, m ? &m->ring : nullptr, "ekpnp_spectrum_read", first, count, steps, times, shells ? rows.data() : nullptr)) return rc;
+  for (int k = 0; k < count; ++k) {  // a row is [shells | peaks]
+    const double* row = rows.data() + (size_t)k * rowd;
+    std::memcpy(shells + (size_t)k * nsh, row, nsh * sizeof(double));
+    if (peaks) std::memcpy(peaks + (size_t)k * np * 3, row + nsh, (size_t)np * 3 * sizeof(double));
   }
   return EKPNP_OK;
 }

@@ -135,23 +135,6 @@ int stats_write_file(const char* path, const ekpnp_params& p, int z0, int nzl, i
 
 }  // namespace ekpnp
 
-#define NEEDCTX(ctx)                    \
-  if (!(ctx)) return EKPNP_ERR_INVALID; \
-  Ctx& c = (ctx)->c
-#define HIPCHK(ctx, call)                                                  \
-  do {                                                                     \
-    hipError_t e_ = (call);                                                \
-    if (e_ != hipSuccess) {                                                \
-      (ctx).err = std::string(#call) + ": " + hipGetErrorString(e_);       \
-      return e_ == hipErrorOutOfMemory ? EKPNP_ERR_NOMEM : EKPNP_ERR_HIP;  \
-    }                                                                      \
-  } while (0)
-
-static int fail(Ctx& c, const char* msg) {
-  c.err = msg;
-  return EKPNP_ERR_INVALID;
-}
-
 static inline size_t stats_entries(const Ctx& c) { return (size_t)NP * (size_t)c.nzl; }
 
 // the three arrays, once: [partials | sums of the last pass | running sums]

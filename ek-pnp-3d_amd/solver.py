@@ -90,14 +90,6 @@ def monitor_spec_check(quantities=None, every: int = 1, capacity: int = 1) -> Mo
     return spec
 
 
-def _monitor_read(L, fn, handle, ck, first: int, count: int):
-    steps = np.zeros(max(count, 0), dtype=np.int64)
-    times = np.zeros(max(count, 0), dtype=np.float64)
-    values = np.zeros((max(count, 0), len(MONITOR_NAMES)), dtype=np.float64)
-    ck(fn(handle, int(first), int(count), steps.ctypes.data_as(C.c_void_p), times.ctypes.data_as(C.c_void_p), values.ctypes.data_as(C.c_void_p)))
-    return steps, times, values
-
-
 SEED_PATTERNS = {"none": 0, "noise": 0, "rolls": 1, "squares": 2, "hexagons": 3}  # include/ekpnp.h: EKPNP_SEED_*
 MAX_MODES = 16
 
@@ -182,14 +174,6 @@ def seed_host(p: "Params", spec: SeedSpec, field, planes, z0: int = 0) -> np.nda
     return a
 
 
-def _modes_read(L, fn, handle, ck, nmodes: int, first: int, count: int):
-    steps = np.zeros(max(count, 0), dtype=np.int64)
-    times = np.zeros(max(count, 0), dtype=np.float64)
-    values = np.zeros((max(count, 0), nmodes), dtype=np.float64)
-    ck(fn(handle, int(first), int(count), steps.ctypes.data_as(C.c_void_p), times.ctypes.data_as(C.c_void_p), values.ctypes.data_as(C.c_void_p)))
-    return steps, times, values
-
-
 MAX_SPECTRUM_PLANES = 16
 
 
@@ -237,16 +221,6 @@ def spectrum_shells(p: "Params"):
     if rc:
         raise EkpnpError(f"ekpnp_spectrum_shells -> status {rc}: {L.ekpnp_last_error(None).decode()}")
     return shell_of, count
-
-
-def _spectrum_read(L, fn, handle, ck, nplanes: int, nshell: int, first: int, count: int):
-    steps = np.zeros(max(count, 0), dtype=np.int64)
-    times = np.zeros(max(count, 0), dtype=np.float64)
-    shells = np.zeros((max(count, 0), nplanes, nshell), dtype=np.float64)
-    peaks = np.zeros((max(count, 0), nplanes, 3), dtype=np.float64)
-    ck(fn(handle, int(first), int(count), steps.ctypes.data_as(C.c_void_p), times.ctypes.data_as(C.c_void_p), shells.ctypes.data_as(C.c_void_p),
-          peaks.ctypes.data_as(C.c_void_p)))
-    return steps, times, shells, peaks
 
 
 HIST_Q = 11  # include/ekpnp.h: EKPNP_HIST_Q, the charge density c - cn as a histogram value
@@ -323,16 +297,6 @@ def hist_edges(axis) -> np.ndarray:
     """the n + 1 edges lo + k (hi - lo) / n of an axis, FOR PLOTTING ONLY: hist_bin is the definition of a bin"""
     ax = _hist_axis(axis)
     return ax.lo + np.arange(ax.n + 1, dtype=np.float64) * (ax.hi - ax.lo) / ax.n
-
-
-def _hist_read(L, fn, handle, ck, spec, first: int, count: int):
-    cells = spec.cells if spec is not None else 0
-    steps = np.zeros(max(count, 0), dtype=np.int64)
-    times = np.zeros(max(count, 0), dtype=np.float64)
-    rows = np.zeros((max(count, 0), cells + 1), dtype=np.int64)
-    ck(fn(handle, int(first), int(count), steps.ctypes.data_as(C.c_void_p), times.ctypes.data_as(C.c_void_p), rows.ctypes.data_as(C.c_void_p)))
-    shape = spec.cell_shape if spec is not None else (0,)
-    return steps, times, rows[:, :cells].reshape((len(steps),) + shape).copy(), rows[:, cells].copy()
 
 
 SECTION_Q = 11  # include/ekpnp.h: EKPNP_SECTION_Q, the charge density c - cn as a section value
@@ -419,63 +383,293 @@ def _section_spec_for(p: "Params", values, across, range, planes) -> SectionSpec
     return section_spec(values, a, range, planes, n=p.nx if a == ACROSS_X else p.ny)
 
 
-def _section_read(fn, handle, ck, spec, nkeep: int, first: int, count: int):
-    nv, npl = (len(spec.names), spec.nplanes) if spec is not None else (0, 0)
-    steps = np.zeros(max(count, 0), dtype=np.int64)
-    times = np.zeros(max(count, 0), dtype=np.float64)
-    values = np.zeros((max(count, 0), nv, npl, nkeep), dtype=np.float64)
-    ck(fn(handle, int(first), int(count), steps.ctypes.data_as(C.c_void_p), times.ctypes.data_as(C.c_void_p), values.ctypes.data_as(C.c_void_p)))
-    return steps, times, values
+def _ptr(a):
+    return a.ctypes.data_as(C.c_void_p)
 
 
-class _Sections:
-    """The section methods of Solver and Group (section.hip): the same calls on a context (ekpnp_section*) and on a group
-    (ekpnp_group_section*), whose rows are the owning slab's."""
+class _Diagnostics:
+    """The diagnostic methods Solver and Group share (stats.hip, snapshot.hip, monitor.hip, seed.hip, modes.hip, spectrum.hip, hist.hip,
+    section.hip): the same calls on a context (ekpnp_*) and on a group (ekpnp_group_*).  The class supplies the prefix (_PREFIX), the
+    handle (_handle) and the planes of a per-plane result (_planes: nz_local of a Solver, its own planes; the lattice's nz of a Group,
+    where every slab works on its own planes on its own device and the host adds or places the slabs' rows)."""
 
-    def _section_fn(self, verb: str):
-        group = hasattr(self, "_g")
-        return getattr(self._L, ("ekpnp_group_section" if group else "ekpnp_section") + verb), (self._g if group else self._h)
+    def _call(self, name: str, *args):
+        self._ck(getattr(self._L, self._PREFIX + name)(self._handle, *args))
 
+    def _count(self, name: str):
+        r, d = C.c_int64(), C.c_int64()
+        self._call(name, C.byref(r), C.byref(d))
+        return int(r.value), int(d.value)
+
+    def _read(self, name: str, first: int, count: int, *rows):
+        """labels + typed row arrays: (steps, times, one array [count, *shape] of dtype per (shape, dtype) in rows)"""
+        n = max(count, 0)
+        steps, times = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.float64)
+        out = [np.zeros((n,) + tuple(shape), dtype=dtype) for shape, dtype in rows]
+        self._call(name, int(first), int(count), _ptr(steps), _ptr(times), *[_ptr(a) for a in out])
+        return (steps, times, *out)
+
+    # -- plane profiles and running statistics (no reference counterpart) --------------------
+    def plane_sums(self) -> np.ndarray:
+        """[len(PROFILE_NAMES)][planes]: sums over the nx*ny nodes of each plane of the current fields, their squares and the flux /
+        body-force products, reduced on the device (a mean is a sum / (nx*ny)).  planes: nz_local of a Solver, its owned planes; NZ of a
+        Group, where every slab reduces its own planes on its own device."""
+        out = np.empty((len(PROFILE_NAMES), self._planes), dtype=np.float64)
+        self._call("plane_sums", _ptr(out))
+        return out
+
+    def stats_reset(self):
+        self._call("stats_reset")
+
+    def stats_accumulate(self):
+        """running sums += plane sums of the current fields; enqueues only (place it between two step() calls)"""
+        self._call("stats_accumulate")
+
+    def stats_get(self):
+        """(running sums [len(PROFILE_NAMES)][planes], number of samples)"""
+        out, n = np.empty((len(PROFILE_NAMES), self._planes), dtype=np.float64), C.c_int()
+        self._call("stats_get", _ptr(out), C.byref(n))
+        return out, n.value
+
+    def save_profiles(self, path: str, time: float = 0.0):
+        """text file of the time-averaged plane means of the planes (ekpnp_save_profiles / ekpnp_group_save_profiles)"""
+        self._call("save_profiles", os.fsencode(path), float(time))
+
+    # -- coarsened FP32 snapshots written while the run continues (snapshot() itself differs: Solver, Group) --
+    def snapshot_begin(self, path: str, fields=None, coarsen=(1, 1, 1), time: float = 0.0):
+        """enqueue a snapshot for the legacy VTK file `path` and return at once (place it between two step() calls);
+        snapshot_finish() writes the file.  At most two are pending: a third begin first finishes the oldest."""
+        spec = snapshot_spec(fields, coarsen)
+        self._call("snapshot_begin", C.byref(spec), os.fsencode(path), float(time))
+
+    def snapshot_finish(self):
+        """wait for the copies of the pending snapshots (not for the compute stream) and write their files"""
+        self._call("snapshot_finish")
+
+    @property
+    def snapshot_pending(self) -> int:
+        return int(getattr(self._L, self._PREFIX + "snapshot_pending")(self._handle))
+
+    # -- per-step scalar time series kept on the device (no reference counterpart) --------------
+    def monitor_sample(self, quantities=None) -> np.ndarray:
+        """the len(MONITOR_NAMES) scalars of the current fields, now (ekpnp_monitor_sample / ekpnp_group_monitor_sample: complete on
+        return; columns that are not selected hold 0.0).  Needs no armed monitor and does not touch the ring."""
+        out = np.zeros(len(MONITOR_NAMES), dtype=np.float64)
+        self._call("monitor_sample", monitor_mask(quantities), _ptr(out))
+        return out
+
+    def monitor_arm(self, quantities=None, every: int = 1, capacity: int = 1024):
+        """from now on step() appends a row to a ring of `capacity` rows in device memory after every `every`-th step:
+        enqueued only, nothing waits.  Arming again resets the ring and the step count."""
+        spec = MonitorSpec(monitor_mask(quantities), int(every), int(capacity))
+        self._call("monitor_arm", C.byref(spec))
+
+    def monitor_disarm(self):
+        self._call("monitor_disarm")
+
+    def monitor_record(self, step: int, time: float):
+        """append a row with the caller's labels (hosts that drive stream_collide_save / fast_Poisson themselves); enqueues only"""
+        self._call("monitor_record", int(step), float(time))
+
+    def monitor_count(self):
+        """(rows recorded since arming, rows lost to overflow); host-known, never synchronises"""
+        return self._count("monitor_count")
+
+    def monitor_read(self, first: int = 0, count: int = None):
+        """(steps[n], times[n], values[n][len(MONITOR_NAMES)]) of the rows still held, oldest first; count None: all from `first` on"""
+        if count is None:
+            r, d = self.monitor_count()
+            count = r - d - first
+        return self._read("monitor_read", first, count, ((len(MONITOR_NAMES),), np.float64))
+
+    def monitor_save(self, path: str):
+        self._call("monitor_save", os.fsencode(path))
+
+    # -- seeding x-y structure and tracking chosen x-y modes (no reference counterpart) -----------
+    def seed(self, spec: SeedSpec = None, **kw):
+        """add a pattern and / or reproducible noise to the selected field arrays on the device (ekpnp_seed / ekpnp_group_seed: enqueues
+        only, no field moves; the bits of get_field, seed_host, set_field).  Then fast_Poisson() and init_equilibrium().  spec, or the
+        keywords of seed_spec()."""
+        spec = spec if spec is not None else seed_spec(**kw)
+        self._call("seed", C.byref(spec))
+
+    def mode_amplitudes(self, field="uz", modes=((1, 1),)) -> np.ndarray:
+        """[nmodes][planes][2]: per plane (self.nz_local of a Solver, self.p.nz of a Group) a = sum v cos(theta), b = sum v sin(theta),
+        theta = 2 pi (m x/nx + n y/ny), unnormalised (ekpnp_mode_amplitudes / ekpnp_group_mode_amplitudes; complete on return).  field may
+        be a ModesSpec."""
+        spec = _as_modes_spec(field, modes)
+        out = np.zeros((max(spec.nmodes, 0), self._planes, 2), dtype=np.float64)
+        self._call("mode_amplitudes", C.byref(spec), _ptr(out))
+        return out
+
+    def modes_arm(self, field="uz", modes=((1, 1),), capacity: int = 1024):
+        """track the energies E = sum_z (a^2 + b^2) of the modes in a ring of `capacity` rows in device memory; rows are appended by
+        modes_record() only"""
+        spec = _as_modes_spec(field, modes)
+        self._call("modes_arm", C.byref(spec), int(capacity))
+        self._modes_n = spec.nmodes
+
+    def modes_disarm(self):
+        self._call("modes_disarm")
+
+    def modes_record(self, step: int, time: float):
+        """append a row with the caller's labels; enqueues only (place it between two step() calls)"""
+        self._call("modes_record", int(step), float(time))
+
+    def modes_count(self):
+        """(rows recorded since arming, rows lost to overflow); host-known, never synchronises"""
+        return self._count("modes_count")
+
+    def modes_read(self, first: int = 0, count: int = None):
+        """(steps[n], times[n], energies[n][nmodes]) of the rows still held, oldest first; count None: all from `first` on"""
+        if count is None:
+            r, d = self.modes_count()
+            count = r - d - first
+        return self._read("modes_read", first, count, ((getattr(self, "_modes_n", 0),), np.float64))
+
+    def modes_save(self, path: str):
+        self._call("modes_save", os.fsencode(path))
+
+    # -- x-y power spectra per plane: shells, peak and their time series (no reference counterpart) --
+    def spectrum_shells(self):
+        """(shell_of[ny][nx/2 + 1], count[nshell]) of this lattice: the library's own binning (ekpnp_spectrum_shells, host only)"""
+        return spectrum_shells(self.p)
+
+    def spectrum_plane(self, field, z: int) -> np.ndarray:
+        """P[ny][nx/2 + 1] of the global plane z in rfft2's layout: w (re^2 + im^2), w = 1 for m = 0 and the even Nyquist column, 2
+        otherwise, unnormalised (ekpnp_spectrum_plane / ekpnp_group_spectrum_plane; complete on return)"""
+        fid = FIELD_ID[field] if isinstance(field, str) else int(field)
+        out = np.zeros((self.p.ny, self.p.nx // 2 + 1), dtype=np.float64)
+        self._call("spectrum_plane", fid, int(z), _ptr(out))
+        return out
+
+    def spectrum(self, field="uz", planes=None):
+        """(shells[np][nshell], peaks[np][3]): per plane the shell spectrum E(s) and the dominant mode (m, n signed, P); planes None:
+        every plane (self.nz_local of a Solver, self.p.nz of a Group), else the chosen global z (ekpnp_spectrum / ekpnp_group_spectrum;
+        complete on return).  field may be a SpectrumSpec."""
+        spec = _as_spectrum_spec(field, planes)
+        rows = spec.nplanes if spec.nplanes else self._planes
+        nshell = self._spectrum_nshell = getattr(self, "_spectrum_nshell", None) or len(self.spectrum_shells()[1])
+        shells = np.zeros((max(rows, 0), nshell), dtype=np.float64)
+        peaks = np.zeros((max(rows, 0), 3), dtype=np.float64)
+        self._call("spectrum", C.byref(spec), _ptr(shells), _ptr(peaks))
+        return shells, peaks
+
+    def spectrum_arm(self, field="uz", planes=(0,), capacity: int = 1024):
+        """track shells and peak of the chosen planes in a ring of `capacity` rows in device memory; rows are appended by
+        spectrum_record() only"""
+        spec = _as_spectrum_spec(field, planes)
+        self._call("spectrum_arm", C.byref(spec), int(capacity))
+        self._spectrum_np = spec.nplanes
+        self._spectrum_nshell = len(self.spectrum_shells()[1])
+
+    def spectrum_disarm(self):
+        self._call("spectrum_disarm")
+
+    def spectrum_record(self, step: int, time: float):
+        """enqueue one row labelled (step, time): nothing waits, the step graph is left alone"""
+        self._call("spectrum_record", int(step), float(time))
+
+    def spectrum_count(self):
+        """(recorded, dropped); host-known, never synchronises"""
+        return self._count("spectrum_count")
+
+    def spectrum_read(self, first: int = 0, count: int = None):
+        """(steps[n], times[n], shells[n][nplanes][nshell], peaks[n][nplanes][3]) of the rows still held, oldest first; count None: all
+        from `first` on"""
+        if count is None:
+            r, d = self.spectrum_count()
+            count = max(r - d - first, 0)
+        nplanes = getattr(self, "_spectrum_np", 0)
+        return self._read("spectrum_read", first, count, ((nplanes, getattr(self, "_spectrum_nshell", 0)), np.float64), ((nplanes, 3), np.float64))
+
+    def spectrum_save(self, path: str):
+        self._call("spectrum_save", os.fsencode(path))
+
+    # ---- histograms, value ranges and their time series (hist.hip) ----
+    def hist_planes(self, a, b=None):
+        """(counts[planes, a.n + 2(, b.n + 2)] int64, nonfinite[planes] int64) of every plane (nz_local of a Solver, its owned planes; nz of
+        a Group, the lattice's): cell 0 is the underflow, n + 1 the overflow, a node with a NaN in either value goes to nonfinite and to no
+        cell (ekpnp_hist_planes / ekpnp_group_hist_planes; complete on return).  a may be a HistSpec."""
+        spec = _as_hist_spec(a, b)
+        counts = np.zeros((self._planes,) + spec.cell_shape, dtype=np.int64)
+        nonfinite = np.zeros(self._planes, dtype=np.int64)
+        self._call("hist_planes", C.byref(spec), _ptr(counts), _ptr(nonfinite))
+        return counts, nonfinite
+
+    def value_range(self, value):
+        """(vmin[planes], vmax[planes]): per plane (as hist_planes) the smallest and largest value that is not NaN (+Inf, -Inf for a plane
+        of NaNs); value: a field or "q" (ekpnp_value_range / ekpnp_group_value_range; complete on return)"""
+        vid = HIST_VALUE_ID[value] if isinstance(value, str) else int(value)
+        vmin, vmax = np.zeros(self._planes, dtype=np.float64), np.zeros(self._planes, dtype=np.float64)
+        self._call("value_range", vid, _ptr(vmin), _ptr(vmax))
+        return vmin, vmax
+
+    def hist_arm(self, a, b=None, planes=None, capacity: int = 1024):
+        """allocate the ring; a row is ONE histogram summed over the global planes planes = (z_lo, z_hi) inclusive (None: the interior
+        1 .. nz - 2); from then on rows are appended by hist_record() only"""
+        spec = _as_hist_spec(a, b)
+        z_lo, z_hi = (1, self.p.nz - 2) if planes is None else (int(planes[0]), int(planes[1]))
+        self._call("hist_arm", C.byref(spec), z_lo, z_hi, int(capacity))
+        self._hist_spec = spec
+
+    def hist_disarm(self):
+        self._call("hist_disarm")
+
+    def hist_record(self, step: int, time: float):
+        """append a row labelled (step, time) (enqueues only)"""
+        self._call("hist_record", int(step), float(time))
+
+    def hist_count(self):
+        """(rows recorded since the arm, rows dropped because the ring was full); never synchronises"""
+        return self._count("hist_count")
+
+    def hist_read(self, first: int = 0, count: int = None):
+        """(steps, times, counts[count, a.n + 2(, b.n + 2)], nonfinite[count]) of the rows still held, oldest first"""
+        if count is None:
+            r, d = self.hist_count()
+            count = max(r - d - first, 0)
+        spec = getattr(self, "_hist_spec", None)
+        cells, shape = (spec.cells, spec.cell_shape) if spec is not None else (0, (0,))
+        steps, times, rows = self._read("hist_read", first, count, ((cells + 1,), np.int64))
+        return steps, times, rows[:, :cells].reshape((len(steps),) + shape).copy(), rows[:, cells].copy()
+
+    def hist_save(self, path: str):
+        self._call("hist_save", os.fsencode(path))
+
+    # ---- sections and their time series (section.hip); a group's rows are the owning slab's ----
     def section(self, values=None, across="x", range=None, planes=None):
         """[nvalues, np, nkeep] float64: every selected value (None: all twelve of SECTION_VALUES, in that order) summed along the axis
         `across` ("x" keeps y, "y" keeps x) over the inclusive index range (None: the whole axis; lo == hi: a cut), per plane - np = the
         chosen global planes, or every plane held when planes is None.  Unnormalised; every entry is section_sum of its line
         (ekpnp_section; complete on return).  values may be a SectionSpec."""
         spec = _section_spec_for(self.p, values, across, range, planes)
-        rows = spec.nplanes if spec.nplanes else (self.p.nz if hasattr(self, "_g") else self.nz_local)
+        rows = spec.nplanes if spec.nplanes else self._planes
         out = np.zeros((len(spec.names), max(rows, 0), self.p.ny if spec.across == ACROSS_X else self.p.nx), dtype=np.float64)
-        fn, h = self._section_fn("")
-        self._ck(fn(h, C.byref(spec), out.ctypes.data_as(C.c_void_p)))
+        self._call("section", C.byref(spec), _ptr(out))
         return out
 
     def section_write(self, path: str, values=None, across="x", range=None, planes=None, time: float = 0.0):
         """the same map as text: a header line, then one row "name z v ..." per value and plane (ekpnp_section_save)"""
         spec = _section_spec_for(self.p, values, across, range, planes)
-        fn, h = self._section_fn("_save")
-        self._ck(fn(h, C.byref(spec), os.fsencode(path), float(time)))
+        self._call("section_save", C.byref(spec), os.fsencode(path), float(time))
 
     def section_arm(self, values=None, across="x", range=None, planes=(0,), capacity: int = 1024):
         """allocate the ring of rows [nvalues, nplanes, nkeep] for 1 .. 16 chosen planes; rows are appended by section_record() only"""
         spec = _section_spec_for(self.p, values, across, range, planes)
-        fn, h = self._section_fn("_arm")
-        self._ck(fn(h, C.byref(spec), int(capacity)))
+        self._call("section_arm", C.byref(spec), int(capacity))
         self._section_spec = spec
 
     def section_disarm(self):
-        fn, h = self._section_fn("_disarm")
-        self._ck(fn(h))
+        self._call("section_disarm")
 
     def section_record(self, step: int, time: float):
         """append a row labelled (step, time) (enqueues only)"""
-        fn, h = self._section_fn("_record")
-        self._ck(fn(h, int(step), float(time)))
+        self._call("section_record", int(step), float(time))
 
     def section_count(self):
         """(rows recorded since the arm, rows dropped because the ring was full); never synchronises"""
-        r, d = C.c_int64(), C.c_int64()
-        fn, h = self._section_fn("_count")
-        self._ck(fn(h, C.byref(r), C.byref(d)))
-        return r.value, d.value
+        return self._count("section_count")
 
     def section_read(self, first: int = 0, count: int = None):
         """(steps, times, values[count, nvalues, nplanes, nkeep]) of the rows still held, oldest first"""
@@ -483,14 +677,12 @@ class _Sections:
             r, d = self.section_count()
             count = max(r - d - first, 0)
         spec = getattr(self, "_section_spec", None)
-        nkeep = 0 if spec is None else (self.p.ny if spec.across == ACROSS_X else self.p.nx)
-        fn, h = self._section_fn("_read")
-        return _section_read(fn, h, self._ck, spec, nkeep, first, count)
+        shape = (0, 0, 0) if spec is None else (len(spec.names), spec.nplanes, self.p.ny if spec.across == ACROSS_X else self.p.nx)
+        return self._read("section_read", first, count, (shape, np.float64))
 
     def section_save(self, path: str):
         """the ring as text: a header line, then one row "step time name z v ..." per held sample, value and plane (ekpnp_section_ring_save)"""
-        fn, h = self._section_fn("_ring_save")
-        self._ck(fn(h, os.fsencode(path)))
+        self._call("section_ring_save", os.fsencode(path))
 
 
 def _snapshot_names(spec: SnapshotSpec) -> list:
@@ -648,127 +840,56 @@ def load_library():
         "ekpnp_group_read_data": (i32, [ctx, C.c_char_p, pd]),
         "ekpnp_group_save_state": (i32, [ctx, C.c_char_p, dbl]),
         "ekpnp_group_read_state": (i32, [ctx, C.c_char_p, pd]),
-        # plane profiles and running statistics
-        "ekpnp_plane_sums": (i32, [ctx, C.c_void_p]),
-        "ekpnp_stats_reset": (i32, [ctx]),
-        "ekpnp_stats_accumulate": (i32, [ctx]),
-        "ekpnp_stats_get": (i32, [ctx, C.c_void_p, C.POINTER(i32)]),
-        "ekpnp_save_profiles": (i32, [ctx, C.c_char_p, dbl]),
-        "ekpnp_group_plane_sums": (i32, [ctx, C.c_void_p]),
-        "ekpnp_group_stats_reset": (i32, [ctx]),
-        "ekpnp_group_stats_accumulate": (i32, [ctx]),
-        "ekpnp_group_stats_get": (i32, [ctx, C.c_void_p, C.POINTER(i32)]),
-        "ekpnp_group_save_profiles": (i32, [ctx, C.c_char_p, dbl]),
-        # coarsened FP32 snapshots
+        # coarsened FP32 snapshots (a context's read also returns its planes)
         "ekpnp_snapshot_extent": (i32, [C.POINTER(Params), C.POINTER(SnapshotSpec), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(sz)]),
         "ekpnp_snapshot_read": (i32, [ctx, C.POINTER(SnapshotSpec), C.c_void_p, C.POINTER(i32), C.POINTER(i32)]),
-        "ekpnp_snapshot_begin": (i32, [ctx, C.POINTER(SnapshotSpec), C.c_char_p, dbl]),
-        "ekpnp_snapshot_finish": (i32, [ctx]),
-        "ekpnp_snapshot_pending": (i32, [ctx]),
         "ekpnp_group_snapshot_read": (i32, [ctx, C.POINTER(SnapshotSpec), C.c_void_p]),
-        "ekpnp_group_snapshot_begin": (i32, [ctx, C.POINTER(SnapshotSpec), C.c_char_p, dbl]),
-        "ekpnp_group_snapshot_finish": (i32, [ctx]),
-        "ekpnp_group_snapshot_pending": (i32, [ctx]),
-        # per-step scalar time series
+        # host arithmetic of the diagnostics
         "ekpnp_monitor_name": (C.c_char_p, [i32]),
         "ekpnp_monitor_spec_check": (i32, [C.POINTER(MonitorSpec)]),
-        "ekpnp_monitor_sample": (i32, [ctx, C.c_uint32, C.c_void_p]),
-        "ekpnp_monitor_arm": (i32, [ctx, C.POINTER(MonitorSpec)]),
-        "ekpnp_monitor_disarm": (i32, [ctx]),
-        "ekpnp_monitor_record": (i32, [ctx, C.c_int64, dbl]),
-        "ekpnp_monitor_count": (i32, [ctx, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
-        "ekpnp_monitor_read": (i32, [ctx, C.c_int64, i32, C.c_void_p, C.c_void_p, C.c_void_p]),
-        "ekpnp_monitor_save": (i32, [ctx, C.c_char_p]),
-        "ekpnp_group_monitor_sample": (i32, [ctx, C.c_uint32, C.c_void_p]),
-        "ekpnp_group_monitor_arm": (i32, [ctx, C.POINTER(MonitorSpec)]),
-        "ekpnp_group_monitor_disarm": (i32, [ctx]),
-        "ekpnp_group_monitor_record": (i32, [ctx, C.c_int64, dbl]),
-        "ekpnp_group_monitor_count": (i32, [ctx, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
-        "ekpnp_group_monitor_read": (i32, [ctx, C.c_int64, i32, C.c_void_p, C.c_void_p, C.c_void_p]),
-        "ekpnp_group_monitor_save": (i32, [ctx, C.c_char_p]),
-        # seeding x-y structure
         "ekpnp_seed_spec_check": (i32, [C.POINTER(Params), C.POINTER(SeedSpec)]),
         "ekpnp_seed_uniform": (dbl, [C.c_uint64, C.c_uint64, i32]),
         "ekpnp_seed_host": (i32, [C.POINTER(Params), C.POINTER(SeedSpec), i32, i32, i32, C.c_void_p]),
-        "ekpnp_seed": (i32, [ctx, C.POINTER(SeedSpec)]),
-        "ekpnp_group_seed": (i32, [ctx, C.POINTER(SeedSpec)]),
-        # projection onto chosen x-y modes and its time series
         "ekpnp_modes_spec_check": (i32, [C.POINTER(Params), C.POINTER(ModesSpec)]),
-        "ekpnp_mode_amplitudes": (i32, [ctx, C.POINTER(ModesSpec), C.c_void_p]),
-        "ekpnp_modes_arm": (i32, [ctx, C.POINTER(ModesSpec), i32]),
-        "ekpnp_modes_disarm": (i32, [ctx]),
-        "ekpnp_modes_record": (i32, [ctx, C.c_int64, dbl]),
-        "ekpnp_modes_count": (i32, [ctx, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
-        "ekpnp_modes_read": (i32, [ctx, C.c_int64, i32, C.c_void_p, C.c_void_p, C.c_void_p]),
-        "ekpnp_modes_save": (i32, [ctx, C.c_char_p]),
-        "ekpnp_group_mode_amplitudes": (i32, [ctx, C.POINTER(ModesSpec), C.c_void_p]),
-        "ekpnp_group_modes_arm": (i32, [ctx, C.POINTER(ModesSpec), i32]),
-        "ekpnp_group_modes_disarm": (i32, [ctx]),
-        "ekpnp_group_modes_record": (i32, [ctx, C.c_int64, dbl]),
-        "ekpnp_group_modes_count": (i32, [ctx, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
-        "ekpnp_group_modes_read": (i32, [ctx, C.c_int64, i32, C.c_void_p, C.c_void_p, C.c_void_p]),
-        "ekpnp_group_modes_save": (i32, [ctx, C.c_char_p]),
-        # x-y power spectra per plane: shells, peak and their time series
         "ekpnp_spectrum_spec_check": (i32, [C.POINTER(Params), C.POINTER(SpectrumSpec)]),
         "ekpnp_spectrum_shell_count": (i32, [C.POINTER(Params), C.POINTER(i32)]),
         "ekpnp_spectrum_shells": (i32, [C.POINTER(Params), C.c_void_p, C.c_void_p]),
-        "ekpnp_spectrum_plane": (i32, [ctx, i32, i32, C.c_void_p]),
-        "ekpnp_spectrum": (i32, [ctx, C.POINTER(SpectrumSpec), C.c_void_p, C.c_void_p]),
-        "ekpnp_spectrum_arm": (i32, [ctx, C.POINTER(SpectrumSpec), i32]),
-        "ekpnp_spectrum_disarm": (i32, [ctx]),
-        "ekpnp_spectrum_record": (i32, [ctx, C.c_int64, dbl]),
-        "ekpnp_spectrum_count": (i32, [ctx, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
-        "ekpnp_spectrum_read": (i32, [ctx, C.c_int64, i32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-        "ekpnp_spectrum_save": (i32, [ctx, C.c_char_p]),
-        "ekpnp_group_spectrum_plane": (i32, [ctx, i32, i32, C.c_void_p]),
-        "ekpnp_group_spectrum": (i32, [ctx, C.POINTER(SpectrumSpec), C.c_void_p, C.c_void_p]),
-        "ekpnp_group_spectrum_arm": (i32, [ctx, C.POINTER(SpectrumSpec), i32]),
-        "ekpnp_group_spectrum_disarm": (i32, [ctx]),
-        "ekpnp_group_spectrum_record": (i32, [ctx, C.c_int64, dbl]),
-        "ekpnp_group_spectrum_count": (i32, [ctx, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
-        "ekpnp_group_spectrum_read": (i32, [ctx, C.c_int64, i32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-        "ekpnp_group_spectrum_save": (i32, [ctx, C.c_char_p]),
-        # histograms, value ranges and their time series
         "ekpnp_hist_bin": (i32, [dbl, dbl, i32, dbl]),
         "ekpnp_hist_spec_check": (i32, [C.POINTER(Params), C.POINTER(HistSpec)]),
         "ekpnp_hist_range_check": (i32, [C.POINTER(Params), i32, i32, i32]),
-        "ekpnp_hist_planes": (i32, [ctx, C.POINTER(HistSpec), C.c_void_p, C.c_void_p]),
-        "ekpnp_value_range": (i32, [ctx, i32, C.c_void_p, C.c_void_p]),
-        "ekpnp_hist_arm": (i32, [ctx, C.POINTER(HistSpec), i32, i32, i32]),
-        "ekpnp_hist_disarm": (i32, [ctx]),
-        "ekpnp_hist_record": (i32, [ctx, C.c_int64, dbl]),
-        "ekpnp_hist_count": (i32, [ctx, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
-        "ekpnp_hist_read": (i32, [ctx, C.c_int64, i32, C.c_void_p, C.c_void_p, C.c_void_p]),
-        "ekpnp_hist_save": (i32, [ctx, C.c_char_p]),
-        "ekpnp_group_hist_planes": (i32, [ctx, C.POINTER(HistSpec), C.c_void_p, C.c_void_p]),
-        "ekpnp_group_value_range": (i32, [ctx, i32, C.c_void_p, C.c_void_p]),
-        "ekpnp_group_hist_arm": (i32, [ctx, C.POINTER(HistSpec), i32, i32, i32]),
-        "ekpnp_group_hist_disarm": (i32, [ctx]),
-        "ekpnp_group_hist_record": (i32, [ctx, C.c_int64, dbl]),
-        "ekpnp_group_hist_count": (i32, [ctx, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
-        "ekpnp_group_hist_read": (i32, [ctx, C.c_int64, i32, C.c_void_p, C.c_void_p, C.c_void_p]),
-        "ekpnp_group_hist_save": (i32, [ctx, C.c_char_p]),
-        # sections and their time series
         "ekpnp_section_sum": (dbl, [C.c_void_p, C.c_ssize_t, i32]),
         "ekpnp_section_spec_check": (i32, [C.POINTER(Params), C.POINTER(SectionSpec)]),
         "ekpnp_section_extent": (i32, [C.POINTER(Params), C.POINTER(SectionSpec), C.POINTER(i32), C.POINTER(i32)]),
-        "ekpnp_section": (i32, [ctx, C.POINTER(SectionSpec), C.c_void_p]),
-        "ekpnp_section_save": (i32, [ctx, C.POINTER(SectionSpec), C.c_char_p, dbl]),
-        "ekpnp_section_arm": (i32, [ctx, C.POINTER(SectionSpec), i32]),
-        "ekpnp_section_disarm": (i32, [ctx]),
-        "ekpnp_section_record": (i32, [ctx, C.c_int64, dbl]),
-        "ekpnp_section_count": (i32, [ctx, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
-        "ekpnp_section_read": (i32, [ctx, C.c_int64, i32, C.c_void_p, C.c_void_p, C.c_void_p]),
-        "ekpnp_section_ring_save": (i32, [ctx, C.c_char_p]),
-        "ekpnp_group_section": (i32, [ctx, C.POINTER(SectionSpec), C.c_void_p]),
-        "ekpnp_group_section_save": (i32, [ctx, C.POINTER(SectionSpec), C.c_char_p, dbl]),
-        "ekpnp_group_section_arm": (i32, [ctx, C.POINTER(SectionSpec), i32]),
-        "ekpnp_group_section_disarm": (i32, [ctx]),
-        "ekpnp_group_section_record": (i32, [ctx, C.c_int64, dbl]),
-        "ekpnp_group_section_count": (i32, [ctx, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
-        "ekpnp_group_section_read": (i32, [ctx, C.c_int64, i32, C.c_void_p, C.c_void_p, C.c_void_p]),
-        "ekpnp_group_section_ring_save": (i32, [ctx, C.c_char_p]),
     }
+    # the diagnostics a context and a group both have: ekpnp_<name>(ctx, ...) and ekpnp_group_<name>(group, ...) with the same arguments
+    series = {  # the verbs of a time series on a ring (csrc/ring.h)
+        "disarm": [], "record": [C.c_int64, dbl], "count": [C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
+        "read": [C.c_int64, i32, C.c_void_p, C.c_void_p, C.c_void_p],
+    }
+    both = {
+        # plane profiles and running statistics
+        "plane_sums": [C.c_void_p], "stats_reset": [], "stats_accumulate": [], "stats_get": [C.c_void_p, C.POINTER(i32)], "save_profiles": [C.c_char_p, dbl],
+        "snapshot_begin": [C.POINTER(SnapshotSpec), C.c_char_p, dbl], "snapshot_finish": [], "snapshot_pending": [],
+        # per-step scalar time series
+        "monitor_sample": [C.c_uint32, C.c_void_p], "monitor_arm": [C.POINTER(MonitorSpec)], "monitor_save": [C.c_char_p],
+        # seeding x-y structure; projection onto chosen x-y modes and its time series
+        "seed": [C.POINTER(SeedSpec)],
+        "mode_amplitudes": [C.POINTER(ModesSpec), C.c_void_p], "modes_arm": [C.POINTER(ModesSpec), i32], "modes_save": [C.c_char_p],
+        # x-y power spectra per plane: shells, peak and their time series (a row is read as shells and peaks)
+        "spectrum_plane": [i32, i32, C.c_void_p], "spectrum": [C.POINTER(SpectrumSpec), C.c_void_p, C.c_void_p],
+        "spectrum_arm": [C.POINTER(SpectrumSpec), i32], "spectrum_save": [C.c_char_p],
+        # histograms, value ranges and their time series
+        "hist_planes": [C.POINTER(HistSpec), C.c_void_p, C.c_void_p], "value_range": [i32, C.c_void_p, C.c_void_p],
+        "hist_arm": [C.POINTER(HistSpec), i32, i32, i32], "hist_save": [C.c_char_p],
+        # sections and their time series
+        "section": [C.POINTER(SectionSpec), C.c_void_p], "section_save": [C.POINTER(SectionSpec), C.c_char_p, dbl],
+        "section_arm": [C.POINTER(SectionSpec), i32], "section_ring_save": [C.c_char_p],
+    }
+    for kind in ("monitor", "modes", "spectrum", "hist", "section"):
+        for verb, args in series.items():
+            both[f"{kind}_{verb}"] = args + [C.c_void_p] if (kind, verb) == ("spectrum", "read") else args
+    for name, args in both.items():
+        sig["ekpnp_" + name] = sig["ekpnp_group_" + name] = (i32, [ctx] + args)
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError if the library does not export it
         fn.restype = res
@@ -850,8 +971,12 @@ def comm_timing(L, handle, check) -> dict:
     return out
 
 
-class Solver(_Sections):
+class Solver(_Diagnostics):
     """One EK-PNP simulation on the current HIP device (or one z slab of it)."""
+
+    _PREFIX = "ekpnp_"  # (_Diagnostics)
+    _handle = property(lambda self: self._h)
+    _planes = property(lambda self: self.nz_local)
 
     def __init__(self, params: Params, rank: int = 0, nranks: int = 1, slab: bool = False):
         self._L = load_library()
@@ -1015,31 +1140,6 @@ class Solver(_Sections):
         self._ck(self._L.ekpnp_read_state(self._h, os.fsencode(path), C.byref(t)))
         return t.value
 
-    # -- plane profiles and running statistics (no reference counterpart) --------------------
-    def plane_sums(self) -> np.ndarray:
-        """[len(PROFILE_NAMES)][nz_local]: sums over the nx*ny nodes of each owned plane of the current fields, their
-        squares and the flux / body-force products, reduced on the device (a mean is a sum / (nx*ny))."""
-        out = np.empty((len(PROFILE_NAMES), self.nz_local), dtype=np.float64)
-        self._ck(self._L.ekpnp_plane_sums(self._h, out.ctypes.data_as(C.c_void_p)))
-        return out
-
-    def stats_reset(self):
-        self._ck(self._L.ekpnp_stats_reset(self._h))
-
-    def stats_accumulate(self):
-        """running sums += plane sums of the current fields; enqueues only (place it between two step() calls)"""
-        self._ck(self._L.ekpnp_stats_accumulate(self._h))
-
-    def stats_get(self):
-        """(running sums [len(PROFILE_NAMES)][nz_local], number of samples)"""
-        out, n = np.empty((len(PROFILE_NAMES), self.nz_local), dtype=np.float64), C.c_int()
-        self._ck(self._L.ekpnp_stats_get(self._h, out.ctypes.data_as(C.c_void_p), C.byref(n)))
-        return out, n.value
-
-    def save_profiles(self, path: str, time: float = 0.0):
-        """text file of the time-averaged plane means of the owned planes (ekpnp_save_profiles)"""
-        self._ck(self._L.ekpnp_save_profiles(self._h, os.fsencode(path), float(time)))
-
     # -- coarsened FP32 snapshots (no reference counterpart) -----------------------------------
     def snapshot_planes(self, cz: int = 1):
         """(first output plane, number of output planes) of this context for a z sampling step cz: planes k with k*cz owned"""
@@ -1061,209 +1161,6 @@ class Solver(_Sections):
         self._ck(self._L.ekpnp_snapshot_read(self._h, C.byref(spec), out.ctypes.data_as(C.c_void_p), C.byref(k0), C.byref(kn)))
         assert (k0.value, kn.value) == self.snapshot_planes(spec.cz)
         return {n: out[i] for i, n in enumerate(names)}
-
-    def snapshot_begin(self, path: str, fields=None, coarsen=(1, 1, 1), time: float = 0.0):
-        """enqueue a snapshot for the legacy VTK file `path` and return at once (place it between two step() calls);
-        snapshot_finish() writes the file.  At most two are pending: a third begin first finishes the oldest."""
-        spec = snapshot_spec(fields, coarsen)
-        self._ck(self._L.ekpnp_snapshot_begin(self._h, C.byref(spec), os.fsencode(path), float(time)))
-
-    def snapshot_finish(self):
-        """wait for the copies of the pending snapshots (not for the compute stream) and write their files"""
-        self._ck(self._L.ekpnp_snapshot_finish(self._h))
-
-    @property
-    def snapshot_pending(self) -> int:
-        return int(self._L.ekpnp_snapshot_pending(self._h))
-
-    # -- per-step scalar time series kept on the device (no reference counterpart) --------------
-    def monitor_sample(self, quantities=None) -> np.ndarray:
-        """the len(MONITOR_NAMES) scalars of the current fields, now (ekpnp_monitor_sample: complete on return; columns
-        that are not selected hold 0.0).  Needs no armed monitor and does not touch the ring."""
-        out = np.zeros(len(MONITOR_NAMES), dtype=np.float64)
-        self._ck(self._L.ekpnp_monitor_sample(self._h, monitor_mask(quantities), out.ctypes.data_as(C.c_void_p)))
-        return out
-
-    def monitor_arm(self, quantities=None, every: int = 1, capacity: int = 1024):
-        """from now on step() appends a row to a ring of `capacity` rows in device memory after every `every`-th step:
-        enqueued only, nothing waits.  Arming again resets the ring and the step count."""
-        spec = MonitorSpec(monitor_mask(quantities), int(every), int(capacity))
-        self._ck(self._L.ekpnp_monitor_arm(self._h, C.byref(spec)))
-
-    def monitor_disarm(self):
-        self._ck(self._L.ekpnp_monitor_disarm(self._h))
-
-    def monitor_record(self, step: int, time: float):
-        """append a row with the caller's labels (hosts that drive stream_collide_save / fast_Poisson themselves); enqueues only"""
-        self._ck(self._L.ekpnp_monitor_record(self._h, int(step), float(time)))
-
-    def monitor_count(self):
-        """(rows recorded since arming, rows lost to overflow); host-known, never synchronises"""
-        r, d = C.c_int64(), C.c_int64()
-        self._ck(self._L.ekpnp_monitor_count(self._h, C.byref(r), C.byref(d)))
-        return int(r.value), int(d.value)
-
-    def monitor_read(self, first: int = 0, count: int = None):
-        """(steps[n], times[n], values[n][len(MONITOR_NAMES)]) of the rows still held, oldest first; count None: all from `first` on"""
-        if count is None:
-            r, d = self.monitor_count()
-            count = r - d - first
-        return _monitor_read(self._L, self._L.ekpnp_monitor_read, self._h, self._ck, first, count)
-
-    def monitor_save(self, path: str):
-        self._ck(self._L.ekpnp_monitor_save(self._h, os.fsencode(path)))
-
-    # -- seeding x-y structure and tracking chosen x-y modes (no reference counterpart) -----------
-    def seed(self, spec: SeedSpec = None, **kw):
-        """add a pattern and / or reproducible noise to the selected field arrays on the device (ekpnp_seed: enqueues only, no
-        field moves; the bits of get_field, seed_host, set_field).  Then fast_Poisson() and init_equilibrium().  spec, or the
-        keywords of seed_spec()."""
-        spec = spec if spec is not None else seed_spec(**kw)
-        self._ck(self._L.ekpnp_seed(self._h, C.byref(spec)))
-
-    def mode_amplitudes(self, field="uz", modes=((1, 1),)) -> np.ndarray:
-        """[nmodes][self.nz_local][2]: per plane a = sum v cos(theta), b = sum v sin(theta), theta = 2 pi (m x/nx + n y/ny), unnormalised
-        (ekpnp_mode_amplitudes; complete on return).  field may be a ModesSpec."""
-        spec = _as_modes_spec(field, modes)
-        out = np.zeros((max(spec.nmodes, 0), self.nz_local, 2), dtype=np.float64)
-        self._ck(self._L.ekpnp_mode_amplitudes(self._h, C.byref(spec), out.ctypes.data_as(C.c_void_p)))
-        return out
-
-    def modes_arm(self, field="uz", modes=((1, 1),), capacity: int = 1024):
-        """track the energies E = sum_z (a^2 + b^2) of the modes in a ring of `capacity` rows in device memory; rows are appended by
-        modes_record() only"""
-        spec = _as_modes_spec(field, modes)
-        self._ck(self._L.ekpnp_modes_arm(self._h, C.byref(spec), int(capacity)))
-        self._modes_n = spec.nmodes
-
-    def modes_disarm(self):
-        self._ck(self._L.ekpnp_modes_disarm(self._h))
-
-    def modes_record(self, step: int, time: float):
-        """append a row with the caller's labels; enqueues only (place it between two step() calls)"""
-        self._ck(self._L.ekpnp_modes_record(self._h, int(step), float(time)))
-
-    def modes_count(self):
-        """(rows recorded since arming, rows lost to overflow); host-known, never synchronises"""
-        r, d = C.c_int64(), C.c_int64()
-        self._ck(self._L.ekpnp_modes_count(self._h, C.byref(r), C.byref(d)))
-        return int(r.value), int(d.value)
-
-    def modes_read(self, first: int = 0, count: int = None):
-        """(steps[n], times[n], energies[n][nmodes]) of the rows still held, oldest first; count None: all from `first` on"""
-        if count is None:
-            r, d = self.modes_count()
-            count = r - d - first
-        return _modes_read(self._L, self._L.ekpnp_modes_read, self._h, self._ck, getattr(self, "_modes_n", 0), first, count)
-
-    def modes_save(self, path: str):
-        self._ck(self._L.ekpnp_modes_save(self._h, os.fsencode(path)))
-
-    # -- x-y power spectra per plane: shells, peak and their time series (no reference counterpart) --
-    def spectrum_shells(self):
-        """(shell_of[ny][nx/2 + 1], count[nshell]) of this lattice: the library's own binning (ekpnp_spectrum_shells, host only)"""
-        return spectrum_shells(self.p)
-
-    def spectrum_plane(self, field, z: int) -> np.ndarray:
-        """P[ny][nx/2 + 1] of the global plane z in rfft2's layout: w (re^2 + im^2), w = 1 for m = 0 and the even Nyquist column, 2
-        otherwise, unnormalised (ekpnp_spectrum_plane; complete on return)"""
-        fid = FIELD_ID[field] if isinstance(field, str) else int(field)
-        out = np.zeros((self.p.ny, self.p.nx // 2 + 1), dtype=np.float64)
-        self._ck(self._L.ekpnp_spectrum_plane(self._h, fid, int(z), out.ctypes.data_as(C.c_void_p)))
-        return out
-
-    def spectrum(self, field="uz", planes=None):
-        """(shells[np][nshell], peaks[np][3]): per plane the shell spectrum E(s) and the dominant mode (m, n signed, P); planes None:
-        every plane (self.nz_local), else the chosen global z (ekpnp_spectrum; complete on return).  field may be a SpectrumSpec."""
-        spec = _as_spectrum_spec(field, planes)
-        rows = spec.nplanes if spec.nplanes else self.nz_local
-        nshell = self._spectrum_nshell = getattr(self, "_spectrum_nshell", None) or len(self.spectrum_shells()[1])
-        shells = np.zeros((max(rows, 0), nshell), dtype=np.float64)
-        peaks = np.zeros((max(rows, 0), 3), dtype=np.float64)
-        self._ck(self._L.ekpnp_spectrum(self._h, C.byref(spec), shells.ctypes.data_as(C.c_void_p), peaks.ctypes.data_as(C.c_void_p)))
-        return shells, peaks
-
-    def spectrum_arm(self, field="uz", planes=(0,), capacity: int = 1024):
-        """track shells and peak of the chosen planes in a ring of `capacity` rows in device memory; rows are appended by
-        spectrum_record() only"""
-        spec = _as_spectrum_spec(field, planes)
-        self._ck(self._L.ekpnp_spectrum_arm(self._h, C.byref(spec), int(capacity)))
-        self._spectrum_np = spec.nplanes
-        self._spectrum_nshell = len(self.spectrum_shells()[1])
-
-    def spectrum_disarm(self):
-        self._ck(self._L.ekpnp_spectrum_disarm(self._h))
-
-    def spectrum_record(self, step: int, time: float):
-        """enqueue one row labelled (step, time): nothing waits, the step graph is left alone"""
-        self._ck(self._L.ekpnp_spectrum_record(self._h, int(step), float(time)))
-
-    def spectrum_count(self):
-        """(recorded, dropped); host-known, never synchronises"""
-        r, d = C.c_int64(), C.c_int64()
-        self._ck(self._L.ekpnp_spectrum_count(self._h, C.byref(r), C.byref(d)))
-        return r.value, d.value
-
-    def spectrum_read(self, first: int = 0, count: int = None):
-        """(steps[n], times[n], shells[n][nplanes][nshell], peaks[n][nplanes][3]) of the rows still held, oldest first; count None: all
-        from `first` on"""
-        if count is None:
-            r, d = self.spectrum_count()
-            count = max(r - d - first, 0)
-        return _spectrum_read(self._L, self._L.ekpnp_spectrum_read, self._h, self._ck, getattr(self, "_spectrum_np", 0),
-                              getattr(self, "_spectrum_nshell", 0), first, count)
-
-    def spectrum_save(self, path: str):
-        self._ck(self._L.ekpnp_spectrum_save(self._h, os.fsencode(path)))
-
-    # ---- histograms, value ranges and their time series (hist.hip) ----
-    def hist_planes(self, a, b=None):
-        """(counts[nz_local, a.n + 2(, b.n + 2)] int64, nonfinite[nz_local] int64) of every owned plane: cell 0 is the underflow, n + 1 the overflow,
-        a node with a NaN in either value goes to nonfinite and to no cell (ekpnp_hist_planes; complete on return).  a may be a HistSpec."""
-        spec = _as_hist_spec(a, b)
-        counts = np.zeros((self.nz_local,) + spec.cell_shape, dtype=np.int64)
-        nonfinite = np.zeros(self.nz_local, dtype=np.int64)
-        self._ck(self._L.ekpnp_hist_planes(self._h, C.byref(spec), counts.ctypes.data_as(C.c_void_p), nonfinite.ctypes.data_as(C.c_void_p)))
-        return counts, nonfinite
-
-    def value_range(self, value):
-        """(vmin[nz_local], vmax[nz_local]): per owned plane the smallest and largest value that is not NaN (+Inf, -Inf for a plane of NaNs);
-        value: a field or "q" (ekpnp_value_range; complete on return)"""
-        vid = HIST_VALUE_ID[value] if isinstance(value, str) else int(value)
-        vmin, vmax = np.zeros(self.nz_local, dtype=np.float64), np.zeros(self.nz_local, dtype=np.float64)
-        self._ck(self._L.ekpnp_value_range(self._h, vid, vmin.ctypes.data_as(C.c_void_p), vmax.ctypes.data_as(C.c_void_p)))
-        return vmin, vmax
-
-    def hist_arm(self, a, b=None, planes=None, capacity: int = 1024):
-        """allocate the ring; a row is ONE histogram summed over the global planes planes = (z_lo, z_hi) inclusive (None: the interior
-        1 .. nz - 2); from then on rows are appended by hist_record() only"""
-        spec = _as_hist_spec(a, b)
-        z_lo, z_hi = (1, self.p.nz - 2) if planes is None else (int(planes[0]), int(planes[1]))
-        self._ck(self._L.ekpnp_hist_arm(self._h, C.byref(spec), z_lo, z_hi, int(capacity)))
-        self._hist_spec = spec
-
-    def hist_disarm(self):
-        self._ck(self._L.ekpnp_hist_disarm(self._h))
-
-    def hist_record(self, step: int, time: float):
-        """append a row labelled (step, time) (enqueues only)"""
-        self._ck(self._L.ekpnp_hist_record(self._h, int(step), float(time)))
-
-    def hist_count(self):
-        """(rows recorded since the arm, rows dropped because the ring was full); never synchronises"""
-        r, d = C.c_int64(), C.c_int64()
-        self._ck(self._L.ekpnp_hist_count(self._h, C.byref(r), C.byref(d)))
-        return r.value, d.value
-
-    def hist_read(self, first: int = 0, count: int = None):
-        """(steps, times, counts[count, a.n + 2(, b.n + 2)], nonfinite[count]) of the rows still held, oldest first"""
-        if count is None:
-            r, d = self.hist_count()
-            count = max(r - d - first, 0)
-        return _hist_read(self._L, self._L.ekpnp_hist_read, self._h, self._ck, getattr(self, "_hist_spec", None), first, count)
-
-    def hist_save(self, path: str):
-        self._ck(self._L.ekpnp_hist_save(self._h, os.fsencode(path)))
 
     def tune(self, knob: str, value: int):
         self._ck(self._L.ekpnp_tune(self._h, knob.encode(), int(value)))
@@ -1342,10 +1239,14 @@ class Solver(_Sections):
         return comm_timing(self._L, self._h, self._ck)
 
 
-class Group(_Sections):
+class Group(_Diagnostics):
     """nslabs z slabs driven by ONE process (ekpnp_group_*): slab i on HIP device devices[i]
     (default: i modulo the device count; devices may repeat, then the halos move by device copies).
     Same method names as Solver; fields are whole-lattice arrays [NZ][NY][NX]."""
+
+    _PREFIX = "ekpnp_group_"  # (_Diagnostics)
+    _handle = property(lambda self: self._g)
+    _planes = property(lambda self: self.p.nz)
 
     def __init__(self, params: Params, nslabs: int, devices=None, transport: int = TRANSPORT_AUTO):
         self._L = load_library()
@@ -1505,26 +1406,6 @@ class Group(_Sections):
         self._ck(self._L.ekpnp_group_read_state(self._g, os.fsencode(path), C.byref(t)))
         return t.value
 
-    def plane_sums(self) -> np.ndarray:
-        """[len(PROFILE_NAMES)][NZ]: every slab reduces its own planes on its own device"""
-        out = np.empty((len(PROFILE_NAMES), self.p.nz), dtype=np.float64)
-        self._ck(self._L.ekpnp_group_plane_sums(self._g, out.ctypes.data_as(C.c_void_p)))
-        return out
-
-    def stats_reset(self):
-        self._ck(self._L.ekpnp_group_stats_reset(self._g))
-
-    def stats_accumulate(self):
-        self._ck(self._L.ekpnp_group_stats_accumulate(self._g))
-
-    def stats_get(self):
-        out, n = np.empty((len(PROFILE_NAMES), self.p.nz), dtype=np.float64), C.c_int()
-        self._ck(self._L.ekpnp_group_stats_get(self._g, out.ctypes.data_as(C.c_void_p), C.byref(n)))
-        return out, n.value
-
-    def save_profiles(self, path: str, time: float = 0.0):
-        self._ck(self._L.ekpnp_group_save_profiles(self._g, os.fsencode(path), float(time)))
-
     def snapshot(self, fields=None, coarsen=(1, 1, 1)) -> dict:
         """name -> float32 [Z][Y][X] of the whole lattice: every slab coarsens and lands its own sampled planes"""
         spec = snapshot_spec(fields, coarsen)
@@ -1533,206 +1414,6 @@ class Group(_Sections):
         out = np.empty((len(names), Z, Y, X), dtype=np.float32)
         self._ck(self._L.ekpnp_group_snapshot_read(self._g, C.byref(spec), out.ctypes.data_as(C.c_void_p)))
         return {n: out[i] for i, n in enumerate(names)}
-
-    def snapshot_begin(self, path: str, fields=None, coarsen=(1, 1, 1), time: float = 0.0):
-        spec = snapshot_spec(fields, coarsen)
-        self._ck(self._L.ekpnp_group_snapshot_begin(self._g, C.byref(spec), os.fsencode(path), float(time)))
-
-    def snapshot_finish(self):
-        self._ck(self._L.ekpnp_group_snapshot_finish(self._g))
-
-    @property
-    def snapshot_pending(self) -> int:
-        return int(self._L.ekpnp_group_snapshot_pending(self._g))
-
-    # -- per-step scalar time series kept on the device (no reference counterpart) --------------
-    def monitor_sample(self, quantities=None) -> np.ndarray:
-        """the len(MONITOR_NAMES) scalars of the current fields, now (ekpnp_group_monitor_sample: complete on return; columns
-        that are not selected hold 0.0).  Needs no armed monitor and does not touch the ring."""
-        out = np.zeros(len(MONITOR_NAMES), dtype=np.float64)
-        self._ck(self._L.ekpnp_group_monitor_sample(self._g, monitor_mask(quantities), out.ctypes.data_as(C.c_void_p)))
-        return out
-
-    def monitor_arm(self, quantities=None, every: int = 1, capacity: int = 1024):
-        """from now on step() appends a row to a ring of `capacity` rows in device memory after every `every`-th step:
-        enqueued only, nothing waits.  Arming again resets the ring and the step count."""
-        spec = MonitorSpec(monitor_mask(quantities), int(every), int(capacity))
-        self._ck(self._L.ekpnp_group_monitor_arm(self._g, C.byref(spec)))
-
-    def monitor_disarm(self):
-        self._ck(self._L.ekpnp_group_monitor_disarm(self._g))
-
-    def monitor_record(self, step: int, time: float):
-        """append a row with the caller's labels (hosts that drive stream_collide_save / fast_Poisson themselves); enqueues only"""
-        self._ck(self._L.ekpnp_group_monitor_record(self._g, int(step), float(time)))
-
-    def monitor_count(self):
-        """(rows recorded since arming, rows lost to overflow); host-known, never synchronises"""
-        r, d = C.c_int64(), C.c_int64()
-        self._ck(self._L.ekpnp_group_monitor_count(self._g, C.byref(r), C.byref(d)))
-        return int(r.value), int(d.value)
-
-    def monitor_read(self, first: int = 0, count: int = None):
-        """(steps[n], times[n], values[n][len(MONITOR_NAMES)]) of the rows still held, oldest first; count None: all from `first` on"""
-        if count is None:
-            r, d = self.monitor_count()
-            count = r - d - first
-        return _monitor_read(self._L, self._L.ekpnp_group_monitor_read, self._g, self._ck, first, count)
-
-    def monitor_save(self, path: str):
-        self._ck(self._L.ekpnp_group_monitor_save(self._g, os.fsencode(path)))
-
-    # -- seeding x-y structure and tracking chosen x-y modes (no reference counterpart) -----------
-    def seed(self, spec: SeedSpec = None, **kw):
-        """add a pattern and / or reproducible noise to the selected field arrays on the device (ekpnp_group_seed: enqueues only, no
-        field moves; the bits of get_field, seed_host, set_field).  Then fast_Poisson() and init_equilibrium().  spec, or the
-        keywords of seed_spec()."""
-        spec = spec if spec is not None else seed_spec(**kw)
-        self._ck(self._L.ekpnp_group_seed(self._g, C.byref(spec)))
-
-    def mode_amplitudes(self, field="uz", modes=((1, 1),)) -> np.ndarray:
-        """[nmodes][self.p.nz][2]: per plane a = sum v cos(theta), b = sum v sin(theta), theta = 2 pi (m x/nx + n y/ny), unnormalised
-        (ekpnp_group_mode_amplitudes; complete on return).  field may be a ModesSpec."""
-        spec = _as_modes_spec(field, modes)
-        out = np.zeros((max(spec.nmodes, 0), self.p.nz, 2), dtype=np.float64)
-        self._ck(self._L.ekpnp_group_mode_amplitudes(self._g, C.byref(spec), out.ctypes.data_as(C.c_void_p)))
-        return out
-
-    def modes_arm(self, field="uz", modes=((1, 1),), capacity: int = 1024):
-        """track the energies E = sum_z (a^2 + b^2) of the modes in a ring of `capacity` rows in device memory; rows are appended by
-        modes_record() only"""
-        spec = _as_modes_spec(field, modes)
-        self._ck(self._L.ekpnp_group_modes_arm(self._g, C.byref(spec), int(capacity)))
-        self._modes_n = spec.nmodes
-
-    def modes_disarm(self):
-        self._ck(self._L.ekpnp_group_modes_disarm(self._g))
-
-    def modes_record(self, step: int, time: float):
-        """append a row with the caller's labels; enqueues only (place it between two step() calls)"""
-        self._ck(self._L.ekpnp_group_modes_record(self._g, int(step), float(time)))
-
-    def modes_count(self):
-        """(rows recorded since arming, rows lost to overflow); host-known, never synchronises"""
-        r, d = C.c_int64(), C.c_int64()
-        self._ck(self._L.ekpnp_group_modes_count(self._g, C.byref(r), C.byref(d)))
-        return int(r.value), int(d.value)
-
-    def modes_read(self, first: int = 0, count: int = None):
-        """(steps[n], times[n], energies[n][nmodes]) of the rows still held, oldest first; count None: all from `first` on"""
-        if count is None:
-            r, d = self.modes_count()
-            count = r - d - first
-        return _modes_read(self._L, self._L.ekpnp_group_modes_read, self._g, self._ck, getattr(self, "_modes_n", 0), first, count)
-
-    def modes_save(self, path: str):
-        self._ck(self._L.ekpnp_group_modes_save(self._g, os.fsencode(path)))
-
-    # -- x-y power spectra per plane: shells, peak and their time series (no reference counterpart) --
-    def spectrum_shells(self):
-        """(shell_of[ny][nx/2 + 1], count[nshell]) of this lattice: the library's own binning (ekpnp_spectrum_shells, host only)"""
-        return spectrum_shells(self.p)
-
-    def spectrum_plane(self, field, z: int) -> np.ndarray:
-        """P[ny][nx/2 + 1] of the global plane z in rfft2's layout: w (re^2 + im^2), w = 1 for m = 0 and the even Nyquist column, 2
-        otherwise, unnormalised (ekpnp_group_spectrum_plane; complete on return)"""
-        fid = FIELD_ID[field] if isinstance(field, str) else int(field)
-        out = np.zeros((self.p.ny, self.p.nx // 2 + 1), dtype=np.float64)
-        self._ck(self._L.ekpnp_group_spectrum_plane(self._g, fid, int(z), out.ctypes.data_as(C.c_void_p)))
-        return out
-
-    def spectrum(self, field="uz", planes=None):
-        """(shells[np][nshell], peaks[np][3]): per plane the shell spectrum E(s) and the dominant mode (m, n signed, P); planes None:
-        every plane (self.p.nz), else the chosen global z (ekpnp_group_spectrum; complete on return).  field may be a SpectrumSpec."""
-        spec = _as_spectrum_spec(field, planes)
-        rows = spec.nplanes if spec.nplanes else self.p.nz
-        nshell = self._spectrum_nshell = getattr(self, "_spectrum_nshell", None) or len(self.spectrum_shells()[1])
-        shells = np.zeros((max(rows, 0), nshell), dtype=np.float64)
-        peaks = np.zeros((max(rows, 0), 3), dtype=np.float64)
-        self._ck(self._L.ekpnp_group_spectrum(self._g, C.byref(spec), shells.ctypes.data_as(C.c_void_p), peaks.ctypes.data_as(C.c_void_p)))
-        return shells, peaks
-
-    def spectrum_arm(self, field="uz", planes=(0,), capacity: int = 1024):
-        """track shells and peak of the chosen planes in a ring of `capacity` rows in device memory; rows are appended by
-        spectrum_record() only"""
-        spec = _as_spectrum_spec(field, planes)
-        self._ck(self._L.ekpnp_group_spectrum_arm(self._g, C.byref(spec), int(capacity)))
-        self._spectrum_np = spec.nplanes
-        self._spectrum_nshell = len(self.spectrum_shells()[1])
-
-    def spectrum_disarm(self):
-        self._ck(self._L.ekpnp_group_spectrum_disarm(self._g))
-
-    def spectrum_record(self, step: int, time: float):
-        """enqueue one row labelled (step, time): nothing waits, the step graph is left alone"""
-        self._ck(self._L.ekpnp_group_spectrum_record(self._g, int(step), float(time)))
-
-    def spectrum_count(self):
-        """(recorded, dropped); host-known, never synchronises"""
-        r, d = C.c_int64(), C.c_int64()
-        self._ck(self._L.ekpnp_group_spectrum_count(self._g, C.byref(r), C.byref(d)))
-        return r.value, d.value
-
-    def spectrum_read(self, first: int = 0, count: int = None):
-        """(steps[n], times[n], shells[n][nplanes][nshell], peaks[n][nplanes][3]) of the rows still held, oldest first; count None: all
-        from `first` on"""
-        if count is None:
-            r, d = self.spectrum_count()
-            count = max(r - d - first, 0)
-        return _spectrum_read(self._L, self._L.ekpnp_group_spectrum_read, self._g, self._ck, getattr(self, "_spectrum_np", 0),
-                              getattr(self, "_spectrum_nshell", 0), first, count)
-
-    def spectrum_save(self, path: str):
-        self._ck(self._L.ekpnp_group_spectrum_save(self._g, os.fsencode(path)))
-
-    # ---- histograms, value ranges and their time series (hist.hip) ----
-    def hist_planes(self, a, b=None):
-        """(counts[nz, a.n + 2(, b.n + 2)] int64, nonfinite[nz] int64) of every plane of the lattice: cell 0 is the underflow, n + 1 the overflow,
-        a node with a NaN in either value goes to nonfinite and to no cell (ekpnp_group_hist_planes; complete on return).  a may be a HistSpec."""
-        spec = _as_hist_spec(a, b)
-        counts = np.zeros((self.p.nz,) + spec.cell_shape, dtype=np.int64)
-        nonfinite = np.zeros(self.p.nz, dtype=np.int64)
-        self._ck(self._L.ekpnp_group_hist_planes(self._g, C.byref(spec), counts.ctypes.data_as(C.c_void_p), nonfinite.ctypes.data_as(C.c_void_p)))
-        return counts, nonfinite
-
-    def value_range(self, value):
-        """(vmin[nz], vmax[nz]): per plane of the lattice the smallest and largest value that is not NaN (+Inf, -Inf for a plane of NaNs);
-        value: a field or "q" (ekpnp_group_value_range; complete on return)"""
-        vid = HIST_VALUE_ID[value] if isinstance(value, str) else int(value)
-        vmin, vmax = np.zeros(self.p.nz, dtype=np.float64), np.zeros(self.p.nz, dtype=np.float64)
-        self._ck(self._L.ekpnp_group_value_range(self._g, vid, vmin.ctypes.data_as(C.c_void_p), vmax.ctypes.data_as(C.c_void_p)))
-        return vmin, vmax
-
-    def hist_arm(self, a, b=None, planes=None, capacity: int = 1024):
-        """allocate the ring; a row is ONE histogram summed over the global planes planes = (z_lo, z_hi) inclusive (None: the interior
-        1 .. nz - 2); from then on rows are appended by hist_record() only"""
-        spec = _as_hist_spec(a, b)
-        z_lo, z_hi = (1, self.p.nz - 2) if planes is None else (int(planes[0]), int(planes[1]))
-        self._ck(self._L.ekpnp_group_hist_arm(self._g, C.byref(spec), z_lo, z_hi, int(capacity)))
-        self._hist_spec = spec
-
-    def hist_disarm(self):
-        self._ck(self._L.ekpnp_group_hist_disarm(self._g))
-
-    def hist_record(self, step: int, time: float):
-        """append a row labelled (step, time) (enqueues only)"""
-        self._ck(self._L.ekpnp_group_hist_record(self._g, int(step), float(time)))
-
-    def hist_count(self):
-        """(rows recorded since the arm, rows dropped because the ring was full); never synchronises"""
-        r, d = C.c_int64(), C.c_int64()
-        self._ck(self._L.ekpnp_group_hist_count(self._g, C.byref(r), C.byref(d)))
-        return r.value, d.value
-
-    def hist_read(self, first: int = 0, count: int = None):
-        """(steps, times, counts[count, a.n + 2(, b.n + 2)], nonfinite[count]) of the rows still held, oldest first"""
-        if count is None:
-            r, d = self.hist_count()
-            count = max(r - d - first, 0)
-        return _hist_read(self._L, self._L.ekpnp_group_hist_read, self._g, self._ck, getattr(self, "_hist_spec", None), first, count)
-
-    def hist_save(self, path: str):
-        self._ck(self._L.ekpnp_group_hist_save(self._g, os.fsencode(path)))
 
     def save_checkpoint(self, path: str):
         self._ck(self._L.ekpnp_group_save_checkpoint(self._g, os.fsencode(path)))
