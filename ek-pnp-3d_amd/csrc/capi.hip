@@ -705,23 +705,17 @@ static int poisson_single(Ctx& c, bool allow_lazy) {
   if (trc) return trc;
   if (!c.rhs_ready) launch_poisson_rhs(c);
   c.rhs_ready = false;
-  const int nb = poisson_block_count(c);
-  if (nb > 1) {
-    // The middle passes (y forward, z solve, y inverse) of one kx column block back to back, so that the block stays in the
-    // Infinity Cache from one pass to the next (poisson.hip: poisson_block; same kernels, same bits).
-    if (int frc = plane_fft_forward_rows(c)) return frc;
-    for (int k = 0; k < nb; ++k) {
-      const ModeBlock blk = poisson_block(c, k);
-      plane_fft_forward_columns(c, blk);
-      launch_tridiag(c, &blk);
-      plane_fft_inverse_columns(c, blk);
-    }
-    if (int frc = plane_fft_inverse_rows(c)) return frc;
-  } else {
-    if (int frc = plane_fft_forward(c)) return frc;
-    launch_tridiag(c);
-    if (int frc = plane_fft_inverse(c)) return frc;
+  // The middle passes (y forward, z solve, y inverse) of one kx column block back to back, so that the block stays in the
+  // Infinity Cache from one pass to the next (poisson.hip: poisson_block; same kernels, same bits).  One block - the whole
+  // half spectrum - wherever blocks do not apply; with rocFFT plans the rows are the whole 2-D transform and the columns nothing.
+  if (int frc = plane_fft_forward_rows(c)) return frc;
+  for (int k = 0, nb = poisson_block_count(c); k < nb; ++k) {
+    const ModeBlock blk = poisson_block(c, k);
+    plane_fft_forward_columns(c, blk);
+    launch_tridiag(c, &blk);
+    plane_fft_inverse_columns(c, blk);
   }
+  if (int frc = plane_fft_inverse_rows(c)) return frc;
   const bool lazy = allow_lazy && lazy_efield_ok(c);
   if (!lazy) launch_phi_efield(c);
   mark_solved(c, lazy);

@@ -302,7 +302,7 @@ struct Ctx {
   int zchunk = 0;              // planes per bulk launch in in-place mode (shift >= zchunk + 1)
   int bulk_yband = -1;         // the interior sweep (in place: each of its launches) takes bands of this many rows of EVERY plane, band after band, instead of
                                // plane after plane (lbm_kernels.hip: bulk_row_of_block): the three uses of a phi row lie within the Infinity
-                               // Cache's reach.  -1: decided from the plane's traffic (bulk_dispatch), 0: plane after plane (ekpnp_tune
+                               // Cache's reach.  -1: decided from the plane's traffic (launch_collide_bulk), 0: plane after plane (ekpnp_tune
                                // "bulk_yband", EKPNP_BULK_YBAND)
   bool merged_walls = true;    // launch-bound two-buffer lattices: plates and bulk in one launch (k_collide_all)
   // base pointer of lattice l's CURRENT state (plane zg = 0 is the ghost plane below)

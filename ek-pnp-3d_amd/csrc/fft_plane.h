@@ -233,16 +233,25 @@ inline void fft_y_twiddles(int ny, double2* h) {
   h[3 * ny / 4] = make_double2(0.0, 1.0);
 }
 
+// the column pass of `ny` rows and sign `sign` (-1: forward, +1: inverse): f(kernel, its dynamic LDS bytes)
+template <class F>
+__attribute__((always_inline)) inline void fft_y_dispatch(int ny, int sign, F&& f) {
+  if (ny == 512) {
+    if (sign < 0) f(k_fft_y512c4<-1>, fy_lds_bytes(512, 4));
+    else f(k_fft_y512c4<1>, fy_lds_bytes(512, 4));
+  } else {
+    if (sign < 0) f(k_fft_y1024<-1>, fy_lds_bytes(1024, 4));
+    else f(k_fft_y1024<1>, fy_lds_bytes(1024, 4));
+  }
+}
+
 // per-device function attributes (more than 64 KB of dynamic LDS); false if the device refuses
 inline bool fft_y_prepare(int ny) {
   hipError_t e = hipSuccess;
-  if (ny == 512) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fft_y512c4<-1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fy_lds_bytes(512, 4));
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fft_y512c4<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fy_lds_bytes(512, 4));
-  } else {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fft_y1024<-1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fy_lds_bytes(1024, 4));
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fft_y1024<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fy_lds_bytes(1024, 4));
-  }
+  for (const int sign : {-1, 1})
+    fft_y_dispatch(ny, sign, [&](auto kernel, size_t lds) {
+      if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    });
   if (e != hipSuccess) { (void)hipGetLastError(); return false; }
   return true;
 }
@@ -257,19 +266,10 @@ inline void fft_y_launch(double2* spec, const double2* tw, int ny, int nxh, int 
   const long long ps = (long long)ny * nxh;
   const int npairs = nplanes * ngroups;
   const unsigned blocks = (unsigned)((npairs + 7) / 8) * 8 * 2;
-  if (ny == 512) {
-    if (sign < 0)
-      hipLaunchKernelGGL(k_fft_y512c4<-1>, dim3(blocks), dim3(256), fy_lds_bytes(512, 4), stream, spec, tw, nxh, ps, npairs, group0, ngroups);
-    else
-      hipLaunchKernelGGL(k_fft_y512c4<1>, dim3(blocks), dim3(256), fy_lds_bytes(512, 4), stream, spec, tw, nxh, ps, npairs, group0, ngroups);
-  } else {
-    if (sign < 0)
-      hipLaunchKernelGGL(k_fft_y1024<-1>, dim3(blocks), dim3(256), fy_lds_bytes(1024, 4), stream, spec, tw, nxh, ps, npairs, group0, ngroups);
-    else
-      hipLaunchKernelGGL(k_fft_y1024<1>, dim3(blocks), dim3(256), fy_lds_bytes(1024, 4), stream, spec, tw, nxh, ps, npairs, group0, ngroups);
-  }
+  fft_y_dispatch(ny, sign, [&](auto kernel, size_t lds) {
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), lds, stream, spec, tw, nxh, ps, npairs, group0, ngroups);
+  });
 }
-
 
 // ---- x pass: rows of NX real values <-> NX/2 + 1 complex ones (pitch nxh), NX = 1024 or 512 ------------------------
 // A real row x[0..NX-1] is read as N = NX/2 complex numbers z[n] = x[2n] + i x[2n+1]; one wavefront per row does the
@@ -443,15 +443,18 @@ __global__ void __launch_bounds__(64 * FX_ROWS) k_fft_x_c2r(const double2* __res
 }
 
 inline bool fft_x_supported(int nx) { return nx == 1024 || nx == 512; }
+// the row passes of `nx` nodes: f(k_fft_x_r2c<NX>, k_fft_x_c2r<NX>, their dynamic LDS bytes)
+template <class F>
+__attribute__((always_inline)) inline void fft_x_dispatch(int nx, F&& f) {
+  if (nx == 1024) f(k_fft_x_r2c<1024>, k_fft_x_c2r<1024>, fx_lds_bytes(1024));
+  else f(k_fft_x_r2c<512>, k_fft_x_c2r<512>, fx_lds_bytes(512));
+}
 inline bool fft_x_prepare(int nx) {
-  hipError_t e;
-  if (nx == 1024) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fft_x_r2c<1024>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fx_lds_bytes(1024));
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fft_x_c2r<1024>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fx_lds_bytes(1024));
-  } else {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fft_x_r2c<512>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fx_lds_bytes(512));
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fft_x_c2r<512>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fx_lds_bytes(512));
-  }
+  hipError_t e = hipSuccess;
+  fft_x_dispatch(nx, [&](auto r2c, auto c2r, size_t lds) {
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(r2c), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(c2r), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  });
   if (e != hipSuccess) { (void)hipGetLastError(); return false; }
   return true;
 }
@@ -459,18 +462,12 @@ inline bool fft_x_prepare(int nx) {
 inline void fft_x_forward(const double* real, double2* spec, const double2* tw, int nx, int nxh, long long nrows, hipStream_t stream) {
   if (nrows <= 0) return;
   const dim3 grid((unsigned)((nrows + FX_ROWS - 1) / FX_ROWS)), block(64 * FX_ROWS);
-  if (nx == 1024)
-    hipLaunchKernelGGL(k_fft_x_r2c<1024>, grid, block, fx_lds_bytes(1024), stream, real, spec, tw, nxh, nrows);
-  else
-    hipLaunchKernelGGL(k_fft_x_r2c<512>, grid, block, fx_lds_bytes(512), stream, real, spec, tw, nxh, nrows);
+  fft_x_dispatch(nx, [&](auto r2c, auto, size_t lds) { hipLaunchKernelGGL(r2c, grid, block, lds, stream, real, spec, tw, nxh, nrows); });
 }
 inline void fft_x_inverse(const double2* spec, double* real, const double2* tw, int nx, int nxh, long long nrows, hipStream_t stream) {
   if (nrows <= 0) return;
   const dim3 grid((unsigned)((nrows + FX_ROWS - 1) / FX_ROWS)), block(64 * FX_ROWS);
-  if (nx == 1024)
-    hipLaunchKernelGGL(k_fft_x_c2r<1024>, grid, block, fx_lds_bytes(1024), stream, spec, real, tw, nxh, nrows);
-  else
-    hipLaunchKernelGGL(k_fft_x_c2r<512>, grid, block, fx_lds_bytes(512), stream, spec, real, tw, nxh, nrows);
+  fft_x_dispatch(nx, [&](auto, auto c2r, size_t lds) { hipLaunchKernelGGL(c2r, grid, block, lds, stream, spec, real, tw, nxh, nrows); });
 }
 
 }  // namespace ekpnp

@@ -19,6 +19,7 @@
 #include <utility>
 
 #include "ekpnp_internal.h"
+#include "launch_plan.h"
 
 namespace ekpnp {
 
@@ -751,33 +752,66 @@ void launch_pbe_relax(Ctx& c, double* phi_old, double omega) {
   note_launch(c, "k_pbe_relax");
 }
 
+// ---- the one dispatcher: a context's runtime (n_lattices, streamed_state, E from phi) as compile-time constants -------------
+// (launch_plan.h: collide_variant decides; generic lambdas and empty tag types, inlined: nothing is allocated or called
+// indirectly on the launch-bound lattices' way to hipLaunchKernelGGL)
+template <int NL_, bool PULL_, bool EPHI_>
+struct Variant {
+  static constexpr int NL = NL_;
+  static constexpr bool PULL = PULL_, EPHI = EPHI_;
+};
+// f(std::integral_constant<int, NL>), NL = 1, 3 or 4
+template <class F>
+static inline void with_lattices(int n_lattices, F&& f) {
+  switch (n_lattices) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    default: f(std::integral_constant<int, 4>{}); break;
+  }
+}
+// f(Variant<NL, PULL, EPHI>): per kernel family NL = 1 with its two PULL variants, NL = 3, 4 with four variants each
+template <class F>
+static inline void with_collide_variant(const Ctx& c, F&& f) {
+  const CollideVariant v = collide_variant(c.p.n_lattices, c.streamed_state, collide_takes_e_from_phi(c));
+  with_lattices(v.nl, [&](auto nl) {
+    constexpr int NL = decltype(nl)::value;
+    constexpr bool E = NL > 1;  // no EPHI kernels for NL = 1 (v.ephi is false there)
+    if (v.pull) {
+      if (v.ephi) f(Variant<NL, true, E>{});
+      else f(Variant<NL, true, false>{});
+    } else {
+      if (v.ephi) f(Variant<NL, false, E>{});
+      else f(Variant<NL, false, false>{});
+    }
+  });
+}
+// the workgroups of a row-based collide launch: nrows rows of nxb tiles, dealt to the XCDs in runs of BULK_RCHUNK rows
+static inline dim3 collide_grid(int nrows, int nxb) { return dim3((unsigned)xcd_grid_blocks(nrows, nxb, BULK_RCHUNK)); }
+
 void launch_init_equilibrium(Ctx& c) {
   KArgs a = c.kargs();
   // write into the CURRENT buffer: kargs() exposes it as A (const); B is the other one
   for (int l = 0; l < MAXL; ++l) a.B[l] = c.cur_base(l);
-  dim3 g = grid1d((long long)c.nloc, 128), b(128);
-  switch (c.p.n_lattices) {
-    case 1: hipLaunchKernelGGL(k_init_equilibrium<1>, g, b, 0, c.stream, a); note_launch(c, "k_init_equilibrium<1>"); break;
-    case 3: hipLaunchKernelGGL(k_init_equilibrium<3>, g, b, 0, c.stream, a); note_launch(c, "k_init_equilibrium<3>"); break;
-    default: hipLaunchKernelGGL(k_init_equilibrium<4>, g, b, 0, c.stream, a); note_launch(c, "k_init_equilibrium<4>"); break;
-  }
+  with_lattices(c.p.n_lattices, [&](auto nl) {
+    constexpr int NL = decltype(nl)::value;
+    hipLaunchKernelGGL(k_init_equilibrium<NL>, grid1d((long long)c.nloc, 128), dim3(128), 0, c.stream, a);
+    note_launch(c, NL == 1 ? "k_init_equilibrium<1>" : NL == 3 ? "k_init_equilibrium<3>" : "k_init_equilibrium<4>");
+  });
 }
 
-// rows per band of the interior sweep in effect (0: plane after plane): Ctx::bulk_yband, or the rule above bulk_dispatch's launch
+// rows per band of the interior sweep in effect (0: plane after plane): Ctx::bulk_yband, or the rule above launch_collide_bulk's launch
 int bulk_band_rows(const Ctx& c) {
   int yband = c.bulk_yband;
   if (yband < 0) yband = (size_t)c.p.nx * c.p.ny * (size_t)(c.p.n_lattices * 27 * 16 + 80) > ((size_t)192 << 20) ? 128 : 0;
   return yband > 0 && yband < 0x7fff && yband < c.p.ny && c.p.ny % yband == 0 && yband % BULK_RCHUNK == 0 ? yband : 0;
 }
 
-template <int NL>
-static void bulk_dispatch(Ctx& c, const KArgs& a, int zl_begin, int zl_end) {
+void launch_collide_bulk(Ctx& c, int zl_begin, int zl_end) { launch_collide_bulk(c, c.kargs(), zl_begin, zl_end); }
+
+void launch_collide_bulk(Ctx& c, const KArgs& a, int zl_begin, int zl_end) {
   const int nrows = (zl_end - zl_begin) * c.p.ny;
   if (nrows <= 0) return;
   const int nxb = (c.p.nx + 63) / 64;
-  // rows per XCD, rounded up to whole runs: the 8 XCDs together cover [0, 8*per_xcd) >= nrows
-  const long long per_xcd = ((long long)nrows + 8LL * BULK_RCHUNK - 1) / (8LL * BULK_RCHUNK) * BULK_RCHUNK;
-  dim3 g((unsigned)(8 * per_xcd * nxb)), b(64 * NL);
   // y bands (bulk_row_of_block; in-place contexts: inside each of the sweep's launches of `zchunk` planes - a launch writes only
   // where no plane it reads lies, whatever the order of its workgroups).  The
   // sweep of one PLANE moves nx ny x 1 808 B = 474 MB on 512 x 512 planes, 1.9 GB on 1024 x 1024 ones, so the phi row a
@@ -787,116 +821,43 @@ static void bulk_dispatch(Ctx& c, const KArgs& a, int zl_begin, int zl_end) {
   // another order of the workgroups: same bits.  Default (-1): bands of 128 rows where a plane's sweep moves more than
   // 192 MiB and NY is a multiple of 128; smaller planes (256 x 256: 90 - 118 MB) are within the cache's reach as they are.
   const int rchunk = BULK_RCHUNK | bulk_band_rows(c) << 16;
-  const bool ephi = collide_takes_e_from_phi(c);
-  if (c.streamed_state) {
-    if (ephi) hipLaunchKernelGGL((k_collide_bulk<NL, false, (NL > 1)>), g, b, 0, c.stream, a, zl_begin, nrows, nxb, rchunk);
-    else hipLaunchKernelGGL((k_collide_bulk<NL, false, false>), g, b, 0, c.stream, a, zl_begin, nrows, nxb, rchunk);
-  } else {
-    if (ephi) hipLaunchKernelGGL((k_collide_bulk<NL, true, (NL > 1)>), g, b, 0, c.stream, a, zl_begin, nrows, nxb, rchunk);
-    else hipLaunchKernelGGL((k_collide_bulk<NL, true, false>), g, b, 0, c.stream, a, zl_begin, nrows, nxb, rchunk);
-  }
+  with_collide_variant(c, [&](auto v) {
+    using V = decltype(v);
+    hipLaunchKernelGGL((k_collide_bulk<V::NL, V::PULL, V::EPHI>), collide_grid(nrows, nxb), dim3(64 * V::NL), 0, c.stream, a, zl_begin, nrows, nxb, rchunk);
+  });
   note_launch(c, "k_collide_bulk");
 }
 
-template <int NL>
-static void edge_dispatch(Ctx& c, const KArgs& a, int zl) {
-  const int nrows = c.p.ny, nxb = (c.p.nx + 63) / 64, rchunk = BULK_RCHUNK;
-  const long long per_xcd = ((long long)nrows + 8LL * rchunk - 1) / (8LL * rchunk) * rchunk;
-  dim3 g((unsigned)(8 * per_xcd * nxb)), b(64 * NL);
-  const bool ephi = collide_takes_e_from_phi(c);
-  if (c.streamed_state) {
-    if (ephi) hipLaunchKernelGGL((k_collide_edge<NL, false, (NL > 1)>), g, b, 0, c.stream, a, zl, nrows, nxb, rchunk);
-    else hipLaunchKernelGGL((k_collide_edge<NL, false, false>), g, b, 0, c.stream, a, zl, nrows, nxb, rchunk);
-  } else {
-    if (ephi) hipLaunchKernelGGL((k_collide_edge<NL, true, (NL > 1)>), g, b, 0, c.stream, a, zl, nrows, nxb, rchunk);
-    else hipLaunchKernelGGL((k_collide_edge<NL, true, false>), g, b, 0, c.stream, a, zl, nrows, nxb, rchunk);
-  }
+// one slab edge plane: KArgs::halo_* honoured (EDGE kernels)
+void launch_collide_bulk_edge(Ctx& c, const KArgs& a, int zl) {
+  const int nrows = c.p.ny, nxb = (c.p.nx + 63) / 64;
+  with_collide_variant(c, [&](auto v) {
+    using V = decltype(v);
+    hipLaunchKernelGGL((k_collide_edge<V::NL, V::PULL, V::EPHI>), collide_grid(nrows, nxb), dim3(64 * V::NL), 0, c.stream, a, zl, nrows, nxb, BULK_RCHUNK);
+  });
   note_launch(c, "k_collide_edge");
-}
-
-template <int NL>
-static void faces_dispatch(Ctx& c, const KArgs& lo, const KArgs& hi, int lo_plate, int hi_plate) {
-  const int nrows = 2 * c.p.ny, nxb = (c.p.nx + 63) / 64, rchunk = BULK_RCHUNK;
-  const long long per_xcd = ((long long)nrows + 8LL * rchunk - 1) / (8LL * rchunk) * rchunk;
-  dim3 g((unsigned)(8 * per_xcd * nxb)), b(64 * NL);
-  const bool ephi = collide_takes_e_from_phi(c);
-  if (c.streamed_state) {
-    if (ephi) hipLaunchKernelGGL((k_collide_faces<NL, false, (NL > 1)>), g, b, 0, c.stream, lo, hi, lo_plate, hi_plate, nxb, rchunk);
-    else hipLaunchKernelGGL((k_collide_faces<NL, false, false>), g, b, 0, c.stream, lo, hi, lo_plate, hi_plate, nxb, rchunk);
-  } else {
-    if (ephi) hipLaunchKernelGGL((k_collide_faces<NL, true, (NL > 1)>), g, b, 0, c.stream, lo, hi, lo_plate, hi_plate, nxb, rchunk);
-    else hipLaunchKernelGGL((k_collide_faces<NL, true, false>), g, b, 0, c.stream, lo, hi, lo_plate, hi_plate, nxb, rchunk);
-  }
-  note_launch(c, "k_collide_faces");
 }
 
 // a slab's first and last plane in one launch (plates and / or interior faces; KArgs::halo_* honoured)
 void launch_collide_faces(Ctx& c, const KArgs& lo, const KArgs& hi) {
   const int lo_plate = c.z0 == 0, hi_plate = c.z0 + c.nzl == c.p.nz;
-  switch (c.p.n_lattices) {
-    case 1: faces_dispatch<1>(c, lo, hi, lo_plate, hi_plate); break;
-    case 3: faces_dispatch<3>(c, lo, hi, lo_plate, hi_plate); break;
-    default: faces_dispatch<4>(c, lo, hi, lo_plate, hi_plate); break;
-  }
-}
-
-void launch_collide_bulk_edge(Ctx& c, const KArgs& a, int zl) {
-  switch (c.p.n_lattices) {
-    case 1: edge_dispatch<1>(c, a, zl); break;
-    case 3: edge_dispatch<3>(c, a, zl); break;
-    default: edge_dispatch<4>(c, a, zl); break;
-  }
-}
-
-template <int NL>
-static void all_dispatch(Ctx& c, const KArgs& a) {
-  const int nrows_bulk = (c.nzl - 2) * c.p.ny, nrows = nrows_bulk + 2 * c.p.ny;
-  const int nxb = (c.p.nx + 63) / 64, rchunk = BULK_RCHUNK;
-  const long long per_xcd = ((long long)nrows + 8LL * rchunk - 1) / (8LL * rchunk) * rchunk;
-  dim3 g((unsigned)(8 * per_xcd * nxb)), b(64 * NL);
-  const bool ephi = collide_takes_e_from_phi(c);
-  if (c.streamed_state) {
-    if (ephi) hipLaunchKernelGGL((k_collide_all<NL, false, (NL > 1)>), g, b, 0, c.stream, a, 1, nrows_bulk, nxb, rchunk);
-    else hipLaunchKernelGGL((k_collide_all<NL, false, false>), g, b, 0, c.stream, a, 1, nrows_bulk, nxb, rchunk);
-  } else {
-    if (ephi) hipLaunchKernelGGL((k_collide_all<NL, true, (NL > 1)>), g, b, 0, c.stream, a, 1, nrows_bulk, nxb, rchunk);
-    else hipLaunchKernelGGL((k_collide_all<NL, true, false>), g, b, 0, c.stream, a, 1, nrows_bulk, nxb, rchunk);
-  }
-  note_launch(c, "k_collide_all");
+  const int nrows = 2 * c.p.ny, nxb = (c.p.nx + 63) / 64;
+  with_collide_variant(c, [&](auto v) {
+    using V = decltype(v);
+    hipLaunchKernelGGL((k_collide_faces<V::NL, V::PULL, V::EPHI>), collide_grid(nrows, nxb), dim3(64 * V::NL), 0, c.stream, lo, hi, lo_plate, hi_plate, nxb, BULK_RCHUNK);
+  });
+  note_launch(c, "k_collide_faces");
 }
 
 // the whole lattice of a single two-buffer context (both plates and everything in between) in one launch
 void launch_collide_all(Ctx& c) {
   const KArgs a = c.kargs();
-  switch (c.p.n_lattices) {
-    case 1: all_dispatch<1>(c, a); break;
-    case 3: all_dispatch<3>(c, a); break;
-    default: all_dispatch<4>(c, a); break;
-  }
-}
-
-void launch_collide_bulk(Ctx& c, int zl_begin, int zl_end) { launch_collide_bulk(c, c.kargs(), zl_begin, zl_end); }
-
-void launch_collide_bulk(Ctx& c, const KArgs& a, int zl_begin, int zl_end) {
-  switch (c.p.n_lattices) {
-    case 1: bulk_dispatch<1>(c, a, zl_begin, zl_end); break;
-    case 3: bulk_dispatch<3>(c, a, zl_begin, zl_end); break;
-    default: bulk_dispatch<4>(c, a, zl_begin, zl_end); break;
-  }
-}
-
-template <int NL>
-static void wall_dispatch(Ctx& c, const KArgs& a, int first_wall, int nwalls, hipStream_t stream) {
-  dim3 g((unsigned)((c.p.nx + 63) / 64), (unsigned)c.p.ny, (unsigned)nwalls), b(64 * NL);
-  const bool ephi = collide_takes_e_from_phi(c);
-  if (c.streamed_state) {
-    if (ephi) hipLaunchKernelGGL((k_collide_wall<NL, false, (NL > 1)>), g, b, 0, stream, a, first_wall);
-    else hipLaunchKernelGGL((k_collide_wall<NL, false, false>), g, b, 0, stream, a, first_wall);
-  } else {
-    if (ephi) hipLaunchKernelGGL((k_collide_wall<NL, true, (NL > 1)>), g, b, 0, stream, a, first_wall);
-    else hipLaunchKernelGGL((k_collide_wall<NL, true, false>), g, b, 0, stream, a, first_wall);
-  }
-  note_launch(c, "k_collide_wall");
+  const int nrows_bulk = (c.nzl - 2) * c.p.ny, nrows = nrows_bulk + 2 * c.p.ny, nxb = (c.p.nx + 63) / 64;
+  with_collide_variant(c, [&](auto v) {
+    using V = decltype(v);
+    hipLaunchKernelGGL((k_collide_all<V::NL, V::PULL, V::EPHI>), collide_grid(nrows, nxb), dim3(64 * V::NL), 0, c.stream, a, 1, nrows_bulk, nxb, BULK_RCHUNK);
+  });
+  note_launch(c, "k_collide_all");
 }
 
 void launch_collide_walls(Ctx& c, hipStream_t stream, bool want_lower, bool want_upper) {
@@ -907,11 +868,12 @@ void launch_collide_walls(Ctx& c, const KArgs& a, hipStream_t stream, bool want_
   const bool lower = want_lower && c.z0 == 0, upper = want_upper && c.z0 + c.nzl == c.p.nz;
   if (!lower && !upper) return;
   const int first_wall = lower ? 0 : 1, nwalls = (lower && upper) ? 2 : 1;
-  switch (c.p.n_lattices) {
-    case 1: wall_dispatch<1>(c, a, first_wall, nwalls, stream); break;
-    case 3: wall_dispatch<3>(c, a, first_wall, nwalls, stream); break;
-    default: wall_dispatch<4>(c, a, first_wall, nwalls, stream); break;
-  }
+  const dim3 g((unsigned)((c.p.nx + 63) / 64), (unsigned)c.p.ny, (unsigned)nwalls);
+  with_collide_variant(c, [&](auto v) {
+    using V = decltype(v);
+    hipLaunchKernelGGL((k_collide_wall<V::NL, V::PULL, V::EPHI>), g, dim3(64 * V::NL), 0, stream, a, first_wall);
+  });
+  note_launch(c, "k_collide_wall");
 }
 
 static PopGeom pop_geom(const Ctx& c) { return PopGeom{c.p.nx, c.p.ny, c.nzl, (long long)c.rowstride, (long long)c.pplane}; }

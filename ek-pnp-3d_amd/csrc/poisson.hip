@@ -17,6 +17,7 @@
 
 #include "ekpnp_internal.h"
 #include "fft_plane.h"
+#include "launch_plan.h"
 
 namespace ekpnp {
 
@@ -51,11 +52,15 @@ int plane_fft_setup(Ctx& c) {
   return EKPNP_OK;
 }
 
-// The transforms in pieces, for the slab solve with mode blocks (own passes only; with rocFFT plans the 2-D transform is one
-// call, issued with the first / last piece): forward = rows of all planes, then the columns of block k; inverse = the columns
-// of block k, then the rows of all planes.
+// The transforms in pieces: forward = rows of all planes, then the columns of a kx block; inverse = the columns of a block, then
+// the rows of all planes.  The slab solve with mode blocks and the single context's column blocks take them block by block
+// (own passes only: with rocFFT plans the 2-D transform is one call, issued with the rows, and the columns are nothing).
 int plane_fft_forward_rows(Ctx& c) {
-  if (!c.own_fft) return plane_fft_forward(c);
+  if (!c.own_fft) {
+    const hipfftResult r = hipfftExecD2Z(c.plan_fwd, c.fft_in(), c.fft_spec());
+    if (r != HIPFFT_SUCCESS) { c.err = "hipfftExecD2Z: hipfft error " + std::to_string((int)r); return EKPNP_ERR_FFT; }
+    return EKPNP_OK;
+  }
   fft_x_forward(c.fft_in(), reinterpret_cast<double2*>(c.fft_spec()), c.fft_tw, c.p.nx, c.nxh, (long long)c.p.ny * c.fft_nz, c.stream);
   note_launch(c, "k_fft_x_r2c");
   return EKPNP_OK;
@@ -71,36 +76,26 @@ void plane_fft_inverse_columns(Ctx& c, const ModeBlock& b) {
   note_launch(c, "k_fft_y<1>");
 }
 int plane_fft_inverse_rows(Ctx& c) {
-  if (!c.own_fft) return plane_fft_inverse(c);
+  if (!c.own_fft) {
+    const hipfftResult r = hipfftExecZ2D(c.plan_inv, c.fft_spec(), c.fft_out());
+    if (r != HIPFFT_SUCCESS) { c.err = "hipfftExecZ2D: hipfft error " + std::to_string((int)r); return EKPNP_ERR_FFT; }
+    return EKPNP_OK;
+  }
   fft_x_inverse(reinterpret_cast<const double2*>(c.fft_spec()), c.fft_out(), c.fft_tw, c.p.nx, c.nxh, (long long)c.p.ny * c.fft_nz, c.stream);
   note_launch(c, "k_fft_x_c2r");
   return EKPNP_OK;
 }
 
+// the whole transform: the pieces on the block that is the whole half spectrum
+static inline ModeBlock whole_spectrum(const Ctx& c) { return ModeBlock{0, c.nxh, 0, 0, (size_t)4 * c.p.ny * c.nxh}; }
 int plane_fft_forward(Ctx& c) {
-  if (c.own_fft) {
-    fft_x_forward(c.fft_in(), reinterpret_cast<double2*>(c.fft_spec()), c.fft_tw, c.p.nx, c.nxh, (long long)c.p.ny * c.fft_nz, c.stream);
-    note_launch(c, "k_fft_x_r2c");
-    fft_y_launch(reinterpret_cast<double2*>(c.fft_spec()), c.fft_tw + c.p.nx, c.p.ny, c.nxh, c.fft_nz, -1, c.stream);
-    note_launch(c, "k_fft_y<-1>");
-    return EKPNP_OK;
-  }
-  const hipfftResult r = hipfftExecD2Z(c.plan_fwd, c.fft_in(), c.fft_spec());
-  if (r != HIPFFT_SUCCESS) { c.err = "hipfftExecD2Z: hipfft error " + std::to_string((int)r); return EKPNP_ERR_FFT; }
+  if (int rc = plane_fft_forward_rows(c)) return rc;
+  plane_fft_forward_columns(c, whole_spectrum(c));
   return EKPNP_OK;
 }
-
 int plane_fft_inverse(Ctx& c) {
-  if (c.own_fft) {
-    fft_y_launch(reinterpret_cast<double2*>(c.fft_spec()), c.fft_tw + c.p.nx, c.p.ny, c.nxh, c.fft_nz, +1, c.stream);
-    note_launch(c, "k_fft_y<1>");
-    fft_x_inverse(reinterpret_cast<const double2*>(c.fft_spec()), c.fft_out(), c.fft_tw, c.p.nx, c.nxh, (long long)c.p.ny * c.fft_nz, c.stream);
-    note_launch(c, "k_fft_x_c2r");
-    return EKPNP_OK;
-  }
-  const hipfftResult r = hipfftExecZ2D(c.plan_inv, c.fft_spec(), c.fft_out());
-  if (r != HIPFFT_SUCCESS) { c.err = "hipfftExecZ2D: hipfft error " + std::to_string((int)r); return EKPNP_ERR_FFT; }
-  return EKPNP_OK;
+  plane_fft_inverse_columns(c, whole_spectrum(c));
+  return plane_fft_inverse_rows(c);
 }
 
 // rhs of the interior planes, poisson.cu:114-135: g = -F (c - cn)/eps, wall potentials folded
@@ -1038,54 +1033,55 @@ int build_cprime(Ctx& c) {
   return EKPNP_OK;
 }
 
-// Slabs of up to 512 unknown rows take the read-once pair (k_slab_edges + k_slab_part: the spectrum is read once for
-// the solve, plus the few rows at either end of the block for the edge values); taller slabs and
-// ekpnp_tune(ctx, "tri_partition", 0) (the A/B partner) keep the serial pair k_slab_thomas_local + k_slab_reduce_correct.
-static inline bool slab_read_once(const Ctx& c) { return c.tri_partition > 0 && c.tri_lds_ok && c.nxh % 8 == 0 && c.slab_m >= 1 && c.slab_m <= 512; }
+// ---- which z solve runs (launch_plan.h: z_solve_plan, the one table of the partition instantiations) ---------------------------
+// Single context: k_tridiag_pcr64 up to 64 rows; the partition solve k_tridiag_part up to 512 rows on large lattices
+// (c.tri_partition - ekpnp_tune "tri_partition" / EKPNP_TRI_PARTITION: 0 never, the A/B partner; 1 on large lattices; 2 wherever
+// it applies, tests); else the serial sweeps k_tridiag.  Slabs of up to 512 unknown rows take the read-once pair (k_slab_edges +
+// k_slab_part: the spectrum is read once for the solve, plus the few rows at either end of the block for the edge values);
+// taller slabs and tri_partition 0 keep the serial pair k_slab_thomas_local + k_slab_reduce_correct.
+// The instantiation is chosen from the WHOLE spectrum, never from a block - a block solved by another instantiation would
+// eliminate in another order and change the bits.
+static inline ZPlan z_plan(const Ctx& c) {
+  return z_solve_plan(c.slab ? c.slab_m : c.p.nz - 2, c.p.ny * c.nxh, c.nxh, c.tri_partition, c.tri_lds_ok, c.slab);
+}
+
+// the partition kernel of plan p on `modes` modes (whole workgroups of it: column_block), every row of the table instantiated
+// here: k_slab_part<R, LANES>(a, extra...) or k_tridiag_part<R, LANES>(a); notes the kernel it launched by the plan's name
+template <bool SLAB, class... Extra>
+static void launch_part(Ctx& c, const ZPlan& p, const PArgs& a, int modes, Extra... extra) {
+  for_each_zpart_row([&](auto i) {
+    constexpr ZPartRow r = kZPartRows[decltype(i)::value];
+    if (decltype(i)::value != p.row) return;
+    const dim3 grid(modes / p.modes_per_wg), block(512);
+    if constexpr (SLAB) hipLaunchKernelGGL((k_slab_part<r.R, r.lanes>), grid, block, p.lds_bytes, c.stream, a, extra...);
+    else if constexpr (r.single) hipLaunchKernelGGL((k_tridiag_part<r.R, r.lanes>), grid, block, p.lds_bytes, c.stream, a);
+  });
+  note_launch(c, p.name);
+}
+
+// the dynamic-LDS limit of the partition solves is a per-DEVICE function attribute: set when a context is made, on
+// the device it is made on (ekpnp_group_* drives contexts on several devices from one process)
+bool tridiag_prepare_device() {
+  hipError_t e = hipSuccess;
+  auto lds = [&](const void* fn, int bytes) {
+    if (e == hipSuccess) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  };
+  for_each_zpart_row([&](auto i) {
+    constexpr ZPartRow r = kZPartRows[decltype(i)::value];
+    if constexpr (r.single) lds(reinterpret_cast<const void*>(&k_tridiag_part<r.R, r.lanes>), r.R * 8192);
+    lds(reinterpret_cast<const void*>(&k_slab_part<r.R, r.lanes>), r.R * 8192);
+  });
+  if (e != hipSuccess) { (void)hipGetLastError(); return false; }
+  return true;
+}
 
 // ---- mode blocks of the slab z solve ("edge_chunks", ekpnp_internal.h: Ctx::edge_chunks) --------------------------------
-// The half spectrum's nxh / 8 column groups (8 kx columns = one 128-byte line of every row) are dealt to the blocks as evenly
-// as they go; block k covers kx in [x0, x0 + bw) and owns the piece [4][ny bw] at doubles offset 4 ny x0 of edge_local and
-// [nranks][4][ny bw] at nranks 4 ny x0 of edge_all.  One block (the default) is the layout of rounds 1-4.
-//
-// The z-solve kernel (which instantiation of k_slab_part: how many modes share a workgroup) is chosen from the WHOLE
-// spectrum, never from a block - a block solved by another instantiation would eliminate in another order and change the
-// bits - so blocks are made of units of `gu` column groups such that every block holds whole workgroups of any of them
-// (ny 8 gu a multiple of 32 modes; gu = 1 on every lattice with ny a multiple of 4), the same units on every rank.
-static int slab_part_modes(const Ctx& c) {  // modes per workgroup of the k_slab_part instantiation this slab runs
-  const int m = c.slab_m, nm = c.p.ny * c.nxh;
-  if (m <= 128) return nm % 32 == 0 ? 32 : 8;
-  if (m <= 256) return nm % 16 == 0 ? 16 : 8;
-  return 8;
-}
-static int gcd_int(int a, int b) { return b == 0 ? a : gcd_int(b, a % b); }
-static int block_unit_groups(const Ctx& c) {
-  // The same on EVERY rank (the blocks are the pieces of a collective): it depends on the lattice only, not on this slab's row
-  // count or knobs - units that hold whole workgroups of the widest instantiation (32 modes) hold whole ones of the others too.
-  if (c.nxh % 8 != 0) return 1;
-  return 4 / gcd_int(4, c.p.ny);
-}
-int edge_chunk_count(const Ctx& c) {
-  if (c.nxh % 8 != 0) return 1;
-  const int gu = block_unit_groups(c), units = (c.nxh / 8 + gu - 1) / gu;
-  return c.edge_chunks < 1 ? 1 : (c.edge_chunks > units ? units : c.edge_chunks);
-}
+// Block k (launch_plan.h: column_block) covers kx in [x0, x0 + bw) and owns the piece [4][ny bw] at doubles offset 4 ny x0 of
+// edge_local and [nranks][4][ny bw] at nranks 4 ny x0 of edge_all.  One block (the default) is the layout of rounds 1-4.
+int edge_chunk_count(const Ctx& c) { return edge_chunk_count(c.nxh, c.p.ny, c.edge_chunks); }
 ModeBlock mode_block(const Ctx& c, int k) {
-  ModeBlock b;
-  if (c.nxh % 8 != 0) {
-    b.x0 = 0;
-    b.bw = c.nxh;
-  } else {
-    const int groups = c.nxh / 8, gu = block_unit_groups(c), units = (groups + gu - 1) / gu, nb = edge_chunk_count(c);
-    const int u0 = (int)((long long)units * k / nb), u1 = (int)((long long)units * (k + 1) / nb);
-    const int g0 = u0 * gu, g1 = u1 * gu < groups ? u1 * gu : groups;
-    b.x0 = g0 * 8;
-    b.bw = (g1 - g0) * 8;
-  }
-  b.local_off = (size_t)4 * c.p.ny * b.x0;
-  b.all_off = (size_t)c.nranks * 4 * c.p.ny * b.x0;
-  b.doubles = (size_t)4 * c.p.ny * b.bw;
-  return b;
+  const ColumnBlock cb = column_block(c.nxh, c.p.ny, edge_chunk_count(c), k);
+  return ModeBlock{cb.x0, cb.bw, (size_t)4 * c.p.ny * cb.x0, (size_t)c.nranks * 4 * c.p.ny * cb.x0, (size_t)4 * c.p.ny * cb.bw};
 }
 static inline PArgs block_args(const Ctx& c, const ModeBlock& b) {
   PArgs a = c.pargs();
@@ -1099,7 +1095,7 @@ void launch_slab_thomas_local(Ctx& c, int k) {
   PArgs a = block_args(c, blk);
   const int nm = c.p.ny * blk.bw;
   double* edge = c.edge_local + blk.local_off;
-  if (slab_read_once(c)) {
+  if (z_plan(c).family == ZFamily::partition) {
     hipLaunchKernelGGL(k_slab_edges, dim3((nm + 63) / 64), dim3(64 * EDGE_SEGS), 0, c.stream, a, c.slab_row_a, c.slab_m, c.slab_u, edge);
     note_launch(c, "k_slab_edges");
     return;
@@ -1116,27 +1112,13 @@ void launch_slab_reduce_correct(Ctx& c, int k) {
   // this block's piece of the rank's edge buffer has been gathered and is free again: it takes (g_lo, g_hi)
   hipLaunchKernelGGL(k_slab_interface, dim3((nm + 63) / 64), dim3(64), 0, c.stream, a, c.rank, c.nranks, c.edge_all + blk.all_off, c.u1um, bound);
   note_launch(c, "k_slab_interface");
-  if (slab_read_once(c)) {
-    const int m = c.slab_m;
-    // (launch + name of one instantiation)
-#define SLAB_PART(RR, LL, GROUP, NAME)                                                                                           \
-    do {                                                                                                                         \
-        hipLaunchKernelGGL((k_slab_part<RR, LL>), dim3(nm / (GROUP)), dim3(512), (RR) * 8192, c.stream, a, c.slab_row_a, m, bound); \
-        note_launch(c, "k_slab_part<" NAME ">");                                                                                 \
-    } while (0)
-    // short columns: several modes per wavefront (LANES of the partition solve) where the mode count allows whole workgroups
-    // - decided on the whole spectrum (slab_part_modes), the block holds whole workgroups of it by construction (mode_block)
-    const int mc = slab_part_modes(c);
-    if (m <= 128 && mc == 32) SLAB_PART(8, 16, 32, "8,16");
-    else if (m <= 128) SLAB_PART(2, 64, 8, "2");
-    else if (m <= 256 && mc == 16) SLAB_PART(8, 32, 16, "8,32");
-    else if (m <= 256) SLAB_PART(4, 64, 8, "4");
-    else SLAB_PART(8, 64, 8, "8");
-#undef SLAB_PART
+  const ZPlan p = z_plan(c);
+  if (p.family == ZFamily::partition) {
+    launch_part<true>(c, p, a, nm, c.slab_row_a, c.slab_m, (const double*)bound);
     return;
   }
   hipLaunchKernelGGL(k_slab_reduce_correct, dim3((nm + 63) / 64), dim3(64), 0, c.stream, a, c.slab_row_a, c.slab_m, bound, c.slab_w);
-  note_launch(c, "k_slab_reduce_correct");
+  note_launch(c, p.name);
 }
 
 void launch_phi_halo_pack(Ctx& c) {
@@ -1151,116 +1133,58 @@ void launch_poisson_rhs(Ctx& c) {
   note_launch(c, "k_poisson_rhs");
 }
 
-// the dynamic-LDS limit of the partition solves is a per-DEVICE function attribute: set when a context is made, on
-// the device it is made on (ekpnp_group_* drives contexts on several devices from one process)
-bool tridiag_prepare_device() {
-  hipError_t e = hipSuccess;
-  auto lds = [&](const void* fn, int bytes) {
-    if (e == hipSuccess) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  };
-  lds(reinterpret_cast<const void*>(&k_tridiag_part<8, 64>), 8 * 8192);
-  lds(reinterpret_cast<const void*>(&k_tridiag_part<4, 64>), 4 * 8192);
-  lds(reinterpret_cast<const void*>(&k_tridiag_part<8, 32>), 8 * 8192);
-  lds(reinterpret_cast<const void*>(&k_tridiag_part<8, 16>), 8 * 8192);
-  lds(reinterpret_cast<const void*>(&k_slab_part<8, 64>), 8 * 8192);
-  lds(reinterpret_cast<const void*>(&k_slab_part<4, 64>), 4 * 8192);
-  lds(reinterpret_cast<const void*>(&k_slab_part<2, 64>), 2 * 8192);
-  lds(reinterpret_cast<const void*>(&k_slab_part<8, 32>), 8 * 8192);
-  lds(reinterpret_cast<const void*>(&k_slab_part<8, 16>), 8 * 8192);
-  if (e != hipSuccess) { (void)hipGetLastError(); return false; }
-  return true;
-}
-
-// launch + name of one instantiation of the partition solve
-#define TRI_PART(RR, LL, GROUP, NAME)                                                                                            \
-    do {                                                                                                                         \
-        hipLaunchKernelGGL((k_tridiag_part<RR, LL>), dim3(nb / (GROUP)), dim3(512), (RR) * 8192, c.stream, a);                   \
-        note_launch(c, "k_tridiag_part<" NAME ">");                                                                              \
-    } while (0)
 // ---- column blocks of the single context's solve ("poisson_blocks", ekpnp_internal.h: Ctx::poisson_blocks) ----------------
 // The three middle passes of a solve - y forward, z solve, y inverse - all work on kx COLUMNS of the half spectrum (every ky,
 // every plane of a kx range).  Taken block by block, the three passes of one block back to back, a block that fits the
 // 256 MiB Infinity Cache is read from HBM once and written once instead of three times each.  Same kernels, same
 // instantiation (chosen on the whole spectrum, as for the slab's mode blocks), every mode solved by itself: same bits.
 // Only where the library's own column passes and a partition solve run (cfg2 ... cfg5 plane shapes); else one block.
-static bool tridiag_is_partition(const Ctx& c) {
-  const int nm = c.p.ny * c.nxh, rows = c.p.nz - 2;
-  const bool part = c.tri_partition > 0 && c.tri_lds_ok && c.nxh % 8 == 0;
-  const bool large = c.tri_partition > 1 || (size_t)nm * (size_t)rows >= (size_t)4 * 1024 * 1024;
-  return part && large && rows > 64 && rows <= 512;
-}
 // Measured (profiles/r05c_ab_poisson_blocks*.jsonl, MI355X): half spectra of 1.1 GB - cfg3's 512 x 512 x 512 and a 1024 x 1024 x
 // 128 context - gain 0.13 ms per solve with THREE blocks (2.11 -> 1.97 ms inside cfg3's step; 2, 4, 6 blocks gain less, 11 and
 // more lose: narrow blocks are read in short pieces, tools/mall_probe.hip prices that footprint at +0.2 ms per pass, more
 // than the cache gives back), spectra of 0.13 - 0.27 GB (256^3, 512 x 512 x 128) gain nothing or lose 0.02 - 0.1 ms.  Hence the
 // default (Ctx::poisson_blocks == 0): three blocks from 768 MiB of half spectrum on, one below.
-int poisson_block_count(const Ctx& c) {
-  if (c.slab || !c.own_fft || c.poisson_blocks == 1 || !tridiag_is_partition(c)) return 1;
-  int want = c.poisson_blocks;
-  if (want <= 0) want = (size_t)c.p.ny * c.nxh * (size_t)(c.p.nz - 2) * sizeof(double2) >= ((size_t)768 << 20) ? 3 : 1;
-  const int gu = block_unit_groups(c), units = (c.nxh / 8 + gu - 1) / gu;
-  return want > units ? units : want;
-}
+int poisson_block_count(const Ctx& c) { return poisson_block_count(c.slab, c.own_fft, c.poisson_blocks, z_plan(c), c.nxh, c.p.ny, c.p.nz - 2); }
 ModeBlock poisson_block(const Ctx& c, int k) {
-  ModeBlock b{};
-  const int groups = c.nxh / 8, gu = block_unit_groups(c), units = (groups + gu - 1) / gu, nb = poisson_block_count(c);
-  const int u0 = (int)((long long)units * k / nb), u1 = (int)((long long)units * (k + 1) / nb);
-  const int g0 = u0 * gu, g1 = u1 * gu < groups ? u1 * gu : groups;
-  b.x0 = nb == 1 ? 0 : g0 * 8;
-  b.bw = nb == 1 ? c.nxh : (g1 - g0) * 8;
-  return b;
+  const ColumnBlock cb = column_block(c.nxh, c.p.ny, poisson_block_count(c), k);
+  return ModeBlock{cb.x0, cb.bw, 0, 0, 0};
 }
 
 void launch_tridiag(Ctx& c, const ModeBlock* blk) {
   PArgs a = c.pargs();
   if (blk) { a.bx0 = blk->x0; a.bw = blk->bw; }
-  const int nm = c.p.ny * c.nxh;   // the kernel is chosen on the WHOLE spectrum
-  const int nb = c.p.ny * a.bw;    // modes of this launch
-  // c.tri_partition (ekpnp_tune "tri_partition" / EKPNP_TRI_PARTITION): 0 the serial sweeps everywhere (the A/B
-  // partner of k_tridiag_part), 1 the partition solve on large lattices, 2 wherever it applies (tests)
-  const bool part = c.tri_partition > 0 && c.tri_lds_ok && c.nxh % 8 == 0;
-  const int rows = c.p.nz - 2;
-  const bool large = c.tri_partition > 1 || (size_t)nm * (size_t)rows >= (size_t)4 * 1024 * 1024;  // enough modes to fill the chip 8 at a time
+  const ZPlan p = z_plan(c);
+  const int nm = c.p.ny * c.nxh;  // the serial kernels take the whole spectrum (column blocks exist beside a partition solve only)
   // every branch notes the kernel it really launched: a rejected launch is reported by that name
-  if (rows <= 64) {
-    hipLaunchKernelGGL(k_tridiag_pcr64, dim3((nm + 3) / 4), dim3(256), 0, c.stream, a);
-    note_launch(c, "k_tridiag_pcr64");
-  } else if (part && large && rows <= 128 && nm % 32 == 0) {
-    TRI_PART(8, 16, 32, "8,16");
-  } else if (part && large && rows <= 256 && nm % 16 == 0) {
-    TRI_PART(8, 32, 16, "8,32");
-  } else if (part && large && rows <= 256) {
-    TRI_PART(4, 64, 8, "4");
-  } else if (part && large && rows <= 512) {
-    TRI_PART(8, 64, 8, "8");
-  } else {
-    hipLaunchKernelGGL(k_tridiag, dim3((nm + TRI_THREADS - 1) / TRI_THREADS), dim3(TRI_THREADS), 0, c.stream, a);
-    note_launch(c, "k_tridiag");
+  if (p.family == ZFamily::partition) {
+    launch_part<false>(c, p, a, c.p.ny * a.bw);
+    return;
   }
+  const dim3 grid((nm + p.modes_per_wg - 1) / p.modes_per_wg);
+  if (p.family == ZFamily::pcr64) hipLaunchKernelGGL(k_tridiag_pcr64, grid, dim3(256), 0, c.stream, a);
+  else hipLaunchKernelGGL(k_tridiag, grid, dim3(TRI_THREADS), 0, c.stream, a);
+  note_launch(c, p.name);
 }
-
-#undef TRI_PART
 
 void launch_phi_efield(Ctx& c) {
   PArgs a = c.pargs();
   const bool small = c.nloc < (size_t)2 * 1024 * 1024;
   const int zchunk = small ? 1 : PHI_ZCHUNK_LARGE;
   const int nrows = c.p.ny * ((c.nzl + zchunk - 1) / zchunk);
-  const long long per_xcd = ((long long)nrows + 8 * 64 - 1) / (8 * 64) * 64;
   if (!small && c.p.nx % 128 == 0) {  // whole waves of node pairs
     constexpr int X2_THREADS = 256;
     const int bx = c.p.nx >= 2 * X2_THREADS ? X2_THREADS : c.p.nx / 2;  // threads per block, each two nodes
     const int nxb = (c.p.nx + 2 * bx - 1) / (2 * bx);  // the last block of a row may be partly idle (whole waves: nx % 128 == 0)
-    hipLaunchKernelGGL(k_phi_efield_x2<PHI_ZCHUNK_LARGE>, dim3((unsigned)(8 * per_xcd * nxb)), dim3(bx), 0, c.stream, a, nxb, nrows);
+    hipLaunchKernelGGL(k_phi_efield_x2<PHI_ZCHUNK_LARGE>, dim3((unsigned)xcd_grid_blocks(nrows, nxb, 64)), dim3(bx), 0, c.stream, a, nxb, nrows);
     note_launch(c, "k_phi_efield_x2<PHI_ZCHUNK_LARGE>");
     return;
   }
   const int bx = c.p.nx >= 256 ? 256 : 64;
   const int nxb = (c.p.nx + bx - 1) / bx;
   if (small)
-    hipLaunchKernelGGL(k_phi_efield<1>, dim3((unsigned)(8 * per_xcd * nxb)), dim3(bx), 0, c.stream, a, nxb, nrows);
+    hipLaunchKernelGGL(k_phi_efield<1>, dim3((unsigned)xcd_grid_blocks(nrows, nxb, 64)), dim3(bx), 0, c.stream, a, nxb, nrows);
   else
-    hipLaunchKernelGGL(k_phi_efield<PHI_ZCHUNK_LARGE>, dim3((unsigned)(8 * per_xcd * nxb)), dim3(bx), 0, c.stream, a, nxb, nrows);
+    hipLaunchKernelGGL(k_phi_efield<PHI_ZCHUNK_LARGE>, dim3((unsigned)xcd_grid_blocks(nrows, nxb, 64)), dim3(bx), 0, c.stream, a, nxb, nrows);
   note_launch(c, "k_phi_efield");
 }
 
