@@ -22,7 +22,10 @@ def _same(a, b, what=""):
 
 
 @pytest.mark.parametrize("shape,nl,in_place", [((16, 12, 17), 4, 0), ((50, 8, 51), 4, 0), ((130, 6, 19), 4, 0), ((70, 6, 83), 3, 0),
-                                               ((256, 128, 130), 4, 0), ((24, 6, 150), 4, 1), ((7, 5, 4), 4, 0), ((256, 128, 5), 4, 0)])
+                                               ((256, 128, 130), 4, 0), ((24, 6, 150), 4, 1), ((7, 5, 4), 4, 0), ((256, 128, 5), 4, 0),
+                                               # the shapes of tests/_equivariance.py: its exact properties reach the EPHI kernels through this test
+                                               ((16, 12, 9), 4, 0), ((2, 2, 5), 4, 0), ((64, 3, 6), 4, 0), ((130, 4, 8), 4, 0), ((70, 5, 9), 4, 0),
+                                               ((70, 5, 9), 3, 0), ((70, 5, 19), 4, 1), ((70, 5, 19), 4, 0), ((16, 128, 6), 4, 0)])
 def test_lazy_efield_is_bitwise_the_eager_path(pkg, O, shape, nl, in_place):
     """Launch-bound lattices (one merged launch, hipGraph replay), ragged rows, three lattices (Ez formed by the fluid
     wave), a lattice large enough for the lean bulk / wall kernel pair and the two-nodes-per-lane phi / E kernel, in-place
