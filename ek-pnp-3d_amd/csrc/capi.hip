@@ -512,6 +512,7 @@ extern "C" int ekpnp_destroy(ekpnp_ctx* ctx) {
   spectrum_release(c);
   hist_release(c);
   section_release(c);
+  tracers_release(c);
   for (int k = 0; k < 4; ++k) {
     if (c.halo[k]) (void)hipFree(c.halo[k]);
     if (c.phi_halo[k]) (void)hipFree(c.phi_halo[k]);

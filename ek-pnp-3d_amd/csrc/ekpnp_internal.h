@@ -279,6 +279,9 @@ int section_write_file(const char* path, const ekpnp_params& p, const ekpnp_sect
                        std::string& err);
 int section_write_ring_file(const char* path, const ekpnp_params& p, const ekpnp_section_spec& spec, int64_t recorded, int64_t dropped, int n,
                             const int64_t* steps, const double* times, const double* values, std::string& err);
+// tracers.hip: the particle cloud of a single context, its advance, cell counts, moments and their time series (TracerState: made by the first ekpnp_tracers_seed / _set / _load)
+struct TracerState;
+void tracers_release(Ctx&);                                // ekpnp_tracers_release, ekpnp_destroy
 
 struct Ctx {
   ekpnp_params p{};
@@ -376,6 +379,7 @@ struct Ctx {
   SpecState* spectrum = nullptr;   // plane spectra, their plan and time series (spectrum.hip), made by the first spectrum call
   HistState* hist = nullptr;       // histograms, value ranges and their time series (hist.hip), made by the first hist call
   SectionState* section = nullptr; // sections and their time series (section.hip), made by the first section call
+  TracerState* tracers = nullptr;  // the particle cloud, its scratch and its time series (tracers.hip), made by the first cloud
   int collide_phase = 0;           // 0 idle, 1 boundary planes done
   // slab edge planes without pack / unpack copies (KArgs::halo_*): knob, and where the current halos are
   bool halo_direct = true;         // EKPNP_HALO_DIRECT=0: k_halo_pack / k_halo_unpack as in rounds 1-3 (the A/B partner)

@@ -89,6 +89,15 @@ int main(int argc, char* argv[]) {
   section_spec.values = (1u << EKPNP_SECTION_Q) | (1u << EKPNP_UZ);
   section_spec.across = EKPNP_ACROSS_Y;
   section_spec.lo = section_spec.hi = -1;  // -1: the whole axis
+  // --tracers N / --tracers-grid: a particle cloud (ekpnp_tracers_*) advanced by h = M*dt after every M-th iteration (--tracers-every M), a row of
+  // moments each time; tracers.dat and tracers_final.bin at the end, tracer_cells.dat with --tracers-cells
+  bool tracers = false, tracers_box_given = false;
+  ekpnp_tracers_spec tracers_spec = {};
+  tracers_spec.mode = EKPNP_TRACERS_RANDOM;
+  tracers_spec.seed = 1u;
+  unsigned tracers_every = 1;
+  int tracers_substeps = 1, tracers_cells[3] = {0, 0, 0};
+  double tracers_mu = 0.0;
   static const char* const field_names[EKPNP_NFIELDS] = {"rho", "c", "cn", "phi", "ux", "uy", "uz", "Ex", "Ey", "Ez", "T"};
   auto field_id_of = [&](const char* q, size_t len) {
     for (int k = 0; k < EKPNP_NFIELDS; ++k)
@@ -291,6 +300,53 @@ int main(int argc, char* argv[]) {
         if (*q == ',') ++q;
       }
     }
+    else if ((v = val("--tracers"))) {
+      char* end = nullptr;
+      const long long n = std::strtoll(v, &end, 10);
+      if (end == v || *end) { std::fprintf(stderr, "--tracers wants a number of particles, got %s\n", v); return 2; }
+      tracers = true;
+      tracers_spec.mode = EKPNP_TRACERS_RANDOM;
+      tracers_spec.n = n;
+      tracers_spec.gx = tracers_spec.gy = tracers_spec.gz = 0;
+    }
+    else if ((v = val("--tracers-grid"))) {
+      int used = 0;
+      if (std::sscanf(v, "%d,%d,%d%n", &tracers_spec.gx, &tracers_spec.gy, &tracers_spec.gz, &used) != 3 || v[used]) { std::fprintf(stderr, "--tracers-grid wants gx,gy,gz, got %s\n", v); return 2; }
+      tracers = true;
+      tracers_spec.mode = EKPNP_TRACERS_GRID;
+      tracers_spec.n = (int64_t)tracers_spec.gx * tracers_spec.gy * tracers_spec.gz;
+    }
+    else if ((v = val("--tracers-box"))) {
+      int used = 0;
+      if (std::sscanf(v, "%lf,%lf,%lf,%lf,%lf,%lf%n", &tracers_spec.lo[0], &tracers_spec.hi[0], &tracers_spec.lo[1], &tracers_spec.hi[1], &tracers_spec.lo[2], &tracers_spec.hi[2], &used) != 6 || v[used]) {
+        std::fprintf(stderr, "--tracers-box wants x0,x1,y0,y1,z0,z1, got %s\n", v);
+        return 2;
+      }
+      tracers_box_given = true;
+    }
+    else if ((v = val("--tracers-seed"))) {
+      char* end = nullptr;
+      tracers_spec.seed = std::strtoull(v, &end, 10);
+      if (end == v || *end) { std::fprintf(stderr, "--tracers-seed wants a number, got %s\n", v); return 2; }
+    }
+    else if ((v = val("--tracers-every"))) {
+      const int m = std::atoi(v);
+      if (m < 1) { std::fprintf(stderr, "--tracers-every wants a number of iterations >= 1, got %s\n", v); return 2; }
+      tracers_every = (unsigned)m;
+    }
+    else if ((v = val("--tracers-substeps"))) {
+      tracers_substeps = std::atoi(v);
+      if (tracers_substeps < 1 || tracers_substeps > 4096) { std::fprintf(stderr, "--tracers-substeps wants 1 .. 4096, got %s\n", v); return 2; }
+    }
+    else if ((v = val("--tracers-mobility"))) {
+      char* end = nullptr;
+      tracers_mu = std::strtod(v, &end);
+      if (end == v || *end) { std::fprintf(stderr, "--tracers-mobility wants a number (m^2/V/s), got %s\n", v); return 2; }
+    }
+    else if ((v = val("--tracers-cells"))) {
+      int used = 0;
+      if (std::sscanf(v, "%d,%d,%d%n", &tracers_cells[0], &tracers_cells[1], &tracers_cells[2], &used) != 3 || v[used]) { std::fprintf(stderr, "--tracers-cells wants bx,by,bz, got %s\n", v); return 2; }
+    }
     else if ((v = val("--tune"))) {
       const char* eq = std::strchr(v, '=');
       if (!eq || eq == v) { std::fprintf(stderr, "--tune wants knob=value, got %s\n", v); return 2; }
@@ -312,6 +368,18 @@ int main(int argc, char* argv[]) {
                    "                   [--hist-value2 uz --hist-bins2 64 --hist-range2 lo,hi] [--hist-planes zlo,zhi]]\n"
                    "                  [--section-every N | --section-full-every N  [--section-values q,uz] [--section-across y]\n"
                    "                   [--section-range lo,hi] [--section-planes z,z,...]]\n"
+                   "                  [--tracers N | --tracers-grid gx,gy,gz  [--tracers-box x0,x1,y0,y1,z0,z1] [--tracers-seed S] [--tracers-every M]\n"
+                   "                   [--tracers-substeps k] [--tracers-mobility mu] [--tracers-cells bx,by,bz]]\n"
+                   "  --tracers N: N particles at random places (--tracers-seed S, default 1) - or --tracers-grid gx,gy,gz: the centres of a\n"
+                   "  gx x gy x gz grid - of the box --tracers-box (lattice units; default the interior 0,nx,0,ny,1,nz-2) are advected on the\n"
+                   "  device (ekpnp_tracers_*, a single GPU only): after every M-th iteration (--tracers-every, default 1) the cloud moves by\n"
+                   "  h = M*dt through the fields of that moment, in k midpoint substeps (--tracers-substeps, default 1), with the velocity\n"
+                   "  u + mu E (--tracers-mobility, m^2/V/s; default 0: a passive tracer), and a row of moments - alive, lost, the sums of the\n"
+                   "  unwrapped displacements and of their squares, of z and z^2, min and max z - is appended to a ring in device memory\n"
+                   "  (enqueued only, nothing waits).  tracers.dat (ekpnp_tracers_ring_save) and tracers_final.bin (ekpnp_tracers_save) are written\n"
+                   "  at the end, and with --tracers-cells bx,by,bz the final counts per cell as text, tracer_cells.dat.  Advancing every M\n"
+                   "  iterations uses the fields at the end of the interval: exact in a steady flow, first order in M*dt otherwise.  With\n"
+                   "  --batch 1 the batches are cut at these marks; both loops write the same bytes, and every other file is unchanged.\n"
                    "  --seed-pattern P: after the start-up (or the restart read) a pattern with mx,my whole periods across nx and ny (default 1,1)\n"
                    "  and amplitude A (default 1e-3) plus white noise of amplitude B (default 0; reproducible from --seed N, default 1) is added to\n"
                    "  the fields --seed-fields names (default c,cn; out of rho,c,cn,ux,uy,uz,T) on the interior planes, under a sin(pi z/(nz-1))\n"
@@ -412,6 +480,11 @@ int main(int argc, char* argv[]) {
       section_spec.z[0] = (nz - 1) / 2;
     }
   }
+  if (tracers && !tracers_box_given) {  // the interior
+    tracers_spec.lo[0] = 0.0; tracers_spec.hi[0] = (double)nx;
+    tracers_spec.lo[1] = 0.0; tracers_spec.hi[1] = (double)ny;
+    tracers_spec.lo[2] = 1.0; tracers_spec.hi[2] = (double)(nz - 2);
+  }
   if (nsave == 0) nsave = nsteps / 2 ? nsteps / 2 : 1;  // LBM.h:123
   if (print_current == 0) print_current = 1;
 
@@ -438,6 +511,14 @@ int main(int argc, char* argv[]) {
   if ((section_every && ekpnp_section_spec_check(&P, &section_spec) != EKPNP_OK) || (section_full_every && ekpnp_section_spec_check(&P, &section_full_spec) != EKPNP_OK)) {
     std::fprintf(stderr, "ekpnp_main: --section*: %s\n", ekpnp_last_error(nullptr));
     return 2;
+  }
+  if (tracers) {
+    if (gpus > 1 || !devices.empty()) { std::fprintf(stderr, "ekpnp_main: --tracers*: tracers: slab contexts are not supported (one GPU only)\n"); return 2; }
+    if (ekpnp_tracers_spec_check(&P, &tracers_spec) != EKPNP_OK) { std::fprintf(stderr, "ekpnp_main: --tracers*: %s\n", ekpnp_last_error(nullptr)); return 2; }
+    if (tracers_cells[0] && ekpnp_tracers_cell(&P, tracers_cells[0], tracers_cells[1], tracers_cells[2], 0.0, 0.0, 0.0) < -1) {
+      std::fprintf(stderr, "ekpnp_main: --tracers-cells: %s\n", ekpnp_last_error(nullptr));
+      return 2;
+    }
   }
 
   // main.cu:40-52
@@ -510,6 +591,10 @@ int main(int argc, char* argv[]) {
   if (spectrum_every) CK(RUN(spectrum_arm, &spectrum_spec, (int)((nsteps + spectrum_every - 1) / spectrum_every ? (nsteps + spectrum_every - 1) / spectrum_every : 1)));  // a ring that holds the whole run
   if (hist_every) CK(RUN(hist_arm, &hist_spec, hist_z_lo, hist_z_hi, (int)((nsteps + hist_every - 1) / hist_every ? (nsteps + hist_every - 1) / hist_every : 1)));  // a ring that holds the whole run
   if (section_every) CK(RUN(section_arm, &section_spec, (int)((nsteps + section_every - 1) / section_every ? (nsteps + section_every - 1) / section_every : 1)));  // a ring that holds the whole run
+  if (tracers) {  // the cloud at its start positions and a ring that holds the whole run
+    CK(ekpnp_tracers_seed(ctx, &tracers_spec));
+    CK(ekpnp_tracers_arm(ctx, (int)(nsteps / tracers_every ? nsteps / tracers_every : 1)));
+  }
   CK(RUN(synchronize));
   const auto begin = std::chrono::steady_clock::now();  // main.cu:185-186
   for (unsigned i = 0; i < nsteps; i++) {               // main.cu:189-224
@@ -519,7 +604,8 @@ int main(int argc, char* argv[]) {
       while (j + 1 < nsteps && !(j % nsave == 1 || j % print_current == 1 || (profiles_every && (j + 1) % profiles_every == 0) ||
                                  (snap_every && (j + 1) % snap_every == 0) || (modes_every && (j + 1) % modes_every == 0) ||
                                  (spectrum_every && (j + 1) % spectrum_every == 0) || (hist_every && (j + 1) % hist_every == 0) ||
-                                 (section_every && (j + 1) % section_every == 0) || (section_full_every && (j + 1) % section_full_every == 0))) ++j;
+                                 (section_every && (j + 1) % section_every == 0) || (section_full_every && (j + 1) % section_full_every == 0) ||
+                                 (tracers && (j + 1) % tracers_every == 0))) ++j;
       CK(RUN(step, (int)(j - i + 1)));
       for (unsigned k = i; k <= j; ++k) t = t + P.dt;  // the same additions as the loop below makes, so the files carry the same time
       i = j;
@@ -547,6 +633,10 @@ int main(int argc, char* argv[]) {
       char name[40];
       std::snprintf(name, sizeof name, "/section_%07u.dat", i + 1);
       CK(RUN(section_save, &section_full_spec, (out + name).c_str(), t));  // waits for this one map: [values][nz][nkeep] doubles
+    }
+    if (tracers && (i + 1) % tracers_every == 0) {  // enqueues only: the cloud moves through the fields of this moment
+      CK(ekpnp_tracers_advance(ctx, tracers_mu, (double)tracers_every * P.dt, tracers_substeps));
+      CK(ekpnp_tracers_record(ctx, (int64_t)(i + 1), t));
     }
     if (profiles_every && (i + 1) % profiles_every == 0) CK(RUN(stats_accumulate));  // enqueues only: the loop runs on
     if (snap_every && (i + 1) % snap_every == 0) {
@@ -576,6 +666,24 @@ int main(int argc, char* argv[]) {
   if (spectrum_every) CK(RUN(spectrum_save, (out + "/spectrum.dat").c_str()));
   if (hist_every) CK(RUN(hist_save, (out + "/hist.dat").c_str()));
   if (section_every) CK(RUN(section_ring_save, (out + "/section.dat").c_str()));
+  if (tracers) {
+    CK(ekpnp_tracers_ring_save(ctx, (out + "/tracers.dat").c_str()));
+    CK(ekpnp_tracers_save(ctx, (out + "/tracers_final.bin").c_str(), t));
+    if (tracers_cells[0]) {
+      const int bx = tracers_cells[0], by = tracers_cells[1], bz = tracers_cells[2];
+      std::vector<int64_t> counts((size_t)bx * by * bz);
+      int64_t lost = 0;
+      CK(ekpnp_tracers_cell_counts(ctx, bx, by, bz, counts.data(), &lost));
+      FILE* f = std::fopen((out + "/tracer_cells.dat").c_str(), "wb");
+      if (!f) { std::fprintf(stderr, "ekpnp_main: cannot open tracer_cells.dat\n"); ekpnp_destroy(ctx); return 1; }
+      std::fprintf(f, "# ekpnp tracer cells nx %d ny %d nz %d bx %d by %d bz %d n %lld lost %lld time %.17g\n", nx, ny, nz, bx, by, bz, (long long)tracers_spec.n, (long long)lost, t);
+      for (int r = 0; r < by * bz; ++r) {  // one row per (cz, cy), cx along the row
+        for (int k = 0; k < bx; ++k) std::fprintf(f, "%s%lld", k ? " " : "", (long long)counts[(size_t)r * bx + k]);
+        std::fprintf(f, "\n");
+      }
+      std::fclose(f);
+    }
+  }
   CK(grp ? ekpnp_group_destroy(grp) : ekpnp_destroy(ctx));    // main.cu:264-290
   return 0;
 }

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "ekpnp_internal.h"
+#include "philox.h"
 
 using namespace ekpnp;
 
@@ -26,24 +27,7 @@ constexpr int SEED_THREADS = 256;
 constexpr int SEED_MAXF = 7;                 // rho, c, cn, ux, uy, uz, T
 constexpr uint32_t SEED_FIELDS = (1u << EKPNP_RHO) | (1u << EKPNP_C) | (1u << EKPNP_CN) | (1u << EKPNP_UX) | (1u << EKPNP_UY) | (1u << EKPNP_UZ) | (1u << EKPNP_T);
 
-// Philox4x32-10 (Salmon et al., SC11): counter c[4], key k[2]; the key is bumped by the Weyl constants between the rounds
-__host__ __device__ inline void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
-  for (int round = 0; round < 10; ++round) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1, n3 = (uint32_t)p0;
-    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-}
-
-// the uniform number of (seed, global node, field): 53 bits of the first two output words, exact in [-1, 1)
-__host__ __device__ inline double seed_uniform(uint64_t seed, uint64_t node, int field_id) {
-  uint32_t c[4] = {(uint32_t)(node & 0xffffffffu), (uint32_t)(node >> 32), (uint32_t)field_id, 0u};
-  philox4x32_10(c, (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32));
-  const uint64_t k = ((uint64_t)(c[0] >> 5) << 26) + (uint64_t)(c[1] >> 6);
-  return (double)k * 0x1.0p-52 - 1.0;
-}
+// (Philox4x32-10 and seed_uniform, the uniform number of (seed, global node, field): philox.h)
 
 // the pattern at a node from the tables' values (include/ekpnp.h); every operation rounded once
 __host__ __device__ inline double seed_pattern(int pattern, double cx, double sx, double cy, double sy, double c2y) {

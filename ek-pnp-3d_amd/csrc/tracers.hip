@@ -1,0 +1,915 @@
+// tracers.hip — Lagrangian tracers: one particle cloud per context, advected through the frozen fields on the device, with cell
+// counts, displacement moments and their time series (include/ekpnp.h: ekpnp_tracers_*; no reference counterpart).
+//
+// Every other diagnostic is Eulerian.  Trajectories used to cost three ekpnp_get_field copies per sample (1.07 GB each at 512^3)
+// and an interpolation loop on the host.  Here the cloud stays in device memory, structure of arrays, 56 B per particle:
+//   k_tracers_advance<MOB>   one thread per particle, workgroups of 256.  The positions are loaded and stored coalesced; the nsub
+//                            midpoint substeps run inside the kernel (the fields are frozen during the call).  An evaluation
+//                            computes the 8-node stencil once and issues its 24 loads (MOB, mu != 0: 48, E beside u) before the
+//                            first is used.  No LDS, no atomics.  Every index is clamped to the lattice before any load.
+//   k_tracers_seed           a thread per particle: Philox numbers (RANDOM) or three tables the host made (GRID)
+//   k_tracers_cells<LDS>     counts per cell of a bx x by x bz partition: uint32 counters in LDS where the table fits 32 KB, flushed
+//                            with 64-bit integer atomics; 64-bit global integer atomics otherwise.  Counts are integers: exact.
+//   k_tracers_partials / k_tracers_finish   the 12 moments, the scheme of stats.hip over particles: runs of 4096 particles per
+//                            workgroup, thread t adds t, t + 256, ... ascending, reduce.h's trees, partial sums in ascending order
+// ekpnp_tracers_advance_host IS the definition of an advance and ekpnp_tracers_seed_host of a seed; the device leaves their bits by
+// construction: stencil, interpolation, fold and step are ONE __host__ __device__ function each, the step constants are formed
+// once on the host, and this object is built with -ffp-contract=off (csrc/Makefile, PINNED), so that neither side fuses a
+// multiply-add.  The passive and the mu != 0 kernel are two instantiations of one template; mu alone chooses, not the shape.
+// A gather is uncoalesced by nature: a GRID-seeded cloud starts in memory order, a stirred one does not.  No particle sort is built
+// here; tools/time_tracers.py measures both cases.
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "ekpnp_internal.h"
+#include "philox.h"
+#include "reduce.h"
+#include "ring.h"
+
+using namespace ekpnp;
+
+namespace ekpnp {
+
+constexpr int TR_THREADS = 256;
+constexpr int TR_PER_THREAD = 16;
+constexpr int TR_CHUNK = TR_THREADS * TR_PER_THREAD;  // particles per workgroup of the moments
+constexpr int TR_CELL_PER_THREAD = 32;                // particles per thread of the cell counts
+constexpr int TR_LDS_CELLS = 8192;                    // counters (cells + 1) that fit the workgroup's 32 KB of LDS
+constexpr int NM = EKPNP_NTRACER_MOMENTS;
+constexpr const char* kSlabMsg = "tracers: slab contexts are not supported";
+static const char* const kMomentNames[NM] = {"alive", "lost", "sum_dx", "sum_dy", "sum_dz", "sum_dx2", "sum_dy2", "sum_dz2", "sum_z", "sum_z2", "z_min", "z_max"};
+
+struct TrFields {
+  const double* u[3];  // ux, uy, uz [nz][ny][nx]
+  const double* e[3];  // Ex, Ey, Ez (read only when mu != 0)
+};
+struct TrStep {
+  double hx, hy, hz, ax, ay, az, mu;
+  int nx, ny, nz, nsub;
+};
+
+// (int)v of a coordinate, clamped to 0 .. hi: inside the invariant this is (int)v itself; outside it is some index of the lattice
+__host__ __device__ __forceinline__ int tr_index(double v, int hi) {
+  int i = (v >= 0.0 && v < 2147483647.0) ? (int)v : 0;
+  return i > hi ? hi : i;
+}
+
+// L(p, q, f): d = q - p; t = f*d; r = p + t
+__host__ __device__ __forceinline__ double tr_lerp(double p, double q, double f) {
+  const double d = q - p;
+  const double t = f * d;
+  return p + t;
+}
+// a[0..7] = the nodes (k0,j0,i0) (k0,j0,i1) (k0,j1,i0) (k0,j1,i1) (k1,j0,i0) (k1,j0,i1) (k1,j1,i0) (k1,j1,i1)
+__host__ __device__ __forceinline__ double tr_interp(const double a[8], double fx, double fy, double fz) {
+  const double a00 = tr_lerp(a[0], a[1], fx), a10 = tr_lerp(a[2], a[3], fx);
+  const double a01 = tr_lerp(a[4], a[5], fx), a11 = tr_lerp(a[6], a[7], fx);
+  const double b0 = tr_lerp(a00, a10, fy), b1 = tr_lerp(a01, a11, fy);
+  return tr_lerp(b0, b1, fz);
+}
+
+// w[c] = u_c (+ mu E_c) at (x, y, z): the stencil once, every load before the first use
+template <bool MOB>
+__host__ __device__ __forceinline__ void tr_velocity(const TrFields& f, const TrStep& s, double x, double y, double z, double w[3]) {
+  const int i0 = tr_index(x, s.nx - 1), j0 = tr_index(y, s.ny - 1), k0 = tr_index(z, s.nz - 2);
+  const double fx = x - (double)i0, fy = y - (double)j0, fz = z - (double)k0;
+  const int i1 = i0 + 1 == s.nx ? 0 : i0 + 1, j1 = j0 + 1 == s.ny ? 0 : j0 + 1, k1 = k0 + 1;
+  const long long r00 = ((long long)k0 * s.ny + j0) * s.nx, r10 = ((long long)k0 * s.ny + j1) * s.nx;
+  const long long r01 = ((long long)k1 * s.ny + j0) * s.nx, r11 = ((long long)k1 * s.ny + j1) * s.nx;
+  constexpr int NA = MOB ? 6 : 3;
+  double a[NA][8];
+#pragma unroll
+  for (int q = 0; q < NA; ++q) {
+    const double* p = q < 3 ? f.u[q] : f.e[q - 3];
+    a[q][0] = p[r00 + i0]; a[q][1] = p[r00 + i1];
+    a[q][2] = p[r10 + i0]; a[q][3] = p[r10 + i1];
+    a[q][4] = p[r01 + i0]; a[q][5] = p[r01 + i1];
+    a[q][6] = p[r11 + i0]; a[q][7] = p[r11 + i1];
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    w[c] = tr_interp(a[c], fx, fy, fz);
+    if constexpr (MOB) {
+      const double t = s.mu * tr_interp(a[3 + c], fx, fy, fz);
+      w[c] = w[c] + t;
+    }
+  }
+}
+
+// the fold of a periodic coordinate (include/ekpnp.h, step 6); false: the particle is lost
+__host__ __device__ __forceinline__ bool tr_fold(double& x, double n, int& w) {
+  if (x >= n) { x = x - n; w += 1; }
+  else if (x < 0.0) { x = x + n; w -= 1; }
+  if (x >= n) { x = x - n; w += 1; }
+  return x >= 0.0 && x < n;
+}
+// z between the plates; false (NaN, Inf): the particle is lost
+__host__ __device__ __forceinline__ bool tr_fold_z(double& z, double top) {
+  if (!(z >= -1.7976931348623157e308 && z <= 1.7976931348623157e308)) return false;
+  if (z < 0.0) z = 0.0;
+  if (z > top) z = top;
+  return true;
+}
+
+// nsub midpoint substeps of one particle that is not lost on entry
+template <bool MOB>
+__host__ __device__ __forceinline__ void tr_advance(const TrFields& f, const TrStep& s, double& x, double& y, double& z, int& wx, int& wy) {
+  const double px = (double)s.nx, py = (double)s.ny, top = (double)(s.nz - 1);
+  for (int it = 0; it < s.nsub; ++it) {
+    double w[3];
+    tr_velocity<MOB>(f, s, x, y, z, w);
+    double t = s.ax * w[0];
+    double x1 = x + t;
+    t = s.ay * w[1];
+    double y1 = y + t;
+    t = s.az * w[2];
+    double z1 = z + t;
+    int none = 0;
+    bool ok = tr_fold(x1, px, none);
+    ok = tr_fold(y1, py, none) && ok;
+    ok = tr_fold_z(z1, top) && ok;
+    if (ok) {
+      tr_velocity<MOB>(f, s, x1, y1, z1, w);
+      t = s.hx * w[0];
+      x1 = x + t;
+      t = s.hy * w[1];
+      y1 = y + t;
+      t = s.hz * w[2];
+      z1 = z + t;
+      int nwx = wx, nwy = wy;
+      ok = tr_fold(x1, px, nwx);
+      ok = tr_fold(y1, py, nwy) && ok;
+      ok = tr_fold_z(z1, top) && ok;
+      if (ok) { x = x1; y = y1; z = z1; wx = nwx; wy = nwy; }
+    }
+    if (!ok) {  // lost: the image counts stay what they were
+      x = y = z = NAN;
+      return;
+    }
+  }
+}
+
+__host__ __device__ __forceinline__ bool tr_lost(double x, double y, double z) { return x != x || y != y || z != z; }
+
+// the cell of a position (include/ekpnp.h: ekpnp_tracers_cell), -1 for a lost particle
+__host__ __device__ __forceinline__ int tr_cell(int nx, int ny, int nz, int bx, int by, int bz, double x, double y, double z) {
+  if (tr_lost(x, y, z)) return -1;
+  const int i0 = tr_index(x, nx - 1), j0 = tr_index(y, ny - 1), k0 = tr_index(z, nz - 2);
+  const int cx = (int)(((long long)i0 * bx) / nx), cy = (int)(((long long)j0 * by) / ny), cz = (int)(((long long)k0 * bz) / (nz - 1));
+  return (cz * by + cy) * bx + cx;
+}
+
+// a RANDOM start coordinate: r in [-1, 1) -> u in [0, 1) (exact) -> the box; t = hi - lo
+__host__ __device__ __forceinline__ double tr_seed_random(uint64_t seed, uint64_t p, int axis, double lo, double hi, double t, double period) {
+  const double r = seed_uniform(seed, p, 16 + axis);
+  const double h = 0.5 * r;
+  const double u = h + 0.5;
+  const double s = u * t;
+  const double v = lo + s;
+  return (v >= hi || v >= period) ? lo : v;
+}
+
+struct TrCloud {
+  double *x, *y, *z, *x0, *y0, *z0;
+  int32_t *wx, *wy;
+  long long n;
+};
+
+template <bool MOB>
+__global__ void __launch_bounds__(TR_THREADS) k_tracers_advance(TrFields f, TrStep s, TrCloud c) {
+  const long long i = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
+  if (i >= c.n) return;
+  double x = c.x[i], y = c.y[i], z = c.z[i];
+  if (tr_lost(x, y, z)) return;  // nothing is read, nothing is written
+  int wx = c.wx[i], wy = c.wy[i];
+  tr_advance<MOB>(f, s, x, y, z, wx, wy);
+  c.x[i] = x;
+  c.y[i] = y;
+  c.z[i] = z;
+  c.wx[i] = wx;
+  c.wy[i] = wy;
+}
+
+struct TrSeedArgs {
+  double lo[3], hi[3], t[3], period[3];  // t = hi - lo; period: nx, ny, +Inf
+  uint64_t seed;
+  const double* tab;                     // GRID: [gx | gy | gz] coordinates
+  int mode, gx, gy, gz;
+};
+
+__global__ void __launch_bounds__(TR_THREADS) k_tracers_seed(TrSeedArgs a, TrCloud c) {
+  const long long p = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
+  if (p >= c.n) return;
+  double v[3];
+  if (a.mode == EKPNP_TRACERS_GRID) {
+    const long long row = p / a.gx;
+    const int i = (int)(p - row * a.gx), k = (int)(row / a.gy), j = (int)(row - (long long)k * a.gy);
+    v[0] = a.tab[i];
+    v[1] = a.tab[a.gx + j];
+    v[2] = a.tab[a.gx + a.gy + (k < a.gz ? k : a.gz - 1)];
+  } else {
+#pragma unroll
+    for (int q = 0; q < 3; ++q) v[q] = tr_seed_random(a.seed, (uint64_t)p, q, a.lo[q], a.hi[q], a.t[q], a.period[q]);
+  }
+  c.x[p] = v[0]; c.y[p] = v[1]; c.z[p] = v[2];
+  c.x0[p] = v[0]; c.y0[p] = v[1]; c.z0[p] = v[2];
+  c.wx[p] = 0;
+  c.wy[p] = 0;
+}
+
+// the lanes that agree with the wavefront's first lane add their number at once (hist.hip: hist_add); cell < 0: nothing to add
+__device__ __forceinline__ void tr_count_add(unsigned* cnt, int cell) {
+  const int lead = __builtin_amdgcn_readfirstlane(cell);
+  const bool same = cell == lead;
+  const unsigned long long m = __ballot(same);
+  if (same) {
+    if (lead >= 0 && (int)(threadIdx.x & 63) == __ffsll((long long)m) - 1) atomicAdd(&cnt[lead], (unsigned)__popcll(m));
+  } else if (cell >= 0) {
+    atomicAdd(&cnt[cell], 1u);
+  }
+}
+
+// total[cell] += the workgroup's particles in it; total[cells] counts the lost ones (zeroed by the host's memset before)
+template <bool LDS>
+__global__ void __launch_bounds__(TR_THREADS) k_tracers_cells(const double* __restrict__ x, const double* __restrict__ y, const double* __restrict__ z, long long n,
+                                                              int nx, int ny, int nz, int bx, int by, int bz, int cells, unsigned long long* __restrict__ total) {
+  extern __shared__ unsigned tr_cnt[];
+  if constexpr (LDS) {
+    for (int i = threadIdx.x; i <= cells; i += TR_THREADS) tr_cnt[i] = 0u;
+    __syncthreads();
+  }
+  const long long first = (long long)blockIdx.x * (TR_THREADS * TR_CELL_PER_THREAD) + threadIdx.x;
+  for (int k0 = 0; k0 < TR_CELL_PER_THREAD; k0 += 8) {
+    double px[8], py[8], pz[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const long long i = first + (long long)(k0 + k) * TR_THREADS;
+      const bool in = i < n;
+      px[k] = in ? x[i] : 0.0;
+      py[k] = in ? y[i] : 0.0;
+      pz[k] = in ? z[i] : 0.0;
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const long long i = first + (long long)(k0 + k) * TR_THREADS;
+      int cell = tr_cell(nx, ny, nz, bx, by, bz, px[k], py[k], pz[k]);
+      if (cell < 0) cell = cells;
+      if (i >= n) cell = -1;
+      if constexpr (LDS) tr_count_add(tr_cnt, cell);
+      else if (cell >= 0) atomicAdd(&total[cell], 1ull);
+    }
+  }
+  if constexpr (LDS) {
+    __syncthreads();
+    for (int i = threadIdx.x; i <= cells; i += TR_THREADS) {
+      const unsigned v = tr_cnt[i];
+      if (v) atomicAdd(&total[i], (unsigned long long)v);
+    }
+  }
+}
+
+__device__ __forceinline__ double tr_wave_min(double v) { return -wave_max(-v); }
+
+// partial[b * NM + q] of the workgroup's TR_CHUNK particles
+__global__ void __launch_bounds__(TR_THREADS) k_tracers_partials(TrCloud c, int nx, int ny, double* __restrict__ partial) {
+  __shared__ double lds[NM][TR_THREADS / 64];
+  const long long first = (long long)blockIdx.x * TR_CHUNK + threadIdx.x;
+  const double px = (double)nx, py = (double)ny;
+  double s[NM];
+#pragma unroll
+  for (int q = 0; q < NM; ++q) s[q] = 0.0;
+  s[10] = INFINITY;
+  s[11] = -INFINITY;
+#pragma unroll 4
+  for (int k = 0; k < TR_PER_THREAD; ++k) {
+    const long long i = first + (long long)k * TR_THREADS;
+    if (i < c.n) {
+      const double x = c.x[i], y = c.y[i], z = c.z[i];
+      if (tr_lost(x, y, z)) {
+        s[1] += 1.0;  // (the +0.0 a lost particle adds to the sums changes no bit of them)
+      } else {
+        const double x0 = c.x0[i], y0 = c.y0[i], z0 = c.z0[i];
+        const double wx = (double)c.wx[i], wy = (double)c.wy[i];
+        double t = x - x0;
+        double w = wx * px;
+        const double dx = t + w;
+        t = y - y0;
+        w = wy * py;
+        const double dy = t + w;
+        const double dz = z - z0;
+        s[0] += 1.0;
+        s[2] += dx;
+        s[3] += dy;
+        s[4] += dz;
+        t = dx * dx;
+        s[5] += t;
+        t = dy * dy;
+        s[6] += t;
+        t = dz * dz;
+        s[7] += t;
+        s[8] += z;
+        t = z * z;
+        s[9] += t;
+        s[10] = fmin(s[10], z);
+        s[11] = fmax(s[11], z);
+      }
+    }
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int q = 0; q < NM; ++q) {
+    const double r = q < 10 ? wave_sum(s[q]) : q == 10 ? tr_wave_min(s[q]) : wave_max(s[q]);
+    if (lane == 0) lds[q][wave] = r;
+  }
+  __syncthreads();
+  if (threadIdx.x < NM) {
+    const int q = threadIdx.x;
+    double r = lds[q][0];
+#pragma unroll
+    for (int w = 1; w < TR_THREADS / 64; ++w) r = q < 10 ? r + lds[q][w] : q == 10 ? fmin(r, lds[q][w]) : fmax(r, lds[q][w]);
+    partial[(long long)blockIdx.x * NM + q] = r;
+  }
+}
+
+// out[q] = the partials in ascending workgroup order (sixteen loads in flight); no alive particle: z_min = z_max = 0
+__global__ void __launch_bounds__(64) k_tracers_finish(const double* __restrict__ partial, int nwg, double* __restrict__ out) {
+  __shared__ double sh[NM];
+  const int q = threadIdx.x;
+  if (q < NM) {
+    const double* p = partial + q;
+    double r = q < 10 ? 0.0 : q == 10 ? INFINITY : -INFINITY;
+    for (int b0 = 0; b0 < nwg; b0 += 16) {
+      double v[16];
+#pragma unroll
+      for (int k = 0; k < 16; ++k) v[k] = b0 + k < nwg ? p[(long long)(b0 + k) * NM] : (q < 10 ? 0.0 : q == 10 ? INFINITY : -INFINITY);
+#pragma unroll
+      for (int k = 0; k < 16; ++k)
+        if (b0 + k < nwg) r = q < 10 ? r + v[k] : q == 10 ? fmin(r, v[k]) : fmax(r, v[k]);
+    }
+    sh[q] = r;
+  }
+  __syncthreads();
+  if (q < NM) {
+    double r = sh[q];
+    if (q >= 10 && sh[0] == 0.0) r = 0.0;
+    out[q] = r;
+  }
+}
+
+// Host side of a context's cloud: made by the first ekpnp_tracers_seed / _set / _load / _arm, never by a context that uses none.
+struct TracerState {
+  long long n = 0;
+  void* cloud = nullptr;      // one allocation: x, y, z, x0, y0, z0 [n] doubles, then wx, wy [n] int32, then the moments' partials and result
+  size_t cloud_bytes = 0;
+  int nwg = 0;                // workgroups of the moments: ceil(n / TR_CHUNK)
+  double* part = nullptr;     // [nwg][NM], then out[NM] (inside `cloud`)
+  unsigned long long* cells = nullptr;  // [EKPNP_TRACERS_MAX_CELLS + 1], made by the first ekpnp_tracers_cell_counts
+  size_t cells_bytes = 0;
+  double* tab = nullptr;      // GRID seeding: the three tables and their pinned host twin; `landed` marks the last upload
+  double* tab_host = nullptr;
+  size_t tab_doubles = 0;
+  hipEvent_t landed = nullptr;
+  Ring ring;                  // rows of NM doubles
+  TrCloud dev() const {
+    double* d = (double*)cloud;
+    const size_t m = (size_t)n;
+    int32_t* w = (int32_t*)(d + 6 * m);
+    return TrCloud{d, d + m, d + 2 * m, d + 3 * m, d + 4 * m, d + 5 * m, w, w + m, n};
+  }
+  double* out() const { return part + (size_t)nwg * NM; }
+};
+
+void tracers_release(Ctx& c) {
+  if (!c.tracers) return;
+  TracerState& t = *c.tracers;
+  if (t.cloud) { (void)hipFree(t.cloud); c.bytes -= t.cloud_bytes; }
+  if (t.cells) { (void)hipFree(t.cells); c.bytes -= t.cells_bytes; }
+  if (t.tab) { (void)hipFree(t.tab); c.bytes -= t.tab_doubles * sizeof(double); }
+  if (t.tab_host) (void)hipHostFree(t.tab_host);
+  if (t.landed) (void)hipEventDestroy(t.landed);
+  if (t.ring.alloc) c.bytes -= t.ring.bytes;
+  ring_release(t.ring);
+  delete c.tracers;
+  c.tracers = nullptr;
+}
+
+static std::string num(double v) {
+  char b[40];
+  std::snprintf(b, sizeof b, "%.17g", v);
+  return b;
+}
+
+static int tracers_check_lattice(const ekpnp_params& p, std::string& err) {
+  if (p.nx < 1 || p.ny < 1) { err = "tracers: nx = " + std::to_string(p.nx) + ", ny = " + std::to_string(p.ny) + " (must be >= 1)"; return EKPNP_ERR_INVALID; }
+  if (p.nz < 3) { err = "tracers: nz = " + std::to_string(p.nz) + " (must be >= 3: there is no interior plane)"; return EKPNP_ERR_INVALID; }
+  return EKPNP_OK;
+}
+
+static int tracers_check_spec(const ekpnp_params& p, const ekpnp_tracers_spec* s, std::string& err) {
+  if (!s) { err = "tracers: NULL spec"; return EKPNP_ERR_INVALID; }
+  if (int rc = tracers_check_lattice(p, err)) return rc;
+  if (s->n < 1 || s->n > EKPNP_TRACERS_MAX_N) { err = "tracers: n = " + std::to_string((long long)s->n) + " outside 1 .. " + std::to_string((long long)EKPNP_TRACERS_MAX_N); return EKPNP_ERR_INVALID; }
+  if (s->mode < 0 || s->mode > 1) { err = "tracers: mode = " + std::to_string(s->mode) + " (must be 0 or 1)"; return EKPNP_ERR_INVALID; }
+  const int g[3] = {s->gx, s->gy, s->gz};
+  const char* const gn[3] = {"gx", "gy", "gz"};
+  if (s->mode == EKPNP_TRACERS_GRID) {
+    for (int a = 0; a < 3; ++a)
+      if (g[a] < 1) { err = std::string("tracers: ") + gn[a] + " = " + std::to_string(g[a]) + " (must be >= 1)"; return EKPNP_ERR_INVALID; }
+    const __int128 prod = (__int128)s->gx * s->gy * s->gz;
+    if (prod != (__int128)s->n) {
+      err = "tracers: gx*gy*gz = " + std::to_string(s->gx) + "*" + std::to_string(s->gy) + "*" + std::to_string(s->gz) + " is not n = " + std::to_string((long long)s->n);
+      return EKPNP_ERR_INVALID;
+    }
+  } else {
+    for (int a = 0; a < 3; ++a)
+      if (g[a] != 0) { err = std::string("tracers: ") + gn[a] + " = " + std::to_string(g[a]) + " (must be 0 for random seeding)"; return EKPNP_ERR_INVALID; }
+  }
+  const double top[3] = {(double)p.nx, (double)p.ny, (double)(p.nz - 1)};
+  const char* const an[3] = {"x", "y", "z"};
+  for (int a = 0; a < 3; ++a) {
+    const std::string w = std::string("tracers: box ") + an[a] + ": ";
+    if (!std::isfinite(s->lo[a])) { err = w + "lo = " + num(s->lo[a]) + " (must be finite)"; return EKPNP_ERR_INVALID; }
+    if (!std::isfinite(s->hi[a])) { err = w + "hi = " + num(s->hi[a]) + " (must be finite)"; return EKPNP_ERR_INVALID; }
+    if (!(s->hi[a] > s->lo[a])) { err = w + "hi = " + num(s->hi[a]) + " is not above lo = " + num(s->lo[a]); return EKPNP_ERR_INVALID; }
+    if (s->lo[a] < 0.0) { err = w + "lo = " + num(s->lo[a]) + " below 0"; return EKPNP_ERR_INVALID; }
+    if (s->hi[a] > top[a]) { err = w + "hi = " + num(s->hi[a]) + " above " + num(top[a]); return EKPNP_ERR_INVALID; }
+  }
+  return EKPNP_OK;
+}
+
+static inline double tr_period(const ekpnp_params& p, int axis) { return axis == 0 ? (double)p.nx : axis == 1 ? (double)p.ny : INFINITY; }
+
+// GRID: coordinate i of g along an axis (host arithmetic, the device indexes the table)
+static double tr_grid_value(int i, int g, double lo, double hi, double period) {
+  const double w = hi - lo;
+  const double c = (double)i + 0.5;
+  const double m = c * w;
+  const double q = m / (double)g;
+  const double v = lo + q;
+  return (v >= hi || v >= period) ? lo : v;
+}
+
+// all three NaN, or inside the invariant
+static bool tr_position_ok(const ekpnp_params& p, double x, double y, double z) {
+  if (x != x && y != y && z != z) return true;
+  return x >= 0.0 && x < (double)p.nx && y >= 0.0 && y < (double)p.ny && z >= 0.0 && z <= (double)(p.nz - 1);
+}
+
+static int tracers_check_cells(const ekpnp_params& p, int bx, int by, int bz, std::string& err) {
+  if (int rc = tracers_check_lattice(p, err)) return rc;
+  if (bx < 1 || bx > p.nx) { err = "tracers: bx = " + std::to_string(bx) + " outside 1 .. " + std::to_string(p.nx); return EKPNP_ERR_INVALID; }
+  if (by < 1 || by > p.ny) { err = "tracers: by = " + std::to_string(by) + " outside 1 .. " + std::to_string(p.ny); return EKPNP_ERR_INVALID; }
+  if (bz < 1 || bz > p.nz - 1) { err = "tracers: bz = " + std::to_string(bz) + " outside 1 .. " + std::to_string(p.nz - 1); return EKPNP_ERR_INVALID; }
+  const long long cells = (long long)bx * by * bz;
+  if (cells > EKPNP_TRACERS_MAX_CELLS) { err = "tracers: bx*by*bz = " + std::to_string(cells) + " above " + std::to_string(EKPNP_TRACERS_MAX_CELLS); return EKPNP_ERR_INVALID; }
+  return EKPNP_OK;
+}
+
+static int tracers_check_advance(double mu, double h, int nsub, std::string& err) {
+  if (!std::isfinite(mu)) { err = "tracers: mu = " + num(mu) + " (must be finite)"; return EKPNP_ERR_INVALID; }
+  if (!std::isfinite(h)) { err = "tracers: h = " + num(h) + " (must be finite)"; return EKPNP_ERR_INVALID; }
+  if (nsub < 1 || nsub > 4096) { err = "tracers: nsub = " + std::to_string(nsub) + " outside 1 .. 4096"; return EKPNP_ERR_INVALID; }
+  return EKPNP_OK;
+}
+
+static TrStep tr_step_of(const ekpnp_params& p, double mu, double h, int nsub) {
+  TrStep s{};
+  s.hx = h / p.dx;
+  s.hy = h / p.dy;
+  s.hz = h / p.dz;
+  s.ax = 0.5 * s.hx;
+  s.ay = 0.5 * s.hy;
+  s.az = 0.5 * s.hz;
+  s.mu = mu;
+  s.nx = p.nx;
+  s.ny = p.ny;
+  s.nz = p.nz;
+  s.nsub = nsub;
+  return s;
+}
+
+}  // namespace ekpnp
+
+// ---- host only ---------------------------------------------------------------------------------------------------------------
+
+extern "C" int ekpnp_tracers_spec_check(const ekpnp_params* p, const ekpnp_tracers_spec* spec) {
+  std::string err;
+  int rc = EKPNP_ERR_INVALID;
+  if (!p) err = "tracers: NULL parameters";
+  else rc = tracers_check_spec(*p, spec, err);
+  if (rc) set_create_error(err);
+  return rc;
+}
+
+extern "C" int ekpnp_tracers_seed_host(const ekpnp_params* p, const ekpnp_tracers_spec* spec, int64_t first, int64_t count, double* x, double* y, double* z) {
+  if (int rc = ekpnp_tracers_spec_check(p, spec)) return rc;
+  if (first < 0 || count < 0 || first > spec->n || count > spec->n - first) {
+    set_create_error("tracers: particles " + std::to_string((long long)first) + " .. " + std::to_string((long long)(first + count - 1)) + " are not inside n = " + std::to_string((long long)spec->n));
+    return EKPNP_ERR_INVALID;
+  }
+  if (count == 0) return EKPNP_OK;
+  if (!x || !y || !z) { set_create_error("tracers: NULL pointer"); return EKPNP_ERR_INVALID; }
+  double* const out[3] = {x, y, z};
+  if (spec->mode == EKPNP_TRACERS_GRID) {
+    const int g[3] = {spec->gx, spec->gy, spec->gz};
+    for (int64_t q = 0; q < count; ++q) {
+      const int64_t pi = first + q, row = pi / g[0];
+      const int idx[3] = {(int)(pi - row * g[0]), (int)(row % g[1]), (int)(row / g[1])};
+      for (int a = 0; a < 3; ++a) out[a][q] = tr_grid_value(idx[a], g[a], spec->lo[a], spec->hi[a], tr_period(*p, a));
+    }
+  } else {
+    for (int a = 0; a < 3; ++a) {
+      const double t = spec->hi[a] - spec->lo[a];
+      for (int64_t q = 0; q < count; ++q) out[a][q] = tr_seed_random(spec->seed, (uint64_t)(first + q), a, spec->lo[a], spec->hi[a], t, tr_period(*p, a));
+    }
+  }
+  return EKPNP_OK;
+}
+
+extern "C" int ekpnp_tracers_advance_host(const ekpnp_params* p, const double* ux, const double* uy, const double* uz, const double* ex, const double* ey,
+                                          const double* ez, double mu, double h, int nsub, int64_t n, double* x, double* y, double* z, int32_t* wx, int32_t* wy) {
+  std::string err;
+  int rc = EKPNP_ERR_INVALID;
+  if (!p) err = "tracers: NULL parameters";
+  else if ((rc = tracers_check_lattice(*p, err)) == EKPNP_OK && (rc = tracers_check_advance(mu, h, nsub, err)) == EKPNP_OK) {
+    if (n < 0 || n > EKPNP_TRACERS_MAX_N) { err = "tracers: n = " + std::to_string((long long)n) + " outside 0 .. " + std::to_string((long long)EKPNP_TRACERS_MAX_N); rc = EKPNP_ERR_INVALID; }
+    else if (!ux || !uy || !uz || !x || !y || !z || !wx || !wy || (mu != 0.0 && (!ex || !ey || !ez))) { err = "tracers: NULL pointer"; rc = EKPNP_ERR_INVALID; }
+  }
+  if (rc) { set_create_error(err); return rc; }
+  const TrFields f{{ux, uy, uz}, {ex, ey, ez}};
+  const TrStep s = tr_step_of(*p, mu, h, nsub);
+  for (int64_t i = 0; i < n; ++i) {
+    if (tr_lost(x[i], y[i], z[i])) continue;
+    int a = wx[i], b = wy[i];
+    if (mu != 0.0) tr_advance<true>(f, s, x[i], y[i], z[i], a, b);
+    else tr_advance<false>(f, s, x[i], y[i], z[i], a, b);
+    wx[i] = a;
+    wy[i] = b;
+  }
+  return EKPNP_OK;
+}
+
+extern "C" int ekpnp_tracers_cell(const ekpnp_params* p, int bx, int by, int bz, double x, double y, double z) {
+  std::string err;
+  if (!p) { set_create_error("tracers: NULL parameters"); return -2; }
+  if (tracers_check_cells(*p, bx, by, bz, err)) { set_create_error(err); return -2; }
+  return tr_cell(p->nx, p->ny, p->nz, bx, by, bz, x, y, z);
+}
+
+// ---- the cloud ---------------------------------------------------------------------------------------------------------------
+
+#define NEEDSINGLE(ctx) \
+  NEEDCTX(ctx);         \
+  if (c.slab) return fail(c, kSlabMsg)
+
+static int need_tracers(Ctx& c) {
+  if (c.tracers) return EKPNP_OK;
+  if (int rc = tracers_check_lattice(c.p, c.err)) return rc;
+  c.tracers = new (std::nothrow) TracerState();
+  if (!c.tracers) { c.err = "host allocation failed"; return EKPNP_ERR_NOMEM; }
+  return EKPNP_OK;
+}
+
+// a cloud of n particles (the old allocation if n is unchanged; otherwise the stream is waited for: a pass may still read it)
+static int tracers_alloc(Ctx& c, long long n) {
+  if (int rc = need_tracers(c)) return rc;
+  TracerState& t = *c.tracers;
+  if (t.cloud && t.n == n) return EKPNP_OK;
+  HIPCHK(c, hipStreamSynchronize(c.stream));
+  if (t.cloud) { (void)hipFree(t.cloud); c.bytes -= t.cloud_bytes; t.cloud = nullptr; t.cloud_bytes = 0; t.n = 0; t.part = nullptr; }
+  const int nwg = (int)((n + TR_CHUNK - 1) / TR_CHUNK);
+  const size_t bytes = (size_t)n * 56 + ((size_t)nwg + 1) * NM * sizeof(double);  // (56 n is a multiple of 8: the partials are aligned)
+  HIPCHK(c, hipMalloc(&t.cloud, bytes));
+  t.cloud_bytes = bytes;
+  c.bytes += bytes;
+  t.n = n;
+  t.nwg = nwg;
+  t.part = (double*)((char*)t.cloud + (size_t)n * 56);
+  return EKPNP_OK;
+}
+
+static inline TracerState* cloud_of(Ctx& c) { return c.tracers && c.tracers->cloud ? c.tracers : nullptr; }
+static inline unsigned tr_blocks(long long n, int per) { return (unsigned)((n + per - 1) / per); }
+
+// upload a whole cloud from host arrays (synchronous)
+static int tracers_upload(Ctx& c, long long n, const double* const pos[6], const int32_t* wx, const int32_t* wy) {
+  if (int rc = tracers_alloc(c, n)) return rc;
+  const TrCloud d = c.tracers->dev();
+  double* const dst[6] = {d.x, d.y, d.z, d.x0, d.y0, d.z0};
+  for (int a = 0; a < 6; ++a) HIPCHK(c, hipMemcpyAsync(dst[a], pos[a], (size_t)n * sizeof(double), hipMemcpyHostToDevice, c.stream));
+  if (wx) {
+    HIPCHK(c, hipMemcpyAsync(d.wx, wx, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c.stream));
+    HIPCHK(c, hipMemcpyAsync(d.wy, wy, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c.stream));
+  } else {
+    HIPCHK(c, hipMemsetAsync(d.wx, 0, 2 * (size_t)n * sizeof(int32_t), c.stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c.stream));
+  return EKPNP_OK;
+}
+
+extern "C" int ekpnp_tracers_seed(ekpnp_ctx* ctx, const ekpnp_tracers_spec* spec) {
+  NEEDSINGLE(ctx);
+  if (int rc = tracers_check_spec(c.p, spec, c.err)) return rc;
+  if (int rc = tracers_alloc(c, (long long)spec->n)) return rc;
+  TracerState& t = *c.tracers;
+  TrSeedArgs a{};
+  for (int q = 0; q < 3; ++q) {
+    a.lo[q] = spec->lo[q];
+    a.hi[q] = spec->hi[q];
+    a.t[q] = spec->hi[q] - spec->lo[q];
+    a.period[q] = tr_period(c.p, q);
+  }
+  a.seed = spec->seed;
+  a.mode = spec->mode;
+  a.gx = spec->gx;
+  a.gy = spec->gy;
+  a.gz = spec->gz;
+  if (spec->mode == EKPNP_TRACERS_GRID) {
+    const size_t need = (size_t)spec->gx + (size_t)spec->gy + (size_t)spec->gz;
+    if (need > t.tab_doubles) {
+      HIPCHK(c, hipStreamSynchronize(c.stream));  // an earlier seed may still read the old tables
+      if (t.tab) { (void)hipFree(t.tab); c.bytes -= t.tab_doubles * sizeof(double); t.tab = nullptr; }
+      if (t.tab_host) { (void)hipHostFree(t.tab_host); t.tab_host = nullptr; }
+      t.tab_doubles = 0;
+      HIPCHK(c, hipMalloc((void**)&t.tab, need * sizeof(double)));
+      t.tab_doubles = need;
+      c.bytes += need * sizeof(double);
+      HIPCHK(c, hipHostMalloc((void**)&t.tab_host, need * sizeof(double), hipHostMallocDefault));
+      if (!t.landed) HIPCHK(c, hipEventCreateWithFlags(&t.landed, hipEventDisableTiming));
+    } else {
+      if (!t.tab || !t.tab_host || !t.landed) { c.err = "tracers: the table buffer could not be made earlier"; return EKPNP_ERR_HIP; }
+      HIPCHK(c, hipEventSynchronize(t.landed));  // the previous upload has left the pinned twin (not a wait for the stream)
+    }
+    const int g[3] = {spec->gx, spec->gy, spec->gz};
+    double* h = t.tab_host;
+    for (int q = 0; q < 3; ++q)
+      for (int i = 0; i < g[q]; ++i) *h++ = tr_grid_value(i, g[q], spec->lo[q], spec->hi[q], a.period[q]);
+    HIPCHK(c, hipMemcpyAsync(t.tab, t.tab_host, need * sizeof(double), hipMemcpyHostToDevice, c.stream));
+    HIPCHK(c, hipEventRecord(t.landed, c.stream));
+    a.tab = t.tab;
+  }
+  hipLaunchKernelGGL(k_tracers_seed, dim3(tr_blocks(t.n, TR_THREADS)), dim3(TR_THREADS), 0, c.stream, a, t.dev());
+  note_launch(c, "k_tracers_seed");
+  if (take_launch_error(c) != hipSuccess) return EKPNP_ERR_HIP;
+  return EKPNP_OK;
+}
+
+extern "C" int ekpnp_tracers_set(ekpnp_ctx* ctx, int64_t n, const double* x, const double* y, const double* z) {
+  NEEDSINGLE(ctx);
+  if (n < 1 || n > EKPNP_TRACERS_MAX_N) { c.err = "tracers: n = " + std::to_string((long long)n) + " outside 1 .. " + std::to_string((long long)EKPNP_TRACERS_MAX_N); return EKPNP_ERR_INVALID; }
+  if (!x || !y || !z) return fail(c, "NULL pointer");
+  if (int rc = tracers_check_lattice(c.p, c.err)) return rc;
+  for (int64_t i = 0; i < n; ++i)
+    if (!tr_position_ok(c.p, x[i], y[i], z[i])) {
+      c.err = "tracers: particle " + std::to_string((long long)i) + " at (" + num(x[i]) + ", " + num(y[i]) + ", " + num(z[i]) + ") is outside the lattice";
+      return EKPNP_ERR_INVALID;
+    }
+  const double* const pos[6] = {x, y, z, x, y, z};
+  return tracers_upload(c, (long long)n, pos, nullptr, nullptr);
+}
+
+extern "C" int ekpnp_tracers_get(ekpnp_ctx* ctx, double* x, double* y, double* z, int32_t* wx, int32_t* wy) {
+  NEEDSINGLE(ctx);
+  TracerState* t = cloud_of(c);
+  if (!t) return fail(c, "tracers: no cloud (seed, set or load one first)");
+  const TrCloud d = t->dev();
+  const size_t n = (size_t)t->n;
+  if (x) HIPCHK(c, hipMemcpyAsync(x, d.x, n * sizeof(double), hipMemcpyDeviceToHost, c.stream));
+  if (y) HIPCHK(c, hipMemcpyAsync(y, d.y, n * sizeof(double), hipMemcpyDeviceToHost, c.stream));
+  if (z) HIPCHK(c, hipMemcpyAsync(z, d.z, n * sizeof(double), hipMemcpyDeviceToHost, c.stream));
+  if (wx) HIPCHK(c, hipMemcpyAsync(wx, d.wx, n * sizeof(int32_t), hipMemcpyDeviceToHost, c.stream));
+  if (wy) HIPCHK(c, hipMemcpyAsync(wy, d.wy, n * sizeof(int32_t), hipMemcpyDeviceToHost, c.stream));
+  HIPCHK(c, hipStreamSynchronize(c.stream));
+  return EKPNP_OK;
+}
+
+extern "C" int ekpnp_tracers_size(ekpnp_ctx* ctx, int64_t* n) {
+  NEEDSINGLE(ctx);
+  if (!n) return fail(c, "NULL pointer");
+  TracerState* t = cloud_of(c);
+  *n = t ? (int64_t)t->n : 0;
+  return EKPNP_OK;
+}
+
+extern "C" int ekpnp_tracers_release(ekpnp_ctx* ctx) {
+  NEEDSINGLE(ctx);
+  if (!c.tracers) return EKPNP_OK;
+  HIPCHK(c, hipStreamSynchronize(c.stream));
+  tracers_release(c);
+  return EKPNP_OK;
+}
+
+extern "C" int ekpnp_tracers_advance(ekpnp_ctx* ctx, double mu, double h, int nsub) {
+  NEEDSINGLE(ctx);
+  if (int rc = tracers_check_advance(mu, h, nsub, c.err)) return rc;
+  TracerState* t = cloud_of(c);
+  if (!t) return fail(c, "tracers: no cloud (seed, set or load one first)");
+  const bool mob = mu != 0.0;
+  if (mob)
+    if (int rc = ensure_efield(c)) return rc;  // the arrays as ekpnp_get_field would return them (mu == 0: lazy E is left alone)
+  const TrFields f{{c.fld[EKPNP_UX], c.fld[EKPNP_UY], c.fld[EKPNP_UZ]}, {c.fld[EKPNP_EX], c.fld[EKPNP_EY], c.fld[EKPNP_EZ]}};
+  const TrStep s = tr_step_of(c.p, mu, h, nsub);
+  const dim3 grid(tr_blocks(t->n, TR_THREADS)), block(TR_THREADS);
+  if (mob) hipLaunchKernelGGL((k_tracers_advance<true>), grid, block, 0, c.stream, f, s, t->dev());
+  else hipLaunchKernelGGL((k_tracers_advance<false>), grid, block, 0, c.stream, f, s, t->dev());
+  note_launch(c, "k_tracers_advance");
+  if (take_launch_error(c) != hipSuccess) return EKPNP_ERR_HIP;
+  return EKPNP_OK;
+}
+
+// ---- the cloud's file --------------------------------------------------------------------------------------------------------
+
+namespace {
+struct TracerHeader {
+  char magic[8];
+  int32_t nx, ny, nz, reserved;
+  int64_t n;
+  double time;
+  int64_t reserved2;
+};
+static_assert(sizeof(TracerHeader) == 48, "tracer file header layout");
+constexpr char kTracerMagic[9] = "EKPNPTR1";
+}  // namespace
+
+extern "C" int ekpnp_tracers_save(ekpnp_ctx* ctx, const char* path, double time) {
+  NEEDSINGLE(ctx);
+  if (!path) return fail(c, "NULL path");
+  TracerState* t = cloud_of(c);
+  if (!t) return fail(c, "tracers: no cloud (seed, set or load one first)");
+  const size_t n = (size_t)t->n;
+  HIPCHK(c, hipStreamSynchronize(c.stream));
+  FILE* f = std::fopen(path, "wb");
+  if (!f) return fail(c, "cannot open tracer file");
+  TracerHeader h{};
+  std::memcpy(h.magic, kTracerMagic, 8);
+  h.nx = c.p.nx; h.ny = c.p.ny; h.nz = c.p.nz;
+  h.n = (int64_t)n;
+  h.time = time;
+  bool ok = std::fwrite(&h, sizeof h, 1, f) == 1;
+  std::vector<double> buf(n);
+  const TrCloud d = t->dev();
+  const double* const src[6] = {d.x, d.y, d.z, d.x0, d.y0, d.z0};
+  for (int a = 0; a < 6 && ok; ++a) {
+    if (hipMemcpy(buf.data(), src[a], n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) { std::fclose(f); return fail(c, "tracers: copy from the device failed"); }
+    ok = std::fwrite(buf.data(), sizeof(double), n, f) == n;
+  }
+  const int32_t* const wsrc[2] = {d.wx, d.wy};
+  for (int a = 0; a < 2 && ok; ++a) {
+    if (hipMemcpy(buf.data(), wsrc[a], n * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) { std::fclose(f); return fail(c, "tracers: copy from the device failed"); }
+    ok = std::fwrite(buf.data(), sizeof(int32_t), n, f) == n;
+  }
+  if (std::fclose(f) != 0 || !ok) return fail(c, "write error on tracer file");
+  return EKPNP_OK;
+}
+
+extern "C" int ekpnp_tracers_load(ekpnp_ctx* ctx, const char* path, double* time) {
+  NEEDSINGLE(ctx);
+  if (!path || !time) return fail(c, "NULL pointer");
+  FILE* f = std::fopen(path, "rb");
+  if (!f) return fail(c, "cannot open tracer file");
+  TracerHeader h{};
+  if (std::fread(&h, sizeof h, 1, f) != 1 || std::memcmp(h.magic, kTracerMagic, 8) != 0) { std::fclose(f); return fail(c, "tracers: not a tracer file (EKPNPTR1)"); }
+  if (h.nx != c.p.nx || h.ny != c.p.ny || h.nz != c.p.nz) {
+    std::fclose(f);
+    c.err = "tracers: the file holds a cloud of lattice " + std::to_string(h.nx) + " x " + std::to_string(h.ny) + " x " + std::to_string(h.nz) + ", not of " +
+            std::to_string(c.p.nx) + " x " + std::to_string(c.p.ny) + " x " + std::to_string(c.p.nz);
+    return EKPNP_ERR_INVALID;
+  }
+  if (h.n < 1 || h.n > EKPNP_TRACERS_MAX_N) { std::fclose(f); c.err = "tracers: n = " + std::to_string((long long)h.n) + " in the file, outside 1 .. " + std::to_string((long long)EKPNP_TRACERS_MAX_N); return EKPNP_ERR_INVALID; }
+  const size_t n = (size_t)h.n;
+  std::vector<double> pos[6];
+  std::vector<int32_t> w[2];
+  bool ok = true;
+  for (int a = 0; a < 6 && ok; ++a) { pos[a].resize(n); ok = std::fread(pos[a].data(), sizeof(double), n, f) == n; }
+  for (int a = 0; a < 2 && ok; ++a) { w[a].resize(n); ok = std::fread(w[a].data(), sizeof(int32_t), n, f) == n; }
+  std::fclose(f);
+  if (!ok) { c.err = "tracers: the file is shorter than its " + std::to_string((long long)h.n) + " particles"; return EKPNP_ERR_INVALID; }
+  for (size_t i = 0; i < n; ++i)
+    if (!tr_position_ok(c.p, pos[0][i], pos[1][i], pos[2][i]) || !tr_position_ok(c.p, pos[3][i], pos[4][i], pos[5][i])) {
+      c.err = "tracers: particle " + std::to_string(i) + " of the file is outside the lattice";
+      return EKPNP_ERR_INVALID;
+    }
+  const double* const p6[6] = {pos[0].data(), pos[1].data(), pos[2].data(), pos[3].data(), pos[4].data(), pos[5].data()};
+  if (int rc = tracers_upload(c, (long long)n, p6, w[0].data(), w[1].data())) return rc;
+  *time = h.time;
+  return EKPNP_OK;
+}
+
+// ---- cell counts and moments -------------------------------------------------------------------------------------------------
+
+extern "C" int ekpnp_tracers_cell_counts(ekpnp_ctx* ctx, int bx, int by, int bz, int64_t* counts, int64_t* lost) {
+  NEEDSINGLE(ctx);
+  if (!counts || !lost) return fail(c, "NULL pointer");
+  if (int rc = tracers_check_cells(c.p, bx, by, bz, c.err)) return rc;
+  TracerState* t = cloud_of(c);
+  if (!t) return fail(c, "tracers: no cloud (seed, set or load one first)");
+  if (!t->cells) {
+    const size_t bytes = ((size_t)EKPNP_TRACERS_MAX_CELLS + 1) * sizeof(unsigned long long);
+    HIPCHK(c, hipMalloc((void**)&t->cells, bytes));
+    t->cells_bytes = bytes;
+    c.bytes += bytes;
+  }
+  const int cells = bx * by * bz;
+  HIPCHK(c, hipMemsetAsync(t->cells, 0, ((size_t)cells + 1) * sizeof(unsigned long long), c.stream));
+  const TrCloud d = t->dev();
+  const dim3 grid(tr_blocks(t->n, TR_THREADS * TR_CELL_PER_THREAD)), block(TR_THREADS);
+  if (cells + 1 <= TR_LDS_CELLS)
+    hipLaunchKernelGGL((k_tracers_cells<true>), grid, block, ((size_t)cells + 1) * sizeof(unsigned), c.stream, d.x, d.y, d.z, d.n, c.p.nx, c.p.ny, c.p.nz, bx, by, bz, cells, t->cells);
+  else
+    hipLaunchKernelGGL((k_tracers_cells<false>), grid, block, 0, c.stream, d.x, d.y, d.z, d.n, c.p.nx, c.p.ny, c.p.nz, bx, by, bz, cells, t->cells);
+  note_launch(c, "k_tracers_cells");
+  if (take_launch_error(c) != hipSuccess) return EKPNP_ERR_HIP;
+  std::vector<int64_t> h((size_t)cells + 1);
+  HIPCHK(c, hipMemcpyAsync(h.data(), t->cells, h.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c.stream));
+  HIPCHK(c, hipStreamSynchronize(c.stream));
+  for (int k = 0; k < cells; ++k) counts[k] = h[(size_t)k];
+  *lost = h[(size_t)cells];
+  return EKPNP_OK;
+}
+
+// enqueue the 12 moments of the cloud into `out` (device memory)
+static int tracers_enqueue_moments(Ctx& c, TracerState& t, double* out) {
+  hipLaunchKernelGGL(k_tracers_partials, dim3(t.nwg), dim3(TR_THREADS), 0, c.stream, t.dev(), c.p.nx, c.p.ny, t.part);
+  note_launch(c, "k_tracers_partials");
+  hipLaunchKernelGGL(k_tracers_finish, dim3(1), dim3(64), 0, c.stream, t.part, t.nwg, out);
+  note_launch(c, "k_tracers_finish");
+  if (take_launch_error(c) != hipSuccess) return EKPNP_ERR_HIP;
+  return EKPNP_OK;
+}
+
+extern "C" int ekpnp_tracers_moments(ekpnp_ctx* ctx, double* out) {
+  NEEDSINGLE(ctx);
+  if (!out) return fail(c, "NULL pointer");
+  TracerState* t = cloud_of(c);
+  if (!t) return fail(c, "tracers: no cloud (seed, set or load one first)");
+  if (int rc = tracers_enqueue_moments(c, *t, t->out())) return rc;
+  HIPCHK(c, hipMemcpyAsync(out, t->out(), NM * sizeof(double), hipMemcpyDeviceToHost, c.stream));
+  HIPCHK(c, hipStreamSynchronize(c.stream));
+  return EKPNP_OK;
+}
+
+// ---- the time series ---------------------------------------------------------------------------------------------------------
+
+extern "C" int ekpnp_tracers_arm(ekpnp_ctx* ctx, int capacity) {
+  NEEDSINGLE(ctx);
+  if (capacity < 1) { c.err = "tracers: capacity = " + std::to_string(capacity) + " (must be >= 1)"; return EKPNP_ERR_INVALID; }
+  if (int rc = need_tracers(c)) return rc;
+  return ring_arm(c, c.tracers->ring, capacity, NM * sizeof(double));
+}
+
+extern "C" int ekpnp_tracers_disarm(ekpnp_ctx* ctx) {
+  NEEDSINGLE(ctx);
+  if (c.tracers) c.tracers->ring.armed = false;  // the ring and its rows stay readable until the next arm
+  return EKPNP_OK;
+}
+
+extern "C" int ekpnp_tracers_record(ekpnp_ctx* ctx, int64_t step, double time) {
+  NEEDSINGLE(ctx);
+  if (!c.tracers || !c.tracers->ring.armed) return fail(c, "ekpnp_tracers_record: no ring armed");
+  TracerState* t = cloud_of(c);
+  if (!t) return fail(c, "tracers: no cloud (seed, set or load one first)");
+  if (int rc = tracers_enqueue_moments(c, *t, (double*)ring_next_row(t->ring))) return rc;
+  ring_note_row(t->ring, step, time);
+  return EKPNP_OK;
+}
+
+extern "C" int ekpnp_tracers_count(ekpnp_ctx* ctx, int64_t* recorded, int64_t* dropped) {
+  NEEDSINGLE(ctx);
+  ring_count(c.tracers ? &c.tracers->ring : nullptr, recorded, dropped);
+  return EKPNP_OK;
+}
+
+extern "C" int ekpnp_tracers_read(ekpnp_ctx* ctx, int64_t first, int count, int64_t* steps, double* times, double* values) {
+  NEEDSINGLE(ctx);
+  return ring_read(c, c.tracers ? &c.tracers->ring : nullptr, "ekpnp_tracers_read", first, count, steps, times, values);
+}
+
+extern "C" int ekpnp_tracers_ring_save(ekpnp_ctx* ctx, const char* path) {
+  NEEDSINGLE(ctx);
+  if (!path) return fail(c, "NULL path");
+  if (!c.tracers || !c.tracers->ring.ever_armed) return fail(c, "ekpnp_tracers_ring_save: no ring was armed");
+  int64_t rec = 0, dropped = 0;
+  ring_count(&c.tracers->ring, &rec, &dropped);
+  const int n = (int)(rec - dropped);
+  std::vector<int64_t> steps((size_t)n);
+  std::vector<double> times((size_t)n), values((size_t)n * NM);
+  if (int rc = ring_read(c, &c.tracers->ring, "ekpnp_tracers_ring_save", 0, n, steps.data(), times.data(), values.data())) return rc;
+  FILE* f = std::fopen(path, "wb");
+  if (!f) return fail(c, "cannot open tracers file");
+  std::fprintf(f, "# ekpnp tracers nx %d ny %d nz %d n %lld recorded %lld dropped %lld\n", c.p.nx, c.p.ny, c.p.nz, (long long)c.tracers->n, (long long)rec, (long long)dropped);
+  std::fprintf(f, "# step time");
+  for (int q = 0; q < NM; ++q) std::fprintf(f, " %s", kMomentNames[q]);
+  std::fprintf(f, "\n");
+  for (int r = 0; r < n; ++r) {
+    std::fprintf(f, "%lld %.17g", (long long)steps[(size_t)r], times[(size_t)r]);
+    for (int q = 0; q < NM; ++q) std::fprintf(f, " %.17g", values[(size_t)r * NM + q]);
+    std::fprintf(f, "\n");
+  }
+  const bool bad = std::ferror(f) != 0;
+  if (std::fclose(f) != 0 || bad) return fail(c, "write error on tracers file");
+  return EKPNP_OK;
+}

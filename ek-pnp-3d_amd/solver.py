@@ -383,6 +383,103 @@ def _section_spec_for(p: "Params", values, across, range, planes) -> SectionSpec
     return section_spec(values, a, range, planes, n=p.nx if a == ACROSS_X else p.ny)
 
 
+TRACERS_RANDOM, TRACERS_GRID = 0, 1  # include/ekpnp.h: EKPNP_TRACERS_*
+TRACERS_MAX_N = 1 << 28
+TRACERS_MAX_CELLS = 65536
+TRACER_MOMENTS = ["alive", "lost", "sum_dx", "sum_dy", "sum_dz", "sum_dx2", "sum_dy2", "sum_dz2", "sum_z", "sum_z2", "z_min", "z_max"]
+TRACER_MOMENT_ID = {n: i for i, n in enumerate(TRACER_MOMENTS)}
+
+
+class TracersSpec(C.Structure):
+    """Mirror of `ekpnp_tracers_spec` (include/ekpnp.h): n particles, random in a box or on a gx x gy x gz grid of cell centres, the
+    noise seed, and the box lo .. hi in lattice units (x, y, z)."""
+
+    _fields_ = [("n", C.c_int64), ("mode", C.c_int32), ("gx", C.c_int32), ("gy", C.c_int32), ("gz", C.c_int32), ("seed", C.c_uint64),
+                ("lo", C.c_double * 3), ("hi", C.c_double * 3)]
+
+
+def tracers_spec(n: int = None, grid=None, box=None, seed: int = 1, p: "Params" = None) -> TracersSpec:
+    """n random particles, or grid=(gx, gy, gz) cell centres (n = gx*gy*gz); box: ((x0, x1), (y0, y1), (z0, z1)) in lattice units,
+    default the interior [0, nx] x [0, ny] x [1, nz-2] of the lattice p"""
+    spec = TracersSpec()
+    if grid is not None:
+        spec.mode = TRACERS_GRID
+        spec.gx, spec.gy, spec.gz = (int(g) for g in grid)
+        spec.n = spec.gx * spec.gy * spec.gz if n is None else int(n)
+    else:
+        if n is None:
+            raise ValueError("tracers_spec: n or grid is needed")
+        spec.mode = TRACERS_RANDOM
+        spec.n = int(n)
+    if box is None:
+        if p is None:
+            raise ValueError("tracers_spec: box=None needs the lattice p")
+        box = ((0.0, p.nx), (0.0, p.ny), (1.0, p.nz - 2))
+    for a in range(3):
+        spec.lo[a], spec.hi[a] = float(box[a][0]), float(box[a][1])
+    spec.seed = int(seed)
+    return spec
+
+
+def _tracers_fail(L, name, rc):
+    raise EkpnpError(f"{name} -> status {rc}: {L.ekpnp_last_error(None).decode()}")
+
+
+def tracers_spec_check(p: "Params", spec: TracersSpec) -> TracersSpec:
+    """the spec, or EkpnpError with the library's message (ekpnp_tracers_spec_check: host arithmetic, no device)"""
+    L = load_library()
+    rc = L.ekpnp_tracers_spec_check(C.byref(p), C.byref(spec))
+    if rc:
+        _tracers_fail(L, "ekpnp_tracers_spec_check", rc)
+    return spec
+
+
+def tracers_seed_host(p: "Params", spec: TracersSpec, first: int = 0, count: int = None):
+    """(x, y, z) of particles first .. first + count - 1 of a seed: THE definition (ekpnp_tracers_seed_host, host only)"""
+    L = load_library()
+    if count is None:
+        count = int(spec.n) - int(first)
+    x, y, z = (np.zeros(max(int(count), 0), dtype=np.float64) for _ in range(3))
+    rc = L.ekpnp_tracers_seed_host(C.byref(p), C.byref(spec), int(first), int(count), _ptr(x), _ptr(y), _ptr(z))
+    if rc:
+        _tracers_fail(L, "ekpnp_tracers_seed_host", rc)
+    return x, y, z
+
+
+def tracers_advance_host(p: "Params", u, x, y, z, wx=None, wy=None, E=None, mu: float = 0.0, h: float = 0.0, nsub: int = 1):
+    """nsub midpoint substeps of h seconds through the frozen arrays u = (ux, uy, uz) [nz, ny, nx] (and E = (Ex, Ey, Ez) when
+    mu != 0): THE definition of an advance (ekpnp_tracers_advance_host, host only).  Returns new (x, y, z, wx, wy)."""
+    L = load_library()
+    shape = (p.nz, p.ny, p.nx)
+    u = [np.ascontiguousarray(a, dtype=np.float64).reshape(shape) for a in u]
+    e = [None] * 3 if E is None else [np.ascontiguousarray(a, dtype=np.float64).reshape(shape) for a in E]
+    x, y, z = (np.array(a, dtype=np.float64).ravel() for a in (x, y, z))
+    n = x.size
+    wx = np.zeros(n, dtype=np.int32) if wx is None else np.array(wx, dtype=np.int32).ravel()
+    wy = np.zeros(n, dtype=np.int32) if wy is None else np.array(wy, dtype=np.int32).ravel()
+    if not (y.size == z.size == wx.size == wy.size == n):
+        raise ValueError("tracers_advance_host: x, y, z, wx, wy differ in length")
+    rc = L.ekpnp_tracers_advance_host(C.byref(p), *[_ptr(a) for a in u], *[None if a is None else _ptr(a) for a in e], float(mu), float(h), int(nsub),
+                                      n, _ptr(x), _ptr(y), _ptr(z), _ptr(wx), _ptr(wy))
+    if rc:
+        _tracers_fail(L, "ekpnp_tracers_advance_host", rc)
+    return x, y, z, wx, wy
+
+
+def tracers_cell(p: "Params", cells, x, y, z) -> np.ndarray:
+    """the cell (cz*by + cy)*bx + cx of every position in a cells = (bx, by, bz) partition, -1 for a lost particle: THE definition
+    (ekpnp_tracers_cell, host only)"""
+    L = load_library()
+    bx, by, bz = (int(b) for b in cells)
+    x, y, z = (np.asarray(a, dtype=np.float64).ravel() for a in (x, y, z))
+    out = np.empty(x.size, dtype=np.int64)
+    for i in range(x.size):
+        out[i] = L.ekpnp_tracers_cell(C.byref(p), bx, by, bz, float(x[i]), float(y[i]), float(z[i]))
+    if x.size and out.min() < -1:
+        _tracers_fail(L, "ekpnp_tracers_cell", 1)
+    return out
+
+
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
@@ -860,6 +957,27 @@ def load_library():
         "ekpnp_section_sum": (dbl, [C.c_void_p, C.c_ssize_t, i32]),
         "ekpnp_section_spec_check": (i32, [C.POINTER(Params), C.POINTER(SectionSpec)]),
         "ekpnp_section_extent": (i32, [C.POINTER(Params), C.POINTER(SectionSpec), C.POINTER(i32), C.POINTER(i32)]),
+        # Lagrangian tracers: single contexts only (tracers.hip; no group spellings)
+        "ekpnp_tracers_spec_check": (i32, [C.POINTER(Params), C.POINTER(TracersSpec)]),
+        "ekpnp_tracers_seed_host": (i32, [C.POINTER(Params), C.POINTER(TracersSpec), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "ekpnp_tracers_advance_host": (i32, [C.POINTER(Params)] + [C.c_void_p] * 6 + [dbl, dbl, i32, C.c_int64] + [C.c_void_p] * 5),
+        "ekpnp_tracers_cell": (i32, [C.POINTER(Params), i32, i32, i32, dbl, dbl, dbl]),
+        "ekpnp_tracers_seed": (i32, [ctx, C.POINTER(TracersSpec)]),
+        "ekpnp_tracers_set": (i32, [ctx, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "ekpnp_tracers_get": (i32, [ctx] + [C.c_void_p] * 5),
+        "ekpnp_tracers_size": (i32, [ctx, C.POINTER(C.c_int64)]),
+        "ekpnp_tracers_release": (i32, [ctx]),
+        "ekpnp_tracers_advance": (i32, [ctx, dbl, dbl, i32]),
+        "ekpnp_tracers_save": (i32, [ctx, C.c_char_p, dbl]),
+        "ekpnp_tracers_load": (i32, [ctx, C.c_char_p, pd]),
+        "ekpnp_tracers_cell_counts": (i32, [ctx, i32, i32, i32, C.c_void_p, C.POINTER(C.c_int64)]),
+        "ekpnp_tracers_moments": (i32, [ctx, C.c_void_p]),
+        "ekpnp_tracers_arm": (i32, [ctx, i32]),
+        "ekpnp_tracers_disarm": (i32, [ctx]),
+        "ekpnp_tracers_record": (i32, [ctx, C.c_int64, dbl]),
+        "ekpnp_tracers_count": (i32, [ctx, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+        "ekpnp_tracers_read": (i32, [ctx, C.c_int64, i32, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "ekpnp_tracers_ring_save": (i32, [ctx, C.c_char_p]),
     }
     # the diagnostics a context and a group both have: ekpnp_<name>(ctx, ...) and ekpnp_group_<name>(group, ...) with the same arguments
     series = {  # the verbs of a time series on a ring (csrc/ring.h)
@@ -1161,6 +1279,89 @@ class Solver(_Diagnostics):
         self._ck(self._L.ekpnp_snapshot_read(self._h, C.byref(spec), out.ctypes.data_as(C.c_void_p), C.byref(k0), C.byref(kn)))
         assert (k0.value, kn.value) == self.snapshot_planes(spec.cz)
         return {n: out[i] for i, n in enumerate(names)}
+
+    # -- Lagrangian tracers: one particle cloud per single context (tracers.hip; slab contexts and groups are refused) --
+    def tracers_seed(self, spec: TracersSpec = None, **kw):
+        """make the cloud on the device: tracers_seed(spec) or tracers_seed(n=..., grid=..., box=..., seed=...); enqueues only"""
+        if spec is None:
+            spec = tracers_spec(p=self.p, **kw)
+        self._call("tracers_seed", C.byref(spec))
+
+    def tracers_set(self, x, y, z):
+        """replace the cloud by these positions (lattice units; all-NaN: a lost particle); start positions = positions, image counts 0"""
+        x, y, z = (np.ascontiguousarray(a, dtype=np.float64).ravel() for a in (x, y, z))
+        if not (x.size == y.size == z.size):
+            raise ValueError("tracers_set: x, y, z differ in length")
+        self._call("tracers_set", x.size, _ptr(x), _ptr(y), _ptr(z))
+
+    @property
+    def tracers_size(self) -> int:
+        n = C.c_int64()
+        self._call("tracers_size", C.byref(n))
+        return int(n.value)
+
+    def tracers_get(self):
+        """(x, y, z, wx, wy): positions in lattice units (NaN: lost) and the counts of periodic images crossed; synchronises"""
+        n = self.tracers_size
+        x, y, z = (np.empty(n, dtype=np.float64) for _ in range(3))
+        wx, wy = (np.empty(n, dtype=np.int32) for _ in range(2))
+        self._call("tracers_get", _ptr(x), _ptr(y), _ptr(z), _ptr(wx), _ptr(wy))
+        return x, y, z, wx, wy
+
+    def tracers_release(self):
+        self._call("tracers_release")
+
+    def tracers_advance(self, h: float, nsub: int = 1, mu: float = 0.0):
+        """nsub midpoint substeps of h seconds through the current, frozen fields with velocity u + mu E; enqueues only (place it
+        between two step() calls).  mu != 0 brings a lazy solve's E arrays up to date first."""
+        self._call("tracers_advance", float(mu), float(h), int(nsub))
+
+    def tracers_save(self, path: str, time: float = 0.0):
+        self._call("tracers_save", os.fsencode(path), float(time))
+
+    def tracers_load(self, path: str) -> float:
+        t = C.c_double()
+        self._call("tracers_load", os.fsencode(path), C.byref(t))
+        return t.value
+
+    def tracers_cell_counts(self, cells):
+        """(counts [bz, by, bx] int64, lost): the alive particles per cell of a cells = (bx, by, bz) partition; exact"""
+        bx, by, bz = (int(b) for b in cells)
+        counts, lost = np.zeros((max(bz, 0), max(by, 0), max(bx, 0)), dtype=np.int64), C.c_int64()
+        self._call("tracers_cell_counts", bx, by, bz, _ptr(counts), C.byref(lost))
+        return counts, int(lost.value)
+
+    def tracers_moments(self) -> np.ndarray:
+        """the len(TRACER_MOMENTS) moments of the cloud, now (unwrapped displacements in lattice units); complete on return"""
+        out = np.zeros(len(TRACER_MOMENTS), dtype=np.float64)
+        self._call("tracers_moments", _ptr(out))
+        return out
+
+    def tracers_arm(self, capacity: int = 1024):
+        """allocate the ring of rows of len(TRACER_MOMENTS) moments; rows are appended by tracers_record() only"""
+        self._call("tracers_arm", int(capacity))
+
+    def tracers_disarm(self):
+        self._call("tracers_disarm")
+
+    def tracers_record(self, step: int, time: float):
+        """append the cloud's moments with the caller's labels; enqueues only"""
+        self._call("tracers_record", int(step), float(time))
+
+    def tracers_count(self):
+        """(rows recorded since arming, rows lost to overflow)"""
+        return self._count("tracers_count")
+
+    def tracers_read(self, first: int = 0, count: int = None):
+        """(steps, times, values [count, len(TRACER_MOMENTS)]) of the held rows first .. first + count - 1, oldest first"""
+        if count is None:
+            r, d = self.tracers_count()
+            count = r - d - first
+        return self._read("tracers_read", first, count, ((len(TRACER_MOMENTS),), np.float64))
+
+    def tracers_ring_save(self, path: str):
+        """the ring as text: two header lines, then one row "step time moments ..." per held sample (ekpnp_tracers_ring_save)"""
+        self._call("tracers_ring_save", os.fsencode(path))
 
     def tune(self, knob: str, value: int):
         self._ck(self._L.ekpnp_tune(self._h, knob.encode(), int(value)))

@@ -695,6 +695,117 @@ int ekpnp_section_count(const ekpnp_ctx* ctx, int64_t* recorded, int64_t* droppe
 int ekpnp_section_read(ekpnp_ctx* ctx, int64_t first, int count, int64_t* steps, double* times, double* values);
 int ekpnp_section_ring_save(ekpnp_ctx* ctx, const char* path);
 
+/* ---- Lagrangian tracers: one particle cloud per context, advected on the device (no reference counterpart) ----
+ * Every diagnostic above is Eulerian.  What a mixing channel is built for needs trajectories: dispersion against time, a dye
+ * blob stirred by the rolls, the path of a marker bead that drifts with u + mu E.  The cloud lives in device memory, structure
+ * of arrays, 56 B per particle (1 <= n <= 2^28): x, y, z (doubles, LATTICE UNITS), the counts wx, wy (int32) of periodic images
+ * crossed, and the start position x0, y0, z0 (fixed when the cloud is seeded, set or loaded).  Invariant: 0 <= x < nx,
+ * 0 <= y < ny, 0 <= z <= nz-1 - or all three NaN: the particle is LOST.
+ * SCOPE: single contexts only.  A context made by ekpnp_create_slab (any nranks) or held by a group is refused by every call
+ * below that takes a context: EKPNP_ERR_INVALID, "tracers: slab contexts are not supported" (a stencil crosses slab cuts and
+ * particles migrate between ranks); there are no ekpnp_group_ spellings.
+ * AN ADVANCE - ekpnp_tracers_advance_host IS the definition, and the device leaves exactly its bits.  Inputs: the whole-lattice
+ * arrays ux, uy, uz [nz][ny][nx] as ekpnp_get_field returns them, optionally Ex, Ey, Ez and a mobility mu (m^2/V/s; mu == 0.0
+ * is a passive tracer: the E arrays are neither needed nor read), a substep h in seconds (finite, negative allowed) and
+ * nsub in 1 .. 4096.  The fields are frozen during the call.  The host forms hx = h/dx, hy = h/dy, hz = h/dz and ax = 0.5*hx,
+ * ay = 0.5*hy, az = 0.5*hz once.  Per particle and substep, every operation rounded once, no fused multiply-add:
+ *  1. a lost particle is skipped: nothing is read, nothing is written.
+ *  2. the stencil at (x, y, z): i0 = (int)x; fx = x - (double)i0; i1 = (i0 + 1 == nx) ? 0 : i0 + 1; j0, fy, j1 likewise with ny;
+ *     k0 = (int)z; if (k0 > nz-2) k0 = nz-2; fz = z - (double)k0; k1 = k0 + 1 (z == nz-1 gives fz == 1.0).
+ *  3. the value of an array a there, with L(p, q, f) meaning d = q - p; t = f*d; r = p + t:
+ *     a00 = L(a[k0][j0][i0], a[k0][j0][i1], fx), a10 likewise on row j1, a01 and a11 likewise on plane k1;
+ *     b0 = L(a00, a10, fy); b1 = L(a01, a11, fy); v = L(b0, b1, fz).
+ *  4. the velocity component c: w = v(u_c); if mu != 0.0: t = mu*v(E_c); w = w + t.
+ *  5. midpoint step: w at (x, y, z); x1 = x + ax*wx (t = ax*wx; x1 = x + t), y1, z1 likewise; (x1, y1, z1) is folded (6) without
+ *     touching the image counts - if that loses it, the particle is lost.  w' at the folded midpoint; x = x + hx*w'x and
+ *     likewise y, z, FROM THE ORIGINAL x, y, z; folded again, now counting the images.
+ *  6. the fold of a periodic coordinate x with n = (double)nx and its count w:
+ *       if (x >= n) { x = x - n; w += 1; } else if (x < 0.0) { x = x + n; w -= 1; }
+ *       if (x >= n) { x = x - n; w += 1; }
+ *       if (!(x >= 0.0 && x < n)) the particle is lost
+ *     (every x in [-n, 2n] ends in [0, n); more than one period per substep loses the particle).  z: a NaN or infinite z loses
+ *     the particle; else if (z < 0.0) z = 0.0; if (z > (double)(nz-1)) z = (double)(nz-1) - the plates hold a particle.
+ *  7. losing a particle: all three coordinates become NaN, the image counts stay what they were before the substep.  A NaN or
+ *     Inf in a field reaches only the particles whose stencil holds it.
+ * On the device one thread takes one particle (k_tracers_advance, workgroups of 256, the nsub loop inside the kernel); the 24
+ * (mu != 0: 48) loads of an evaluation are issued before the first is used; every index is clamped to the lattice before any
+ * load, so a broken invariant gives wrong numbers, never a read outside the arrays.  ekpnp_tracers_advance ENQUEUES ONLY.  With
+ * mu != 0 a lazy solve's E arrays are brought up to date first: A CHARGED TRACER GIVES UP THE LAZY-E SAVING AT ADVANCED STEPS;
+ * with mu == 0 lazy E is left alone.  "batch_moments": as for ekpnp_stats_accumulate.  Place it between two ekpnp_step calls.
+ * Advancing every M steps by h = M*dt uses the fields at the END of the interval: exact in a steady flow, first order in M*dt
+ * otherwise (with CFL 0.01 a particle moves far less than a cell per step).
+ * SEEDING - ekpnp_tracers_seed_host is the definition, the device pass leaves its bits.  RANDOM: for particle p and axis a,
+ * r = ekpnp_seed_uniform(seed, p, 16 + a); u = 0.5*r + 0.5; t = hi[a] - lo[a]; s = u*t; v = lo[a] + s.  GRID: p = (k*gy + j)*gx
+ * + i, x fastest; v_x = lo[0] + (((double)i + 0.5)*(hi[0] - lo[0]))/(double)gx, likewise y and z (host arithmetic: the device
+ * indexes three tables the host made).  Both: a result >= hi[a], or for x and y >= the period, becomes lo[a]; the start
+ * position is the position, the image counts are 0.
+ * The cloud, its scratch and its ring are allocated on first use, counted by ekpnp_device_bytes, freed by ekpnp_tracers_release
+ * and ekpnp_destroy, and are NOT part of checkpoint or state files (ekpnp_tracers_save / _load are the cloud's own). */
+#define EKPNP_TRACERS_RANDOM 0
+#define EKPNP_TRACERS_GRID   1
+#define EKPNP_TRACERS_MAX_N (1LL << 28)
+#define EKPNP_TRACERS_MAX_CELLS 65536
+#define EKPNP_NTRACER_MOMENTS 12
+typedef struct ekpnp_tracers_spec {   /* 80 bytes */
+  int64_t  n;            /* RANDOM: any 1 .. 2^28; GRID: must equal gx*gy*gz */
+  int32_t  mode;         /* EKPNP_TRACERS_RANDOM or EKPNP_TRACERS_GRID */
+  int32_t  gx, gy, gz;   /* GRID: >= 1; RANDOM: must be 0 */
+  uint64_t seed;
+  double   lo[3], hi[3]; /* box in lattice units (x, y, z), lo < hi, inside [0,nx] x [0,ny] x [0,nz-1] */
+} ekpnp_tracers_spec;
+/* Host only, no device needed; a refusal is EKPNP_ERR_INVALID with a message that names the offending number (ekpnp_last_error
+ * of NULL).  spec_check: n out of range, a mode outside 0 .. 1, GRID with gx*gy*gz != n, RANDOM with a non-zero g, a non-finite,
+ * empty or out-of-lattice box, nz < 3.  seed_host: the positions of particles first .. first + count - 1 into x, y, z [count].
+ * advance_host: the definition above on n particles in place (ex, ey, ez may be NULL when mu == 0.0).  cell: the cell of a
+ * position in a bx x by x bz partition of the lattice, integer arithmetic on the stencil's i0, j0, k0:
+ * cx = (int)(((int64)i0*bx)/nx), cy likewise, cz = (int)(((int64)k0*bz)/(nz-1)); the result is (cz*by + cy)*bx + cx, -1 for a
+ * lost particle, -2 for arguments the cell counts would refuse. */
+int ekpnp_tracers_spec_check(const ekpnp_params* p, const ekpnp_tracers_spec* spec);
+int ekpnp_tracers_seed_host(const ekpnp_params* p, const ekpnp_tracers_spec* spec, int64_t first, int64_t count, double* x, double* y, double* z);
+int ekpnp_tracers_advance_host(const ekpnp_params* p, const double* ux, const double* uy, const double* uz, const double* ex, const double* ey,
+                               const double* ez, double mu, double h, int nsub, int64_t n, double* x, double* y, double* z, int32_t* wx, int32_t* wy);
+int ekpnp_tracers_cell(const ekpnp_params* p, int bx, int by, int bz, double x, double y, double z);
+/* The cloud.  seed enqueues only.  set replaces the cloud by n positions validated on the host: one outside the invariant is
+ * EKPNP_ERR_INVALID with a message naming the particle's index, lost (all-NaN) particles are allowed; start positions are the
+ * positions, image counts 0.  get synchronises; any pointer may be NULL.  size: 0 when there is no cloud.  release frees the
+ * cloud, its scratch and its ring. */
+int ekpnp_tracers_seed(ekpnp_ctx* ctx, const ekpnp_tracers_spec* spec);                            /* enqueues only */
+int ekpnp_tracers_set(ekpnp_ctx* ctx, int64_t n, const double* x, const double* y, const double* z);
+int ekpnp_tracers_get(ekpnp_ctx* ctx, double* x, double* y, double* z, int32_t* wx, int32_t* wy);
+int ekpnp_tracers_size(ekpnp_ctx* ctx, int64_t* n);
+int ekpnp_tracers_release(ekpnp_ctx* ctx);
+int ekpnp_tracers_advance(ekpnp_ctx* ctx, double mu, double h, int nsub);                          /* enqueues only */
+/* The cloud's own file, raw little-endian: a 48-byte header {"EKPNPTR1", int32 nx, ny, nz, reserved 0, int64 n, double time,
+ * int64 reserved 0}, then x, y, z, x0, y0, z0 as FP64 [n] each, then wx, wy as int32 [n] each.  load refuses another lattice,
+ * a short file and a position outside the invariant; loading and continuing equals not having stopped, bit for bit. */
+int ekpnp_tracers_save(ekpnp_ctx* ctx, const char* path, double time);
+int ekpnp_tracers_load(ekpnp_ctx* ctx, const char* path, double* time);
+/* Cell counts (synchronous): counts[bz][by][bx] of the alive particles by ekpnp_tracers_cell, and the number of lost ones;
+ * 1 <= bx <= nx, 1 <= by <= ny, 1 <= bz <= nz-1, bx*by*bz <= EKPNP_TRACERS_MAX_CELLS.  Integer atomics only (workgroup counters
+ * in LDS where the table fits, 64-bit global ones otherwise): the counts are exact, sum(counts) + lost == n.  A mixing index
+ * is one line of numpy on the counts. */
+int ekpnp_tracers_cell_counts(ekpnp_ctx* ctx, int bx, int by, int bz, int64_t* counts, int64_t* lost);
+/* Moments (synchronous), EKPNP_NTRACER_MOMENTS numbers in this order: alive, lost, sum_dx, sum_dy, sum_dz, sum_dx2, sum_dy2,
+ * sum_dz2, sum_z, sum_z2, z_min, z_max.  dx is formed as t = x - x0; s = (double)wx*(double)nx; dx = t + s, dy likewise,
+ * dz = z - z0: unwrapped displacements in lattice units.  A lost particle adds +0.0 and takes no part in min and max; with no
+ * alive particle z_min = z_max = 0.0.  The reduction is that of ekpnp_plane_sums over particles: workgroups of 256 take runs of
+ * 4096 consecutive particles, thread t adds t, t + 256, ... in ascending order, fixed trees over lanes and waves, the partial
+ * sums added in ascending order by a finish kernel.  No atomics; the order depends on n alone. */
+int ekpnp_tracers_moments(ekpnp_ctx* ctx, double* out);
+/* The time series, shaped like ekpnp_hist_*: a row is the 12 moments.  arm allocates the ring [capacity][12]; arming again
+ * resets it.  record is an explicit ENQUEUE between two ekpnp_step calls and never waits - nothing is appended from inside
+ * ekpnp_step, so the step graph, "batch_moments" and lazy E are left alone.  When the ring is full the oldest row is overwritten
+ * (dropped counts the rows lost); read synchronises and returns rows first .. first + count - 1 of those still held, oldest
+ * first (values is [count][12]).  The ring is NOT part of checkpoint or state files.  ring_save writes text.  Line 1: "# ekpnp
+ * tracers nx <nx> ny <ny> nz <nz> n <n> recorded <r> dropped <d>"; line 2: "# step time" and the twelve names; then one row per
+ * held sample: the step as %lld, the time and the moments as %.17g, single spaces. */
+int ekpnp_tracers_arm(ekpnp_ctx* ctx, int capacity);
+int ekpnp_tracers_disarm(ekpnp_ctx* ctx);
+int ekpnp_tracers_record(ekpnp_ctx* ctx, int64_t step, double time);                              /* enqueues only */
+int ekpnp_tracers_count(ekpnp_ctx* ctx, int64_t* recorded, int64_t* dropped);
+int ekpnp_tracers_read(ekpnp_ctx* ctx, int64_t first, int count, int64_t* steps, double* times, double* values);
+int ekpnp_tracers_ring_save(ekpnp_ctx* ctx, const char* path);
+
 /* ---- measurement hooks (bench.py; no reference counterpart) ------------------ */
 /* When enabled, every launch of the bulk collide/stream kernel is bracketed by
  * HIP events on the context's stream; the sum is returned by ..._get. */
