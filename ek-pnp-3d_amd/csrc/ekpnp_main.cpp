@@ -95,7 +95,8 @@ int main(int argc, char* argv[]) {
   ekpnp_tracers_spec tracers_spec = {};
   tracers_spec.mode = EKPNP_TRACERS_RANDOM;
   tracers_spec.seed = 1u;
-  unsigned tracers_every = 1;
+  unsigned tracers_every = 1, tracers_sort_every = 0;  // --tracers-sort-every K: ekpnp_tracers_sort before every K-th advance (0: never)
+  unsigned long long tracers_advances = 0;
   int tracers_substeps = 1, tracers_cells[3] = {0, 0, 0};
   double tracers_mu = 0.0;
   static const char* const field_names[EKPNP_NFIELDS] = {"rho", "c", "cn", "phi", "ux", "uy", "uz", "Ex", "Ey", "Ez", "T"};
@@ -334,6 +335,11 @@ int main(int argc, char* argv[]) {
       if (m < 1) { std::fprintf(stderr, "--tracers-every wants a number of iterations >= 1, got %s\n", v); return 2; }
       tracers_every = (unsigned)m;
     }
+    else if ((v = val("--tracers-sort-every"))) {
+      const int k = std::atoi(v);
+      if (k < 1) { std::fprintf(stderr, "--tracers-sort-every wants a number of advances >= 1, got %s\n", v); return 2; }
+      tracers_sort_every = (unsigned)k;
+    }
     else if ((v = val("--tracers-substeps"))) {
       tracers_substeps = std::atoi(v);
       if (tracers_substeps < 1 || tracers_substeps > 4096) { std::fprintf(stderr, "--tracers-substeps wants 1 .. 4096, got %s\n", v); return 2; }
@@ -369,7 +375,7 @@ int main(int argc, char* argv[]) {
                    "                  [--section-every N | --section-full-every N  [--section-values q,uz] [--section-across y]\n"
                    "                   [--section-range lo,hi] [--section-planes z,z,...]]\n"
                    "                  [--tracers N | --tracers-grid gx,gy,gz  [--tracers-box x0,x1,y0,y1,z0,z1] [--tracers-seed S] [--tracers-every M]\n"
-                   "                   [--tracers-substeps k] [--tracers-mobility mu] [--tracers-cells bx,by,bz]]\n"
+                   "                   [--tracers-substeps k] [--tracers-mobility mu] [--tracers-cells bx,by,bz] [--tracers-sort-every K]]\n"
                    "  --tracers N: N particles at random places (--tracers-seed S, default 1) - or --tracers-grid gx,gy,gz: the centres of a\n"
                    "  gx x gy x gz grid - of the box --tracers-box (lattice units; default the interior 0,nx,0,ny,1,nz-2) are advected on the\n"
                    "  device (ekpnp_tracers_*, a single GPU only): after every M-th iteration (--tracers-every, default 1) the cloud moves by\n"
@@ -380,6 +386,9 @@ int main(int argc, char* argv[]) {
                    "  at the end, and with --tracers-cells bx,by,bz the final counts per cell as text, tracer_cells.dat.  Advancing every M\n"
                    "  iterations uses the fields at the end of the interval: exact in a steady flow, first order in M*dt otherwise.  With\n"
                    "  --batch 1 the batches are cut at these marks; both loops write the same bytes, and every other file is unchanged.\n"
+                   "  --tracers-sort-every K (K >= 1; default: never): before every K-th advance the cloud is sorted into memory order on the\n"
+                   "  device (ekpnp_tracers_sort), which keeps a stirred cloud's advance at the cost of an ordered one; no trajectory changes,\n"
+                   "  the sums of tracers.dat may differ in their last bits, and tracers_final.bin then carries the particles' ids after wy.\n"
                    "  --seed-pattern P: after the start-up (or the restart read) a pattern with mx,my whole periods across nx and ny (default 1,1)\n"
                    "  and amplitude A (default 1e-3) plus white noise of amplitude B (default 0; reproducible from --seed N, default 1) is added to\n"
                    "  the fields --seed-fields names (default c,cn; out of rho,c,cn,ux,uy,uz,T) on the interior planes, under a sin(pi z/(nz-1))\n"
@@ -512,6 +521,7 @@ int main(int argc, char* argv[]) {
     std::fprintf(stderr, "ekpnp_main: --section*: %s\n", ekpnp_last_error(nullptr));
     return 2;
   }
+  if (tracers_sort_every && !tracers) { std::fprintf(stderr, "ekpnp_main: --tracers-sort-every %u: there is no cloud to sort (give --tracers N or --tracers-grid gx,gy,gz)\n", tracers_sort_every); return 2; }
   if (tracers) {
     if (gpus > 1 || !devices.empty()) { std::fprintf(stderr, "ekpnp_main: --tracers*: tracers: slab contexts are not supported (one GPU only)\n"); return 2; }
     if (ekpnp_tracers_spec_check(&P, &tracers_spec) != EKPNP_OK) { std::fprintf(stderr, "ekpnp_main: --tracers*: %s\n", ekpnp_last_error(nullptr)); return 2; }
@@ -635,6 +645,7 @@ int main(int argc, char* argv[]) {
       CK(RUN(section_save, &section_full_spec, (out + name).c_str(), t));  // waits for this one map: [values][nz][nkeep] doubles
     }
     if (tracers && (i + 1) % tracers_every == 0) {  // enqueues only: the cloud moves through the fields of this moment
+      if (tracers_sort_every && ++tracers_advances % tracers_sort_every == 0) CK(ekpnp_tracers_sort(ctx));
       CK(ekpnp_tracers_advance(ctx, tracers_mu, (double)tracers_every * P.dt, tracers_substeps));
       CK(ekpnp_tracers_record(ctx, (int64_t)(i + 1), t));
     }

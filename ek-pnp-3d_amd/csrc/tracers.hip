@@ -16,8 +16,16 @@
 // construction: stencil, interpolation, fold and step are ONE __host__ __device__ function each, the step constants are formed
 // once on the host, and this object is built with -ffp-contract=off (csrc/Makefile, PINNED), so that neither side fuses a
 // multiply-add.  The passive and the mu != 0 kernel are two instantiations of one template; mu alone chooses, not the shape.
-// A gather is uncoalesced by nature: a GRID-seeded cloud starts in memory order, a stirred one does not.  No particle sort is built
-// here; tools/time_tracers.py measures both cases.
+// A gather is uncoalesced by nature: a GRID-seeded cloud starts in memory order, a stirred one does not (tools/time_tracers.py
+// measures both cases).  ekpnp_tracers_sort puts a stirred cloud back into memory order (tools/time_tracers_sort.py measures it):
+//   k_tracers_sort_keys      item[i] = key << 32 | i, the key being the linear index of the first node an advance loads
+//   k_tracers_sort_hist / _scan / _scan_top / _scatter   four 8-bit passes of a stable LSD radix sort over the 64-bit items, for
+//                            every lattice: a histogram per run of 4096 items, digit-major; its exclusive scan in two levels; a
+//                            scatter whose ranks come from ballots and per-wave LDS counters - no atomic decides an order
+//   k_tracers_sort_gather    the eight arrays and the ids through the final slot list, one array at a time through an 8-byte
+//                            temporary per particle (the second item buffer, free after the last pass) and a copy back
+// ekpnp_tracers_sort_host IS the definition of the order; it is unique, so the device equals it exactly.
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -360,6 +368,187 @@ __global__ void __launch_bounds__(64) k_tracers_finish(const double* __restrict_
   }
 }
 
+// ---- the sort by cell --------------------------------------------------------------------------------------------------------
+
+constexpr int TS_RUN = 4096;                    // items per workgroup of a pass: four waves of TS_ROUNDS rounds of 64
+constexpr int TS_ROUNDS = TS_RUN / TR_THREADS;  // 16
+constexpr int TS_SCAN = 4096;                   // table entries per workgroup of the scan: 256 threads of 16
+constexpr uint32_t TR_KEY_LOST = 0xFFFFFFFFu;
+typedef unsigned long long ts_item;             // key << 32 | slot
+
+// the linear index of the first node an advance of this position loads (integer arithmetic only); lost: 0xFFFFFFFF
+__host__ __device__ __forceinline__ uint32_t tr_sort_key(int nx, int ny, int nz, double x, double y, double z) {
+  if (tr_lost(x, y, z)) return TR_KEY_LOST;
+  const int i0 = tr_index(x, nx - 1), j0 = tr_index(y, ny - 1), k0 = tr_index(z, nz - 2);
+  return (uint32_t)(((unsigned long long)k0 * (unsigned)ny + (unsigned)j0) * (unsigned)nx + (unsigned)i0);
+}
+
+__global__ void __launch_bounds__(TR_THREADS) k_tracers_sort_keys(const double* __restrict__ x, const double* __restrict__ y, const double* __restrict__ z, long long n,
+                                                                  int nx, int ny, int nz, ts_item* __restrict__ items) {
+  const long long i = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
+  if (i >= n) return;
+  items[i] = ((ts_item)tr_sort_key(nx, ny, nz, x[i], y[i], z[i]) << 32) | (ts_item)i;
+}
+
+// hist[digit * nruns + run] = the run's items with that digit.  The tail of the last run (i >= n) is never loaded and counts
+// nowhere (digit -1 in tr_count_add).
+__global__ void __launch_bounds__(TR_THREADS) k_tracers_sort_hist(const ts_item* __restrict__ items, long long n, int shift, unsigned nruns, unsigned* __restrict__ hist) {
+  __shared__ unsigned cnt[256];
+  cnt[threadIdx.x] = 0u;
+  const long long first = (long long)blockIdx.x * TS_RUN + threadIdx.x;
+  ts_item v[TS_ROUNDS];
+#pragma unroll
+  for (int k = 0; k < TS_ROUNDS; ++k) {
+    const long long i = first + (long long)k * TR_THREADS;
+    v[k] = i < n ? items[i] : 0ull;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < TS_ROUNDS; ++k) {
+    const long long i = first + (long long)k * TR_THREADS;
+    tr_count_add(cnt, i < n ? (int)((v[k] >> shift) & 255ull) : -1);
+  }
+  __syncthreads();
+  hist[(size_t)threadIdx.x * nruns + blockIdx.x] = cnt[threadIdx.x];
+}
+
+// inclusive sum over the lanes of a wavefront
+__device__ __forceinline__ unsigned ts_wave_scan(unsigned v, int lane) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned u = __shfl_up(v, o);
+    if (lane >= o) v += u;
+  }
+  return v;
+}
+
+// tab[e] becomes the sum of the entries before it INSIDE its chunk of TS_SCAN; sums[chunk] = the chunk's total.  `total` is a
+// multiple of 256 (256 digits x nruns), so a thread's 16 consecutive entries lie inside the table or all outside it.
+__global__ void __launch_bounds__(TR_THREADS) k_tracers_sort_scan(unsigned* __restrict__ tab, unsigned total, unsigned* __restrict__ sums) {
+  __shared__ unsigned wsum[TR_THREADS / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const unsigned base = blockIdx.x * (unsigned)TS_SCAN + threadIdx.x * 16u;
+  const bool in = base < total;
+  uint4 q[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) q[k] = in ? ((const uint4*)(tab + base))[k] : make_uint4(0u, 0u, 0u, 0u);
+  unsigned s = 0u;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    unsigned t = q[k].x; q[k].x = s; s += t;
+    t = q[k].y; q[k].y = s; s += t;
+    t = q[k].z; q[k].z = s; s += t;
+    t = q[k].w; q[k].w = s; s += t;
+  }
+  const unsigned inc = ts_wave_scan(s, lane);
+  if (lane == 63) wsum[wave] = inc;
+  __syncthreads();
+  unsigned off = inc - s;
+  for (int w = 0; w < wave; ++w) off += wsum[w];
+  if (in) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) ((uint4*)(tab + base))[k] = make_uint4(q[k].x + off, q[k].y + off, q[k].z + off, q[k].w + off);
+  }
+  if (threadIdx.x == TR_THREADS - 1) sums[blockIdx.x] = off + s;
+}
+
+// sums[0 .. m) becomes its exclusive scan: one workgroup, 256 entries at a time with a carry
+__global__ void __launch_bounds__(TR_THREADS) k_tracers_sort_scan_top(unsigned* __restrict__ sums, unsigned m) {
+  __shared__ unsigned wsum[TR_THREADS / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned carry = 0u;
+  for (unsigned b = 0; b < m; b += TR_THREADS) {
+    const unsigned e = b + threadIdx.x;
+    const unsigned v = e < m ? sums[e] : 0u;
+    const unsigned inc = ts_wave_scan(v, lane);
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    unsigned off = carry + inc - v;
+    for (int w = 0; w < wave; ++w) off += wsum[w];
+    if (e < m) sums[e] = off;
+    carry += wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    __syncthreads();
+  }
+}
+
+// The stable scatter of one pass.  Wave w owns items [run*4096 + w*1024, + 1024) and the 256 counters cnt[w][]; after the count,
+// cnt[w][d] is where the wave's first item of digit d goes: the scanned table entry of (d, run) plus the lower waves' counts.
+// The wave then walks its 16 rounds in ascending order; the lanes of equal digit find each other with eight ballots, the rank of
+// a lane is the counter plus the equal lanes below it, and the lowest of them moves the counter on.  Tail items of the last run
+// (i >= n) are never loaded, take part in no ballot mask and write nothing; they are the highest lanes of the last rounds, so
+// they change nobody's rank.  The ranks of a pass are a permutation of 0 .. n-1; the bound check keeps a broken table from
+// writing outside the buffer.
+__global__ void __launch_bounds__(TR_THREADS) k_tracers_sort_scatter(const ts_item* __restrict__ in, ts_item* __restrict__ out, long long n, int shift, unsigned nruns,
+                                                                     const unsigned* __restrict__ hist, const unsigned* __restrict__ sums) {
+  __shared__ unsigned cnt[TR_THREADS / 64][256];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int w = 0; w < TR_THREADS / 64; ++w) cnt[w][threadIdx.x] = 0u;
+  const long long first = (long long)blockIdx.x * TS_RUN + (long long)wave * (TS_ROUNDS * 64) + lane;
+  ts_item v[TS_ROUNDS];
+#pragma unroll
+  for (int r = 0; r < TS_ROUNDS; ++r) {
+    const long long i = first + (long long)r * 64;
+    v[r] = i < n ? in[i] : 0ull;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < TS_ROUNDS; ++r) {
+    const long long i = first + (long long)r * 64;
+    tr_count_add(cnt[wave], i < n ? (int)((v[r] >> shift) & 255ull) : -1);  // counts only: the order of these atomics decides nothing
+  }
+  __syncthreads();
+  {
+    const unsigned d = threadIdx.x;
+    const unsigned e = d * nruns + blockIdx.x;
+    unsigned g = hist[e] + sums[e / (unsigned)TS_SCAN];
+#pragma unroll
+    for (int w = 0; w < TR_THREADS / 64; ++w) {
+      const unsigned t = cnt[w][d];
+      cnt[w][d] = g;
+      g += t;
+    }
+  }
+  __syncthreads();
+  volatile unsigned* mine = cnt[wave];
+  const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+  for (int r = 0; r < TS_ROUNDS; ++r) {
+    const long long i = first + (long long)r * 64;
+    const bool valid = i < n;
+    const unsigned d = (unsigned)((v[r] >> shift) & 255ull);
+    unsigned long long m = __ballot(valid);
+#pragma unroll
+    for (int b = 0; b < 8; ++b) {
+      const bool bit = (d >> b) & 1u;
+      const unsigned long long bb = __ballot(valid && bit);
+      m &= bit ? bb : ~bb;
+    }
+    // one lane per digit, the lowest, touches the counter and hands its value to the equal lanes above it
+    const int lead = valid ? __ffsll((long long)m) - 1 : lane;
+    unsigned at = 0u;
+    if (valid && lane == lead) {
+      at = mine[d];
+      mine[d] = at + (unsigned)__popcll(m);
+    }
+    at = __shfl(at, lead);
+    const unsigned rank = at + (unsigned)__popcll(m & below);
+    if (valid && (long long)rank < n) out[rank] = v[r];
+    __builtin_amdgcn_wave_barrier();  // the next round reads what this round's lowest lanes wrote (LDS serves a wave in order)
+  }
+}
+
+// dst[s] = src[slot of items[s]]; src == nullptr: the slot itself (the ids of a cloud that was never sorted are 0 .. n-1).
+// A slot is the low word of an item, formed from i < n in k_tracers_sort_keys and only moved since.
+template <typename V>
+__global__ void __launch_bounds__(TR_THREADS) k_tracers_sort_gather(const ts_item* __restrict__ items, const V* __restrict__ src, V* __restrict__ dst, long long n) {
+  const long long s = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
+  if (s >= n) return;
+  const unsigned slot = (unsigned)(items[s] & 0xFFFFFFFFull);
+  if ((long long)slot >= n) return;
+  dst[s] = src ? src[slot] : (V)slot;
+}
+
 // Host side of a context's cloud: made by the first ekpnp_tracers_seed / _set / _load / _arm, never by a context that uses none.
 struct TracerState {
   long long n = 0;
@@ -374,6 +563,13 @@ struct TracerState {
   size_t tab_doubles = 0;
   hipEvent_t landed = nullptr;
   Ring ring;                  // rows of NM doubles
+  // the sort (both made by the first ekpnp_tracers_sort, dropped with the cloud they belong to): the two item buffers [n] each,
+  // then the digit table [256][nruns] and its chunk sums; and ids [n], also made by a load of a file that carries ids
+  void* sort = nullptr;
+  size_t sort_bytes = 0;
+  int32_t* ids = nullptr;
+  size_t ids_bytes = 0;
+  bool has_ids = false;       // false: the ids are 0 .. n-1, whatever `ids` holds
   TrCloud dev() const {
     double* d = (double*)cloud;
     const size_t m = (size_t)n;
@@ -383,9 +579,17 @@ struct TracerState {
   double* out() const { return part + (size_t)nwg * NM; }
 };
 
+// the sort's scratch and the id array belong to a cloud of one size
+static void tracers_sort_release(Ctx& c, TracerState& t) {
+  if (t.sort) { (void)hipFree(t.sort); c.bytes -= t.sort_bytes; t.sort = nullptr; t.sort_bytes = 0; }
+  if (t.ids) { (void)hipFree(t.ids); c.bytes -= t.ids_bytes; t.ids = nullptr; t.ids_bytes = 0; }
+  t.has_ids = false;
+}
+
 void tracers_release(Ctx& c) {
   if (!c.tracers) return;
   TracerState& t = *c.tracers;
+  tracers_sort_release(c, t);
   if (t.cloud) { (void)hipFree(t.cloud); c.bytes -= t.cloud_bytes; }
   if (t.cells) { (void)hipFree(t.cells); c.bytes -= t.cells_bytes; }
   if (t.tab) { (void)hipFree(t.tab); c.bytes -= t.tab_doubles * sizeof(double); }
@@ -560,6 +764,41 @@ extern "C" int ekpnp_tracers_cell(const ekpnp_params* p, int bx, int by, int bz,
   return tr_cell(p->nx, p->ny, p->nz, bx, by, bz, x, y, z);
 }
 
+// keys are 32-bit and 0xFFFFFFFF is the lost particles': the largest key nx*ny*(nz-1) - 1 must stay below it
+static int tracers_check_sort_lattice(const ekpnp_params& p, std::string& err) {
+  if (int rc = tracers_check_lattice(p, err)) return rc;
+  const unsigned __int128 prod = (unsigned __int128)(unsigned)p.nx * (unsigned)p.ny * (unsigned)(p.nz - 1);
+  if (prod >= (unsigned __int128)0xFFFFFFFFull) {
+    err = "tracers: nx*ny*(nz-1) = " + std::to_string((unsigned long long)prod) + " does not fit a 32-bit sort key (must be below 4294967295)";
+    return EKPNP_ERR_INVALID;
+  }
+  return EKPNP_OK;
+}
+
+extern "C" uint32_t ekpnp_tracers_sort_key(const ekpnp_params* p, double x, double y, double z) {
+  std::string err;
+  if (!p) { set_create_error("tracers: NULL parameters"); return TR_KEY_LOST; }
+  if (tracers_check_sort_lattice(*p, err)) { set_create_error(err); return TR_KEY_LOST; }
+  return tr_sort_key(p->nx, p->ny, p->nz, x, y, z);
+}
+
+extern "C" int ekpnp_tracers_sort_host(const ekpnp_params* p, int64_t n, const double* x, const double* y, const double* z, int32_t* perm) {
+  std::string err;
+  int rc = EKPNP_ERR_INVALID;
+  if (!p) err = "tracers: NULL parameters";
+  else if ((rc = tracers_check_sort_lattice(*p, err)) == EKPNP_OK) {
+    if (n < 0 || n > EKPNP_TRACERS_MAX_N) { err = "tracers: n = " + std::to_string((long long)n) + " outside 0 .. " + std::to_string((long long)EKPNP_TRACERS_MAX_N); rc = EKPNP_ERR_INVALID; }
+    else if (n > 0 && (!x || !y || !z || !perm)) { err = "tracers: NULL pointer"; rc = EKPNP_ERR_INVALID; }
+  }
+  if (rc) { set_create_error(err); return rc; }
+  // key << 32 | slot: every item is different, so the ascending order of the items IS the stable order of the keys
+  std::vector<ts_item> items((size_t)n);
+  for (int64_t i = 0; i < n; ++i) items[(size_t)i] = ((ts_item)tr_sort_key(p->nx, p->ny, p->nz, x[i], y[i], z[i]) << 32) | (ts_item)i;
+  std::sort(items.begin(), items.end());
+  for (int64_t s = 0; s < n; ++s) perm[s] = (int32_t)(items[(size_t)s] & 0xFFFFFFFFull);
+  return EKPNP_OK;
+}
+
 // ---- the cloud ---------------------------------------------------------------------------------------------------------------
 
 #define NEEDSINGLE(ctx) \
@@ -581,6 +820,7 @@ static int tracers_alloc(Ctx& c, long long n) {
   if (t.cloud && t.n == n) return EKPNP_OK;
   HIPCHK(c, hipStreamSynchronize(c.stream));
   if (t.cloud) { (void)hipFree(t.cloud); c.bytes -= t.cloud_bytes; t.cloud = nullptr; t.cloud_bytes = 0; t.n = 0; t.part = nullptr; }
+  tracers_sort_release(c, t);
   const int nwg = (int)((n + TR_CHUNK - 1) / TR_CHUNK);
   const size_t bytes = (size_t)n * 56 + ((size_t)nwg + 1) * NM * sizeof(double);  // (56 n is a multiple of 8: the partials are aligned)
   HIPCHK(c, hipMalloc(&t.cloud, bytes));
@@ -598,6 +838,7 @@ static inline unsigned tr_blocks(long long n, int per) { return (unsigned)((n + 
 // upload a whole cloud from host arrays (synchronous)
 static int tracers_upload(Ctx& c, long long n, const double* const pos[6], const int32_t* wx, const int32_t* wy) {
   if (int rc = tracers_alloc(c, n)) return rc;
+  c.tracers->has_ids = false;  // a new cloud: slot s holds particle s (a load that carries ids puts them back)
   const TrCloud d = c.tracers->dev();
   double* const dst[6] = {d.x, d.y, d.z, d.x0, d.y0, d.z0};
   for (int a = 0; a < 6; ++a) HIPCHK(c, hipMemcpyAsync(dst[a], pos[a], (size_t)n * sizeof(double), hipMemcpyHostToDevice, c.stream));
@@ -616,6 +857,7 @@ extern "C" int ekpnp_tracers_seed(ekpnp_ctx* ctx, const ekpnp_tracers_spec* spec
   if (int rc = tracers_check_spec(c.p, spec, c.err)) return rc;
   if (int rc = tracers_alloc(c, (long long)spec->n)) return rc;
   TracerState& t = *c.tracers;
+  t.has_ids = false;
   TrSeedArgs a{};
   for (int q = 0; q < 3; ++q) {
     a.lo[q] = spec->lo[q];
@@ -721,6 +963,93 @@ extern "C" int ekpnp_tracers_advance(ekpnp_ctx* ctx, double mu, double h, int ns
   return EKPNP_OK;
 }
 
+// ---- the sort ----------------------------------------------------------------------------------------------------------------
+
+static int tracers_ids_alloc(Ctx& c, TracerState& t) {
+  if (t.ids) return EKPNP_OK;
+  const size_t bytes = (size_t)t.n * sizeof(int32_t);
+  HIPCHK(c, hipMalloc((void**)&t.ids, bytes));
+  t.ids_bytes = bytes;
+  c.bytes += bytes;
+  return EKPNP_OK;
+}
+
+static inline unsigned ts_runs(long long n) { return (unsigned)((n + TS_RUN - 1) / TS_RUN); }
+static inline unsigned ts_chunks(long long n) { return (256u * ts_runs(n) + TS_SCAN - 1) / TS_SCAN; }
+
+extern "C" int ekpnp_tracers_sort(ekpnp_ctx* ctx) {
+  NEEDSINGLE(ctx);
+  TracerState* t = cloud_of(c);
+  if (!t) return fail(c, "tracers: no cloud (seed, set or load one first)");
+  if (int rc = tracers_check_sort_lattice(c.p, c.err)) return rc;
+  const long long n = t->n;
+  const unsigned nruns = ts_runs(n), chunks = ts_chunks(n);
+  if (!t->sort) {  // (16 n is a multiple of 16: the table's uint4 loads are aligned)
+    const size_t bytes = 2 * (size_t)n * sizeof(ts_item) + ((size_t)256 * nruns + chunks) * sizeof(unsigned);
+    HIPCHK(c, hipMalloc(&t->sort, bytes));
+    t->sort_bytes = bytes;
+    c.bytes += bytes;
+  }
+  if (int rc = tracers_ids_alloc(c, *t)) return rc;
+  ts_item* a = (ts_item*)t->sort;
+  ts_item* b = a + (size_t)n;
+  unsigned* hist = (unsigned*)(b + (size_t)n);
+  unsigned* sums = hist + (size_t)256 * nruns;
+  const TrCloud d = t->dev();
+  const dim3 per_particle(tr_blocks(n, TR_THREADS)), block(TR_THREADS);
+  hipLaunchKernelGGL(k_tracers_sort_keys, per_particle, block, 0, c.stream, d.x, d.y, d.z, n, c.p.nx, c.p.ny, c.p.nz, a);
+  note_launch(c, "k_tracers_sort_keys");
+  for (int pass = 0; pass < 4; ++pass) {  // four passes for every lattice: a -> b -> a -> b -> a
+    const int shift = 32 + 8 * pass;
+    hipLaunchKernelGGL(k_tracers_sort_hist, dim3(nruns), block, 0, c.stream, a, n, shift, nruns, hist);
+    note_launch(c, "k_tracers_sort_hist");
+    hipLaunchKernelGGL(k_tracers_sort_scan, dim3(chunks), block, 0, c.stream, hist, 256u * nruns, sums);
+    note_launch(c, "k_tracers_sort_scan");
+    hipLaunchKernelGGL(k_tracers_sort_scan_top, dim3(1), block, 0, c.stream, sums, chunks);
+    note_launch(c, "k_tracers_sort_scan_top");
+    hipLaunchKernelGGL(k_tracers_sort_scatter, dim3(nruns), block, 0, c.stream, a, b, n, shift, nruns, hist, sums);
+    note_launch(c, "k_tracers_sort_scatter");
+    ts_item* const s = a;
+    a = b;
+    b = s;
+  }
+  if (take_launch_error(c) != hipSuccess) return EKPNP_ERR_HIP;
+  // `a` holds the order, `b` is free: the temporary of the gathers
+  double* const arr[6] = {d.x, d.y, d.z, d.x0, d.y0, d.z0};
+  for (int q = 0; q < 6; ++q) {
+    hipLaunchKernelGGL((k_tracers_sort_gather<double>), per_particle, block, 0, c.stream, a, arr[q], (double*)b, n);
+    note_launch(c, "k_tracers_sort_gather");
+    HIPCHK(c, hipMemcpyAsync(arr[q], b, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, c.stream));
+  }
+  int32_t* const tmp = (int32_t*)b;  // wx and wy lie behind one another in the cloud: both halves, one copy back
+  hipLaunchKernelGGL((k_tracers_sort_gather<int32_t>), per_particle, block, 0, c.stream, a, d.wx, tmp, n);
+  note_launch(c, "k_tracers_sort_gather");
+  hipLaunchKernelGGL((k_tracers_sort_gather<int32_t>), per_particle, block, 0, c.stream, a, d.wy, tmp + (size_t)n, n);
+  note_launch(c, "k_tracers_sort_gather");
+  HIPCHK(c, hipMemcpyAsync(d.wx, tmp, 2 * (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, c.stream));
+  hipLaunchKernelGGL((k_tracers_sort_gather<int32_t>), per_particle, block, 0, c.stream, a, t->has_ids ? t->ids : nullptr, tmp, n);
+  note_launch(c, "k_tracers_sort_gather");
+  HIPCHK(c, hipMemcpyAsync(t->ids, tmp, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, c.stream));
+  if (take_launch_error(c) != hipSuccess) return EKPNP_ERR_HIP;
+  t->has_ids = true;
+  return EKPNP_OK;
+}
+
+extern "C" int ekpnp_tracers_ids(ekpnp_ctx* ctx, int32_t* id) {
+  NEEDSINGLE(ctx);
+  if (!id) return fail(c, "NULL pointer");
+  TracerState* t = cloud_of(c);
+  if (!t) return fail(c, "tracers: no cloud (seed, set or load one first)");
+  if (!t->has_ids) {  // never sorted: nothing is allocated, nothing is copied
+    HIPCHK(c, hipStreamSynchronize(c.stream));
+    for (long long i = 0; i < t->n; ++i) id[i] = (int32_t)i;
+    return EKPNP_OK;
+  }
+  HIPCHK(c, hipMemcpyAsync(id, t->ids, (size_t)t->n * sizeof(int32_t), hipMemcpyDeviceToHost, c.stream));
+  HIPCHK(c, hipStreamSynchronize(c.stream));
+  return EKPNP_OK;
+}
+
 // ---- the cloud's file --------------------------------------------------------------------------------------------------------
 
 namespace {
@@ -749,6 +1078,7 @@ extern "C" int ekpnp_tracers_save(ekpnp_ctx* ctx, const char* path, double time)
   h.nx = c.p.nx; h.ny = c.p.ny; h.nz = c.p.nz;
   h.n = (int64_t)n;
   h.time = time;
+  h.reserved = t->has_ids ? 1 : 0;  // a cloud that was never sorted writes the file it always wrote
   bool ok = std::fwrite(&h, sizeof h, 1, f) == 1;
   std::vector<double> buf(n);
   const TrCloud d = t->dev();
@@ -760,6 +1090,10 @@ extern "C" int ekpnp_tracers_save(ekpnp_ctx* ctx, const char* path, double time)
   const int32_t* const wsrc[2] = {d.wx, d.wy};
   for (int a = 0; a < 2 && ok; ++a) {
     if (hipMemcpy(buf.data(), wsrc[a], n * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) { std::fclose(f); return fail(c, "tracers: copy from the device failed"); }
+    ok = std::fwrite(buf.data(), sizeof(int32_t), n, f) == n;
+  }
+  if (t->has_ids && ok) {
+    if (hipMemcpy(buf.data(), t->ids, n * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) { std::fclose(f); return fail(c, "tracers: copy from the device failed"); }
     ok = std::fwrite(buf.data(), sizeof(int32_t), n, f) == n;
   }
   if (std::fclose(f) != 0 || !ok) return fail(c, "write error on tracer file");
@@ -780,12 +1114,14 @@ extern "C" int ekpnp_tracers_load(ekpnp_ctx* ctx, const char* path, double* time
     return EKPNP_ERR_INVALID;
   }
   if (h.n < 1 || h.n > EKPNP_TRACERS_MAX_N) { std::fclose(f); c.err = "tracers: n = " + std::to_string((long long)h.n) + " in the file, outside 1 .. " + std::to_string((long long)EKPNP_TRACERS_MAX_N); return EKPNP_ERR_INVALID; }
+  if (h.reserved != 0 && h.reserved != 1) { std::fclose(f); c.err = "tracers: reserved = " + std::to_string(h.reserved) + " in the file (0: no ids, 1: ids follow; nothing else is known)"; return EKPNP_ERR_INVALID; }
   const size_t n = (size_t)h.n;
   std::vector<double> pos[6];
-  std::vector<int32_t> w[2];
+  std::vector<int32_t> w[2], ids;
   bool ok = true;
   for (int a = 0; a < 6 && ok; ++a) { pos[a].resize(n); ok = std::fread(pos[a].data(), sizeof(double), n, f) == n; }
   for (int a = 0; a < 2 && ok; ++a) { w[a].resize(n); ok = std::fread(w[a].data(), sizeof(int32_t), n, f) == n; }
+  if (h.reserved == 1 && ok) { ids.resize(n); ok = std::fread(ids.data(), sizeof(int32_t), n, f) == n; }
   std::fclose(f);
   if (!ok) { c.err = "tracers: the file is shorter than its " + std::to_string((long long)h.n) + " particles"; return EKPNP_ERR_INVALID; }
   for (size_t i = 0; i < n; ++i)
@@ -794,7 +1130,25 @@ extern "C" int ekpnp_tracers_load(ekpnp_ctx* ctx, const char* path, double* time
       return EKPNP_ERR_INVALID;
     }
   const double* const p6[6] = {pos[0].data(), pos[1].data(), pos[2].data(), pos[3].data(), pos[4].data(), pos[5].data()};
+  if (h.reserved == 1) {  // the ids must be a permutation of 0 .. n-1
+    std::vector<bool> seen(n, false);
+    for (size_t s = 0; s < n; ++s) {
+      const int32_t v = ids[s];
+      if (v < 0 || (size_t)v >= n || seen[(size_t)v]) {
+        c.err = "tracers: the ids of the file are not a permutation of 0 .. " + std::to_string(n - 1) + ": slot " + std::to_string(s) + " holds " + std::to_string(v) +
+                ((v < 0 || (size_t)v >= n) ? " (out of range)" : " (a second time)");
+        return EKPNP_ERR_INVALID;
+      }
+      seen[(size_t)v] = true;
+    }
+  }
   if (int rc = tracers_upload(c, (long long)n, p6, w[0].data(), w[1].data())) return rc;
+  if (h.reserved == 1) {
+    TracerState& t = *c.tracers;
+    if (int rc = tracers_ids_alloc(c, t)) return rc;
+    HIPCHK(c, hipMemcpy(t.ids, ids.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
+    t.has_ids = true;
+  }
   *time = h.time;
   return EKPNP_OK;
 }

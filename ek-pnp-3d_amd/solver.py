@@ -480,6 +480,39 @@ def tracers_cell(p: "Params", cells, x, y, z) -> np.ndarray:
     return out
 
 
+TRACERS_KEY_LOST = 0xFFFFFFFF
+
+
+def tracers_sort_key(p: "Params", x, y, z) -> np.ndarray:
+    """the sort key (k0*ny + j0)*nx + i0 of every position, the linear index of the first node its advance loads; 0xFFFFFFFF for a
+    lost particle: THE definition (ekpnp_tracers_sort_key, host only).  uint32, shaped like x."""
+    L = load_library()
+    x, y, z = (np.asarray(a, dtype=np.float64) for a in (x, y, z))
+    if not (x.shape == y.shape == z.shape):
+        raise ValueError("tracers_sort_key: x, y, z differ in shape")
+    if L.ekpnp_tracers_sort_host(C.byref(p), 0, None, None, None, None):   # the lattice, checked once
+        _tracers_fail(L, "ekpnp_tracers_sort_key", 1)
+    out = np.empty(x.size, dtype=np.uint32)
+    xs, ys, zs = x.ravel(), y.ravel(), z.ravel()
+    for i in range(x.size):
+        out[i] = L.ekpnp_tracers_sort_key(C.byref(p), float(xs[i]), float(ys[i]), float(zs[i]))
+    return out.reshape(x.shape)
+
+
+def tracers_sort_host(p: "Params", x, y, z) -> np.ndarray:
+    """perm (int32): THE stable ascending order of the sort keys; perm[s] is the slot whose particle moves to slot s, lost particles
+    last (ekpnp_tracers_sort_host, host only)"""
+    L = load_library()
+    x, y, z = (np.ascontiguousarray(a, dtype=np.float64).ravel() for a in (x, y, z))
+    if not (x.size == y.size == z.size):
+        raise ValueError("tracers_sort_host: x, y, z differ in length")
+    perm = np.empty(x.size, dtype=np.int32)
+    rc = L.ekpnp_tracers_sort_host(C.byref(p), x.size, _ptr(x), _ptr(y), _ptr(z), _ptr(perm))
+    if rc:
+        _tracers_fail(L, "ekpnp_tracers_sort_host", rc)
+    return perm
+
+
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
@@ -962,6 +995,10 @@ def load_library():
         "ekpnp_tracers_seed_host": (i32, [C.POINTER(Params), C.POINTER(TracersSpec), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
         "ekpnp_tracers_advance_host": (i32, [C.POINTER(Params)] + [C.c_void_p] * 6 + [dbl, dbl, i32, C.c_int64] + [C.c_void_p] * 5),
         "ekpnp_tracers_cell": (i32, [C.POINTER(Params), i32, i32, i32, dbl, dbl, dbl]),
+        "ekpnp_tracers_sort_key": (C.c_uint32, [C.POINTER(Params), dbl, dbl, dbl]),
+        "ekpnp_tracers_sort_host": (i32, [C.POINTER(Params), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "ekpnp_tracers_sort": (i32, [ctx]),
+        "ekpnp_tracers_ids": (i32, [ctx, C.c_void_p]),
         "ekpnp_tracers_seed": (i32, [ctx, C.POINTER(TracersSpec)]),
         "ekpnp_tracers_set": (i32, [ctx, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
         "ekpnp_tracers_get": (i32, [ctx] + [C.c_void_p] * 5),
@@ -1300,13 +1337,33 @@ class Solver(_Diagnostics):
         self._call("tracers_size", C.byref(n))
         return int(n.value)
 
-    def tracers_get(self):
-        """(x, y, z, wx, wy): positions in lattice units (NaN: lost) and the counts of periodic images crossed; synchronises"""
+    def tracers_get(self, by_id: bool = False):
+        """(x, y, z, wx, wy): positions in lattice units (NaN: lost) and the counts of periodic images crossed; synchronises.
+        by_id=True: in the original particle order, whatever tracers_sort() did to the slots (un-permuted on the host)"""
         n = self.tracers_size
         x, y, z = (np.empty(n, dtype=np.float64) for _ in range(3))
         wx, wy = (np.empty(n, dtype=np.int32) for _ in range(2))
         self._call("tracers_get", _ptr(x), _ptr(y), _ptr(z), _ptr(wx), _ptr(wy))
-        return x, y, z, wx, wy
+        if not by_id:
+            return x, y, z, wx, wy
+        ids = self.tracers_ids()
+        out = []
+        for a in (x, y, z, wx, wy):
+            o = np.empty_like(a)
+            o[ids] = a
+            out.append(o)
+        return tuple(out)
+
+    def tracers_sort(self):
+        """put the cloud into memory order: all its arrays permuted by tracers_sort_host of the current positions; enqueues only.
+        No trajectory changes; tracers_ids() / tracers_get(by_id=True) give the particles their original indices back."""
+        self._call("tracers_sort")
+
+    def tracers_ids(self) -> np.ndarray:
+        """ids[s]: the index the particle in slot s had when the cloud was last seeded, set or loaded (int32); synchronises"""
+        ids = np.empty(self.tracers_size, dtype=np.int32)
+        self._call("tracers_ids", _ptr(ids))
+        return ids
 
     def tracers_release(self):
         self._call("tracers_release")

@@ -765,6 +765,16 @@ int ekpnp_tracers_seed_host(const ekpnp_params* p, const ekpnp_tracers_spec* spe
 int ekpnp_tracers_advance_host(const ekpnp_params* p, const double* ux, const double* uy, const double* uz, const double* ex, const double* ey,
                                const double* ez, double mu, double h, int nsub, int64_t n, double* x, double* y, double* z, int32_t* wx, int32_t* wy);
 int ekpnp_tracers_cell(const ekpnp_params* p, int bx, int by, int bz, double x, double y, double z);
+/* THE SORT BY CELL (host only: the definition; ekpnp_tracers_sort below is the device's).  A stirred cloud gathers from all over
+ * the lattice; sorted by the node its advance loads first, neighbours in memory are neighbours in space again.
+ * sort_key: key = (k0*ny + j0)*nx + i0 with exactly the i0, j0, k0 of step 2 of an advance (k0 clamped to nz-2): the linear
+ * index of the first node an advance loads, integer arithmetic only; a lost particle (any coordinate NaN) has key 0xFFFFFFFF.
+ * Keys are 32-bit: a lattice with nx*ny*(nz-1) >= 2^32 - 1 is refused by both functions and by the device call
+ * (EKPNP_ERR_INVALID, the message names the product; sort_key then returns 0xFFFFFFFF and sets the message), and so is nz < 3.
+ * sort_host: perm [n], 0 <= n <= 2^28, is THE stable ascending order of the keys: perm[s] is the slot whose particle moves to
+ * slot s; equal keys keep their slot order, lost particles go to the end in their slot order.  The result is unique. */
+uint32_t ekpnp_tracers_sort_key(const ekpnp_params* p, double x, double y, double z);
+int ekpnp_tracers_sort_host(const ekpnp_params* p, int64_t n, const double* x, const double* y, const double* z, int32_t* perm);
 /* The cloud.  seed enqueues only.  set replaces the cloud by n positions validated on the host: one outside the invariant is
  * EKPNP_ERR_INVALID with a message naming the particle's index, lost (all-NaN) particles are allowed; start positions are the
  * positions, image counts 0.  get synchronises; any pointer may be NULL.  size: 0 when there is no cloud.  release frees the
@@ -775,9 +785,26 @@ int ekpnp_tracers_get(ekpnp_ctx* ctx, double* x, double* y, double* z, int32_t* 
 int ekpnp_tracers_size(ekpnp_ctx* ctx, int64_t* n);
 int ekpnp_tracers_release(ekpnp_ctx* ctx);
 int ekpnp_tracers_advance(ekpnp_ctx* ctx, double mu, double h, int nsub);                          /* enqueues only */
-/* The cloud's own file, raw little-endian: a 48-byte header {"EKPNPTR1", int32 nx, ny, nz, reserved 0, int64 n, double time,
- * int64 reserved 0}, then x, y, z, x0, y0, z0 as FP64 [n] each, then wx, wy as int32 [n] each.  load refuses another lattice,
- * a short file and a position outside the invariant; loading and continuing equals not having stopped, bit for bit. */
+/* sort ENQUEUES ONLY: it permutes all eight arrays of the cloud (x, y, z, x0, y0, z0, wx, wy) by the perm ekpnp_tracers_sort_host
+ * gives for the current positions, and composes the ids: id_new[s] = id_old[perm[s]].  id[s] is the index the particle in slot s
+ * had when the cloud was last seeded, set or loaded; seed, set and a load of a file without ids reset the ids to 0 .. n-1.  A
+ * cloud that was never sorted has no id array in memory: ids (which synchronises) then returns 0 .. n-1 and allocates nothing.
+ * No trajectory changes: a particle's advance reads nothing but its own entries.  A context that never sorts behaves as before,
+ * byte for byte.  On the device: a stable LSD radix sort of one packed uint64 = key << 32 | slot per particle, four 8-bit
+ * passes for every lattice (a digit histogram per run of 4096 items, its exclusive scan, a stable scatter whose ranks come from
+ * wavefront ballots and per-wave LDS counters - no atomic decides an order), then a gather of the eight arrays and the ids
+ * through the slot list.  Hand-written kernels (k_tracers_sort_*), no library.  MEMORY, allocated by the first sort, counted by
+ * ekpnp_device_bytes, freed with the cloud: scratch of 16 B per particle (two item buffers; the second is the gathers' temporary)
+ * plus the digit tables, 1024 B per 4096 particles and 4 B per 65536, and the ids, 4 B per particle: 20 B per particle + tables.
+ * Refusals: no cloud; a slab context; a lattice whose keys do not fit (above). */
+int ekpnp_tracers_sort(ekpnp_ctx* ctx);                                                            /* enqueues only */
+int ekpnp_tracers_ids(ekpnp_ctx* ctx, int32_t* id);
+/* The cloud's own file, raw little-endian: a 48-byte header {"EKPNPTR1", int32 nx, ny, nz, reserved, int64 n, double time,
+ * int64 reserved 0}, then x, y, z, x0, y0, z0 as FP64 [n] each, then wx, wy as int32 [n] each: 48 + 56 n bytes with reserved 0,
+ * what a cloud that was never sorted writes.  A sorted cloud writes reserved 1 and the ids as int32 [n] after wy: 48 + 60 n bytes.
+ * load accepts both and refuses any other reserved value, ids that are not a permutation of 0 .. n-1 (the message names the
+ * first offending slot), another lattice, a short file and a position outside the invariant; loading and continuing equals not
+ * having stopped, bit for bit, ids included. */
 int ekpnp_tracers_save(ekpnp_ctx* ctx, const char* path, double time);
 int ekpnp_tracers_load(ekpnp_ctx* ctx, const char* path, double* time);
 /* Cell counts (synchronous): counts[bz][by][bx] of the alive particles by ekpnp_tracers_cell, and the number of lost ones;
@@ -790,7 +817,9 @@ int ekpnp_tracers_cell_counts(ekpnp_ctx* ctx, int bx, int by, int bz, int64_t* c
  * dz = z - z0: unwrapped displacements in lattice units.  A lost particle adds +0.0 and takes no part in min and max; with no
  * alive particle z_min = z_max = 0.0.  The reduction is that of ekpnp_plane_sums over particles: workgroups of 256 take runs of
  * 4096 consecutive particles, thread t adds t, t + 256, ... in ascending order, fixed trees over lanes and waves, the partial
- * sums added in ascending order by a finish kernel.  No atomics; the order depends on n alone. */
+ * sums added in ascending order by a finish kernel.  No atomics; the order is the SLOT order and depends on n alone.  A sort
+ * moves particles to other slots: alive, lost, z_min and z_max are unchanged exactly, the eight sums may change in their last
+ * bits (within n * 2^-53 * sum|term|, as any order of n additions). */
 int ekpnp_tracers_moments(ekpnp_ctx* ctx, double* out);
 /* The time series, shaped like ekpnp_hist_*: a row is the 12 moments.  arm allocates the ring [capacity][12]; arming again
  * resets it.  record is an explicit ENQUEUE between two ekpnp_step calls and never waits - nothing is appended from inside
