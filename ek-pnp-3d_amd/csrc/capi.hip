@@ -407,9 +407,20 @@ static int create_impl(const ekpnp_params* p, int rank, int nranks, bool slab, e
         c.pop[b][l] = (double*)c.pop_alloc[b][l];
       }
   }
+  // A sweep never writes the padding lanes of a tile row (x >= nx), but they travel in a checkpoint file and through the
+  // staging planes of an in-place slab: zero, not what the allocation happened to hold (the placement search zeroes its arenas too)
+  if (arena) {
+    if (hipMemsetAsync(c.pop_alloc[0][0], 0, pop_pitch * pop_nbuf, c.stream) != hipSuccess) { c.err = "hipMemsetAsync failed"; return bail(EKPNP_ERR_HIP); }
+  } else {
+    for (int b = 0; b < (c.inplace ? 1 : 2); ++b)
+      for (int l = 0; l < p->n_lattices; ++l)
+        if (hipMemsetAsync(c.pop_alloc[b][l], 0, popbytes, c.stream) != hipSuccess) { c.err = "hipMemsetAsync failed"; return bail(EKPNP_ERR_HIP); }
+  }
   if (c.inplace && slab)
-    for (int l = 0; l < p->n_lattices; ++l)
+    for (int l = 0; l < p->n_lattices; ++l) {
       if ((rc = dev_alloc(c, (void**)&c.stage[l], 2 * c.pplane * sizeof(double)))) return bail(rc);
+      if (hipMemsetAsync(c.stage[l], 0, 2 * c.pplane * sizeof(double), c.stream) != hipSuccess) { c.err = "hipMemsetAsync failed"; return bail(EKPNP_ERR_HIP); }
+    }
   // The 11 macroscopic arrays are equally sized (a power of two bytes on cfg2/cfg3) and are walked
   // in lockstep by the kernels; identical placement modulo the HBM channel interleave makes all of
   // their streams queue on the same channels.  Each owned array is therefore skewed by a different

@@ -12,6 +12,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from _observer_pairs import ring_spec
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXE = os.path.join(ROOT, "ek-pnp-3d_amd", "ekpnp_main")
@@ -295,20 +297,7 @@ def _seeded_start(pkg, s, **knobs):
     return s
 
 
-def _ring_spec(s, z_lo, z_hi, joint):
-    """axes from the start fields' own ranges over the recorded planes, a little narrower so that both outer cells are used"""
-    z0 = getattr(s, "z0", 0)
-    lo, hi = (v[z_lo - z0:z_hi - z0 + 1] for v in s.value_range("q"))
-    qlo, qhi = float(lo.min()), float(hi.max())
-    w = qhi - qlo
-    assert w > 0.0
-    a = ("q", 24, qlo + 0.05 * w, qhi - 0.05 * w)
-    if not joint:
-        return a, None
-    plo, phi = s.value_range("phi")
-    plo, phi = float(plo.min()), float(phi.max())
-    assert phi > plo
-    return a, ("phi", 6, plo + 0.05 * (phi - plo), phi - 0.05 * (phi - plo))
+_ring_spec = ring_spec   # axes from the start fields' own ranges (tests/_observer_pairs.py, shared with the pair tests; second axis phi)
 
 
 @pytest.mark.parametrize("stride, batch, joint, planes", [(1, 0, False, (1, 15)), (3, 0, True, (1, 15)), (1, 1, True, (8, 8)), (3, 1, False, (0, 16))])

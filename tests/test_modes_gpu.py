@@ -13,6 +13,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from _observer_pairs import TRACK, energies
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXE = os.path.join(ROOT, "ek-pnp-3d_amd", "ekpnp_main")
@@ -52,19 +54,7 @@ def _phase(nx, ny, m, n):
     return np.cos(th), np.sin(th)
 
 
-def _energies(ab):
-    """[nmodes] from [nmodes][planes][2] in the prescribed order: e = a*a; e = e + b*b; E = E + e, ascending z (Python floats:
-    every operation rounded once)"""
-    out = []
-    for j in range(ab.shape[0]):
-        E = 0.0
-        for z in range(ab.shape[1]):
-            a, b = float(ab[j, z, 0]), float(ab[j, z, 1])
-            e = a * a
-            e = e + b * b
-            E = E + e
-        out.append(E)
-    return np.array(out)
+_energies = energies   # [nmodes] from [nmodes][planes][2] in the prescribed order (tests/_observer_pairs.py, shared with the pair tests)
 
 
 @pytest.fixture(scope="module", params=list(CASES))
@@ -172,7 +162,6 @@ def test_a_seeded_mode_is_read_back(pkg):
 # ---- 4. the ring -------------------------------------------------------------------------------------------
 
 SEED = dict(fields=("c", "cn"), pattern="squares", modes=(1, 1), amplitude=1e-2, noise=1e-4, relative=True, seed=5)
-TRACK = [(1, 1), (1, -1), (0, 0), (2, 1)]
 
 
 def _seeded_start(pkg, s, **knobs):
