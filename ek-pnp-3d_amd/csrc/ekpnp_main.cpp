@@ -99,6 +99,11 @@ int main(int argc, char* argv[]) {
   unsigned long long tracers_advances = 0;
   int tracers_substeps = 1, tracers_cells[3] = {0, 0, 0};
   double tracers_mu = 0.0;
+  // --tracks id,id,... / --tracks-first K: tagged particles of that cloud; after every M-th iteration (--tracks-every M, default --tracers-every) a row
+  // of x, y, z, wx, wy and the --tracks-values of each goes to a ring (ekpnp_tracks_*); tracks.dat at the end
+  bool tracks = false, tracks_flags = false;
+  ekpnp_tracks_spec tracks_spec = {};
+  unsigned tracks_every = 0;
   static const char* const field_names[EKPNP_NFIELDS] = {"rho", "c", "cn", "phi", "ux", "uy", "uz", "Ex", "Ey", "Ez", "T"};
   auto field_id_of = [&](const char* q, size_t len) {
     for (int k = 0; k < EKPNP_NFIELDS; ++k)
@@ -353,6 +358,43 @@ int main(int argc, char* argv[]) {
       int used = 0;
       if (std::sscanf(v, "%d,%d,%d%n", &tracers_cells[0], &tracers_cells[1], &tracers_cells[2], &used) != 3 || v[used]) { std::fprintf(stderr, "--tracers-cells wants bx,by,bz, got %s\n", v); return 2; }
     }
+    else if ((v = val("--tracks"))) {
+      tracks = tracks_flags = true;
+      tracks_spec.ntags = 0;
+      for (const char* q = v; *q;) {
+        char* end = nullptr;
+        const long id = std::strtol(q, &end, 10);
+        if (end == q || (*end && *end != ',') || id < -2147483647L || id > 2147483647L) { std::fprintf(stderr, "--tracks wants id,id,..., got %s\n", v); return 2; }
+        if (tracks_spec.ntags == EKPNP_TRACERS_MAX_TRACKS) { std::fprintf(stderr, "--tracks wants at most %d ids, got %s\n", EKPNP_TRACERS_MAX_TRACKS, v); return 2; }
+        tracks_spec.ids[tracks_spec.ntags++] = (int32_t)id;
+        q = *end ? end + 1 : end;
+      }
+    }
+    else if ((v = val("--tracks-first"))) {
+      const int k = std::atoi(v);
+      if (k < 1 || k > EKPNP_TRACERS_MAX_TRACKS) { std::fprintf(stderr, "--tracks-first wants 1 .. %d, got %s\n", EKPNP_TRACERS_MAX_TRACKS, v); return 2; }
+      tracks = tracks_flags = true;
+      tracks_spec.ntags = k;
+      for (int q = 0; q < k; ++q) tracks_spec.ids[q] = q;
+    }
+    else if ((v = val("--tracks-values"))) {
+      tracks_flags = true;
+      tracks_spec.nvalues = 0;
+      for (const char* q = v; *q;) {
+        const char* e = q;
+        while (*e && *e != ',') ++e;
+        const int id = (e - q == 1 && *q == 'q') ? (int)EKPNP_TRACERS_Q : field_id_of(q, (size_t)(e - q));
+        if (id < 0 || tracks_spec.nvalues == EKPNP_TRACERS_MAX_VALUES) { std::fprintf(stderr, "--tracks-values wants at most 12 names out of rho,c,cn,phi,ux,uy,uz,Ex,Ey,Ez,T,q, got %.*s in %s\n", (int)(e - q), q, v); return 2; }
+        tracks_spec.values[tracks_spec.nvalues++] = id;
+        q = *e ? e + 1 : e;
+      }
+    }
+    else if ((v = val("--tracks-every"))) {
+      const int m = std::atoi(v);
+      if (m < 1) { std::fprintf(stderr, "--tracks-every wants a number of iterations >= 1, got %s\n", v); return 2; }
+      tracks_flags = true;
+      tracks_every = (unsigned)m;
+    }
     else if ((v = val("--tune"))) {
       const char* eq = std::strchr(v, '=');
       if (!eq || eq == v) { std::fprintf(stderr, "--tune wants knob=value, got %s\n", v); return 2; }
@@ -375,7 +417,8 @@ int main(int argc, char* argv[]) {
                    "                  [--section-every N | --section-full-every N  [--section-values q,uz] [--section-across y]\n"
                    "                   [--section-range lo,hi] [--section-planes z,z,...]]\n"
                    "                  [--tracers N | --tracers-grid gx,gy,gz  [--tracers-box x0,x1,y0,y1,z0,z1] [--tracers-seed S] [--tracers-every M]\n"
-                   "                   [--tracers-substeps k] [--tracers-mobility mu] [--tracers-cells bx,by,bz] [--tracers-sort-every K]]\n"
+                   "                   [--tracers-substeps k] [--tracers-mobility mu] [--tracers-cells bx,by,bz] [--tracers-sort-every K]\n"
+                   "                   [--tracks id,id,... | --tracks-first K  [--tracks-values T,q,...] [--tracks-every M]]]\n"
                    "  --tracers N: N particles at random places (--tracers-seed S, default 1) - or --tracers-grid gx,gy,gz: the centres of a\n"
                    "  gx x gy x gz grid - of the box --tracers-box (lattice units; default the interior 0,nx,0,ny,1,nz-2) are advected on the\n"
                    "  device (ekpnp_tracers_*, a single GPU only): after every M-th iteration (--tracers-every, default 1) the cloud moves by\n"
@@ -389,6 +432,12 @@ int main(int argc, char* argv[]) {
                    "  --tracers-sort-every K (K >= 1; default: never): before every K-th advance the cloud is sorted into memory order on the\n"
                    "  device (ekpnp_tracers_sort), which keeps a stirred cloud's advance at the cost of an ordered one; no trajectory changes,\n"
                    "  the sums of tracers.dat may differ in their last bits, and tracers_final.bin then carries the particles' ids after wy.\n"
+                   "  --tracks id,id,... (at most 1024 particle ids of that cloud, the index a particle has when it is seeded) or --tracks-first K\n"
+                   "  (ids 0 .. K-1): after every M-th iteration (--tracks-every, default --tracers-every), after that iteration's advance, a row\n"
+                   "  of x, y, z, the image counts and the --tracks-values (names out of the fields and q = c - cn, interpolated at the particle\n"
+                   "  as the advance does; default none) of each tagged particle is appended to a ring in device memory (ekpnp_tracks_arm /\n"
+                   "  ekpnp_tracks_record: enqueued only, nothing waits); tracks.dat is written at the end (ekpnp_tracks_save: one line per row\n"
+                   "  and tag).  With --batch 1 the batches are cut at these marks; both loops write the same bytes.\n"
                    "  --seed-pattern P: after the start-up (or the restart read) a pattern with mx,my whole periods across nx and ny (default 1,1)\n"
                    "  and amplitude A (default 1e-3) plus white noise of amplitude B (default 0; reproducible from --seed N, default 1) is added to\n"
                    "  the fields --seed-fields names (default c,cn; out of rho,c,cn,ux,uy,uz,T) on the interior planes, under a sin(pi z/(nz-1))\n"
@@ -522,6 +571,13 @@ int main(int argc, char* argv[]) {
     return 2;
   }
   if (tracers_sort_every && !tracers) { std::fprintf(stderr, "ekpnp_main: --tracers-sort-every %u: there is no cloud to sort (give --tracers N or --tracers-grid gx,gy,gz)\n", tracers_sort_every); return 2; }
+  if (tracks_flags) {
+    if (gpus > 1 || !devices.empty()) { std::fprintf(stderr, "ekpnp_main: --tracks*: tracers: slab contexts are not supported (one GPU only)\n"); return 2; }
+    if (!tracers) { std::fprintf(stderr, "ekpnp_main: --tracks*: there is no cloud to tag (give --tracers N or --tracers-grid gx,gy,gz)\n"); return 2; }
+    if (!tracks) { std::fprintf(stderr, "ekpnp_main: --tracks-values / --tracks-every: no particle is tagged (give --tracks id,id,... or --tracks-first K)\n"); return 2; }
+    if (!tracks_every) tracks_every = tracers_every;
+    if (ekpnp_tracks_spec_check(&P, tracers_spec.n, &tracks_spec) != EKPNP_OK) { std::fprintf(stderr, "ekpnp_main: --tracks*: %s\n", ekpnp_last_error(nullptr)); return 2; }
+  }
   if (tracers) {
     if (gpus > 1 || !devices.empty()) { std::fprintf(stderr, "ekpnp_main: --tracers*: tracers: slab contexts are not supported (one GPU only)\n"); return 2; }
     if (ekpnp_tracers_spec_check(&P, &tracers_spec) != EKPNP_OK) { std::fprintf(stderr, "ekpnp_main: --tracers*: %s\n", ekpnp_last_error(nullptr)); return 2; }
@@ -604,6 +660,7 @@ int main(int argc, char* argv[]) {
   if (tracers) {  // the cloud at its start positions and a ring that holds the whole run
     CK(ekpnp_tracers_seed(ctx, &tracers_spec));
     CK(ekpnp_tracers_arm(ctx, (int)(nsteps / tracers_every ? nsteps / tracers_every : 1)));
+    if (tracks) CK(ekpnp_tracks_arm(ctx, &tracks_spec, (int)(nsteps / tracks_every ? nsteps / tracks_every : 1)));
   }
   CK(RUN(synchronize));
   const auto begin = std::chrono::steady_clock::now();  // main.cu:185-186
@@ -615,7 +672,7 @@ int main(int argc, char* argv[]) {
                                  (snap_every && (j + 1) % snap_every == 0) || (modes_every && (j + 1) % modes_every == 0) ||
                                  (spectrum_every && (j + 1) % spectrum_every == 0) || (hist_every && (j + 1) % hist_every == 0) ||
                                  (section_every && (j + 1) % section_every == 0) || (section_full_every && (j + 1) % section_full_every == 0) ||
-                                 (tracers && (j + 1) % tracers_every == 0))) ++j;
+                                 (tracers && (j + 1) % tracers_every == 0) || (tracks && (j + 1) % tracks_every == 0))) ++j;
       CK(RUN(step, (int)(j - i + 1)));
       for (unsigned k = i; k <= j; ++k) t = t + P.dt;  // the same additions as the loop below makes, so the files carry the same time
       i = j;
@@ -649,6 +706,7 @@ int main(int argc, char* argv[]) {
       CK(ekpnp_tracers_advance(ctx, tracers_mu, (double)tracers_every * P.dt, tracers_substeps));
       CK(ekpnp_tracers_record(ctx, (int64_t)(i + 1), t));
     }
+    if (tracks && (i + 1) % tracks_every == 0) CK(ekpnp_tracks_record(ctx, (int64_t)(i + 1), t));  // enqueues only: after this iteration's advance
     if (profiles_every && (i + 1) % profiles_every == 0) CK(RUN(stats_accumulate));  // enqueues only: the loop runs on
     if (snap_every && (i + 1) % snap_every == 0) {
       char name[32];
@@ -680,6 +738,7 @@ int main(int argc, char* argv[]) {
   if (tracers) {
     CK(ekpnp_tracers_ring_save(ctx, (out + "/tracers.dat").c_str()));
     CK(ekpnp_tracers_save(ctx, (out + "/tracers_final.bin").c_str(), t));
+    if (tracks) CK(ekpnp_tracks_save(ctx, (out + "/tracks.dat").c_str()));
     if (tracers_cells[0]) {
       const int bx = tracers_cells[0], by = tracers_cells[1], bz = tracers_cells[2];
       std::vector<int64_t> counts((size_t)bx * by * bz);

@@ -25,6 +25,14 @@
 //   k_tracers_sort_gather    the eight arrays and the ids through the final slot list, one array at a time through an 8-byte
 //                            temporary per particle (the second item buffer, free after the last pass) and a copy back
 // ekpnp_tracers_sort_host IS the definition of the order; it is unique, so the device equals it exactly.
+// What a parcel sees on its way (ekpnp_tracers_sample*, ekpnp_tracks_*): the fields AT the particles, by the advance's own stencil
+// and interpolation (tr_stencil, tr_load8, tr_interp; tr_sample is the per-particle function of host and device alike):
+//   k_tracers_sample         a thread per particle: the stencil once, the named arrays in groups of at most three (24 loads in
+//                            flight, q = c - cn counts two), coalesced stores to out[value][particle]
+//   k_tracers_track_find     sorted clouds only: one pass over the ids with 16-byte loads, the ascending tag list in LDS, a binary
+//                            search per id; the one thread that finds a tag stores its slot - no atomic
+//   k_tracers_track_row      a thread per tag: x, y, z, wx, wy and the sampled values into the next row of the tracks' ring
+// ekpnp_tracers_sample_host IS the definition of a sample.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -80,30 +88,93 @@ __host__ __device__ __forceinline__ double tr_interp(const double a[8], double f
   return tr_lerp(b0, b1, fz);
 }
 
+// the stencil at (x, y, z), step 2 of an advance: the four row starts (k, j) * nx, the two columns and the three fractions; every
+// index is clamped to the lattice, so whatever the position is, a load through it stays inside the arrays
+struct TrStencil {
+  long long r00, r10, r01, r11;
+  int i0, i1;
+  double fx, fy, fz;
+};
+__host__ __device__ __forceinline__ TrStencil tr_stencil(int nx, int ny, int nz, double x, double y, double z) {
+  const int i0 = tr_index(x, nx - 1), j0 = tr_index(y, ny - 1), k0 = tr_index(z, nz - 2);
+  const double fx = x - (double)i0, fy = y - (double)j0, fz = z - (double)k0;
+  const int i1 = i0 + 1 == nx ? 0 : i0 + 1, j1 = j0 + 1 == ny ? 0 : j0 + 1, k1 = k0 + 1;
+  const long long r00 = ((long long)k0 * ny + j0) * nx, r10 = ((long long)k0 * ny + j1) * nx;
+  const long long r01 = ((long long)k1 * ny + j0) * nx, r11 = ((long long)k1 * ny + j1) * nx;
+  return TrStencil{r00, r10, r01, r11, i0, i1, fx, fy, fz};
+}
+// the eight nodes of an array, in tr_interp's order
+__host__ __device__ __forceinline__ void tr_load8(const double* p, const TrStencil& st, double a[8]) {
+  a[0] = p[st.r00 + st.i0]; a[1] = p[st.r00 + st.i1];
+  a[2] = p[st.r10 + st.i0]; a[3] = p[st.r10 + st.i1];
+  a[4] = p[st.r01 + st.i0]; a[5] = p[st.r01 + st.i1];
+  a[6] = p[st.r11 + st.i0]; a[7] = p[st.r11 + st.i1];
+}
+
 // w[c] = u_c (+ mu E_c) at (x, y, z): the stencil once, every load before the first use
 template <bool MOB>
 __host__ __device__ __forceinline__ void tr_velocity(const TrFields& f, const TrStep& s, double x, double y, double z, double w[3]) {
-  const int i0 = tr_index(x, s.nx - 1), j0 = tr_index(y, s.ny - 1), k0 = tr_index(z, s.nz - 2);
-  const double fx = x - (double)i0, fy = y - (double)j0, fz = z - (double)k0;
-  const int i1 = i0 + 1 == s.nx ? 0 : i0 + 1, j1 = j0 + 1 == s.ny ? 0 : j0 + 1, k1 = k0 + 1;
-  const long long r00 = ((long long)k0 * s.ny + j0) * s.nx, r10 = ((long long)k0 * s.ny + j1) * s.nx;
-  const long long r01 = ((long long)k1 * s.ny + j0) * s.nx, r11 = ((long long)k1 * s.ny + j1) * s.nx;
+  const TrStencil st = tr_stencil(s.nx, s.ny, s.nz, x, y, z);
   constexpr int NA = MOB ? 6 : 3;
   double a[NA][8];
 #pragma unroll
-  for (int q = 0; q < NA; ++q) {
-    const double* p = q < 3 ? f.u[q] : f.e[q - 3];
-    a[q][0] = p[r00 + i0]; a[q][1] = p[r00 + i1];
-    a[q][2] = p[r10 + i0]; a[q][3] = p[r10 + i1];
-    a[q][4] = p[r01 + i0]; a[q][5] = p[r01 + i1];
-    a[q][6] = p[r11 + i0]; a[q][7] = p[r11 + i1];
-  }
+  for (int q = 0; q < NA; ++q) tr_load8(q < 3 ? f.u[q] : f.e[q - 3], st, a[q]);
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
-    w[c] = tr_interp(a[c], fx, fy, fz);
+    w[c] = tr_interp(a[c], st.fx, st.fy, st.fz);
     if constexpr (MOB) {
-      const double t = s.mu * tr_interp(a[3 + c], fx, fy, fz);
+      const double t = s.mu * tr_interp(a[3 + c], st.fx, st.fy, st.fz);
       w[c] = w[c] + t;
+    }
+  }
+}
+
+__host__ __device__ __forceinline__ bool tr_lost(double x, double y, double z) { return x != x || y != y || z != z; }
+
+// ---- sampling the fields at a particle (include/ekpnp.h: ekpnp_tracers_sample_host IS the definition) -------------------------
+constexpr int TR_MAXV = EKPNP_TRACERS_MAX_VALUES;
+constexpr int TR_GROUP = 3;  // arrays loaded before the first use: 24 loads in flight, the shape of a passive evaluation
+
+// A group of at most TR_GROUP arrays and what is made of them: entry e is nothing (TR_OP_NONE: the second array of a Q, or past
+// the group's end), the value of array e (TR_OP_VALUE), or q from the arrays e (c) and e + 1 (cn) (TR_OP_Q); slot[e] is the place
+// of the result among the call's values.
+enum { TR_OP_NONE = 0, TR_OP_VALUE = 1, TR_OP_Q = 2 };
+struct TrGroup {
+  const double* p[TR_GROUP];
+  int8_t op[TR_GROUP], slot[TR_GROUP];
+  int16_t narr;
+};
+struct TrSample {
+  TrGroup g[TR_MAXV];  // a group holds at least one value: never more groups than values
+  int ngroups, nvalues;
+  int nx, ny, nz;
+};
+
+// every value of the call at (x, y, z) into out[slot * vstride]: NaN for a lost particle (nothing is read for it), else the
+// stencil ONCE and group after group: all loads of a group before its first use, then v = L(L(L x) y) z of each value - for q
+// of the eight differences d_m = c_m - cn_m, each a subtraction of its own
+__host__ __device__ __forceinline__ void tr_sample(const TrSample& a, double x, double y, double z, double* out, long long vstride) {
+  if (tr_lost(x, y, z)) {
+    for (int v = 0; v < a.nvalues; ++v) out[v * vstride] = NAN;
+    return;
+  }
+  const TrStencil st = tr_stencil(a.nx, a.ny, a.nz, x, y, z);
+  for (int g = 0; g < a.ngroups; ++g) {
+    const TrGroup& G = a.g[g];
+    double v[TR_GROUP][8];
+#pragma unroll
+    for (int q = 0; q < TR_GROUP; ++q)
+      if (q < G.narr) tr_load8(G.p[q], st, v[q]);
+#pragma unroll
+    for (int q = 0; q < TR_GROUP; ++q) {
+      if (G.op[q] == TR_OP_VALUE) {
+        out[G.slot[q] * vstride] = tr_interp(v[q], st.fx, st.fy, st.fz);
+      } else if (q + 1 < TR_GROUP && G.op[q] == TR_OP_Q) {
+        double d[8];
+#pragma unroll
+        for (int m = 0; m < 8; ++m) d[m] = v[q][m] - v[q + 1 < TR_GROUP ? q + 1 : q][m];
+        out[G.slot[q] * vstride] = tr_interp(d, st.fx, st.fy, st.fz);
+      }
     }
   }
 }
@@ -161,8 +232,6 @@ __host__ __device__ __forceinline__ void tr_advance(const TrFields& f, const TrS
   }
 }
 
-__host__ __device__ __forceinline__ bool tr_lost(double x, double y, double z) { return x != x || y != y || z != z; }
-
 // the cell of a position (include/ekpnp.h: ekpnp_tracers_cell), -1 for a lost particle
 __host__ __device__ __forceinline__ int tr_cell(int nx, int ny, int nz, int bx, int by, int bz, double x, double y, double z) {
   if (tr_lost(x, y, z)) return -1;
@@ -200,6 +269,76 @@ __global__ void __launch_bounds__(TR_THREADS) k_tracers_advance(TrFields f, TrSt
   c.z[i] = z;
   c.wx[i] = wx;
   c.wy[i] = wy;
+}
+
+// out[v][i] = value v at the particle in slot i: the stores of a wavefront are coalesced
+__global__ void __launch_bounds__(TR_THREADS) k_tracers_sample(TrSample a, const double* __restrict__ x, const double* __restrict__ y, const double* __restrict__ z,
+                                                               long long n, double* __restrict__ out) {
+  const long long i = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
+  if (i >= n) return;
+  tr_sample(a, x[i], y[i], z[i], out + i, n);
+}
+
+// The tag tables of a track ring (its header): the ids as given, the ids ascending, the place each of those had in the given
+// order, and the slot found for each place.  All [ntags]; the first three are written by the host when the ring is armed.
+struct TrTags {
+  const int32_t *ids, *sorted, *place;
+  int32_t* slot;
+  int ntags;
+};
+constexpr int TK_IDS = 4;  // ids per thread of the find: one 16-byte load
+
+// slot[place of id[s]] = s for every slot s whose id is tagged: one pass over the ids, the ascending tag list in LDS, a binary
+// search per id.  The ids are a permutation, so exactly one thread finds each tag: no atomic, no race decides anything.
+__global__ void __launch_bounds__(TR_THREADS) k_tracers_track_find(const int32_t* __restrict__ ids, long long n, TrTags t) {
+  __shared__ int32_t key[EKPNP_TRACERS_MAX_TRACKS], place[EKPNP_TRACERS_MAX_TRACKS];
+  for (int k = threadIdx.x; k < t.ntags; k += TR_THREADS) {
+    key[k] = t.sorted[k];
+    place[k] = t.place[k];
+  }
+  __syncthreads();
+  const long long base = ((long long)blockIdx.x * TR_THREADS + threadIdx.x) * TK_IDS;
+  if (base >= n) return;
+  int32_t v[TK_IDS] = {-1, -1, -1, -1};  // (no tag is negative)
+  if (base + TK_IDS <= n) {
+    const int4 q = *(const int4*)(ids + base);  // base is a multiple of 4 and the array starts an allocation: aligned
+    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+  } else {
+    for (int k = 0; base + k < n; ++k) v[k] = ids[base + k];
+  }
+#pragma unroll
+  for (int k = 0; k < TK_IDS; ++k) {
+    int lo = 0, hi = t.ntags;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (key[mid] < v[k]) lo = mid + 1;
+      else hi = mid;
+    }
+    if (lo < t.ntags && key[lo] == v[k]) {
+      const int at = place[lo];
+      if (at >= 0 && at < t.ntags) t.slot[at] = (int32_t)(base + k);
+    }
+  }
+}
+
+// row[tag] = x, y, z, (double)wx, (double)wy and the sampled values of the tagged particle: the bits ekpnp_tracers_get and
+// ekpnp_tracers_sample give for it.  slots == null: the cloud was never sorted and the slot of a particle is its id.
+__global__ void __launch_bounds__(TR_THREADS) k_tracers_track_row(TrSample a, TrCloud c, TrTags t, const int32_t* __restrict__ slots, double* __restrict__ row) {
+  const int tag = blockIdx.x * TR_THREADS + threadIdx.x;
+  if (tag >= t.ntags) return;
+  double* r = row + (size_t)tag * (size_t)(5 + a.nvalues);
+  const long long s = slots ? slots[tag] : t.ids[tag];
+  if (s < 0 || s >= c.n) {  // (a checked spec and a permutation of ids never come here)
+    for (int q = 0; q < 5 + a.nvalues; ++q) r[q] = NAN;
+    return;
+  }
+  const double x = c.x[s], y = c.y[s], z = c.z[s];
+  r[0] = x;
+  r[1] = y;
+  r[2] = z;
+  r[3] = (double)c.wx[s];
+  r[4] = (double)c.wy[s];
+  tr_sample(a, x, y, z, r + 5, 1);
 }
 
 struct TrSeedArgs {
@@ -570,6 +709,11 @@ struct TracerState {
   int32_t* ids = nullptr;
   size_t ids_bytes = 0;
   bool has_ids = false;       // false: the ids are 0 .. n-1, whatever `ids` holds
+  double* samp = nullptr;     // ekpnp_tracers_sample's scratch [nvalues][n], grown on demand, dropped with the cloud
+  size_t samp_bytes = 0;
+  Ring tracks;                // rows of [ntags][5 + nvalues] doubles behind a header of four int32 tables [ntags] (TrTags)
+  ekpnp_tracks_spec tspec{};  // the spec of the last ekpnp_tracks_arm and the size of the cloud it tagged (for the file)
+  long long tracks_n = 0;
   TrCloud dev() const {
     double* d = (double*)cloud;
     const size_t m = (size_t)n;
@@ -584,6 +728,7 @@ static void tracers_sort_release(Ctx& c, TracerState& t) {
   if (t.sort) { (void)hipFree(t.sort); c.bytes -= t.sort_bytes; t.sort = nullptr; t.sort_bytes = 0; }
   if (t.ids) { (void)hipFree(t.ids); c.bytes -= t.ids_bytes; t.ids = nullptr; t.ids_bytes = 0; }
   t.has_ids = false;
+  if (t.samp) { (void)hipFree(t.samp); c.bytes -= t.samp_bytes; t.samp = nullptr; t.samp_bytes = 0; }  // and so does the sample scratch
 }
 
 void tracers_release(Ctx& c) {
@@ -597,6 +742,8 @@ void tracers_release(Ctx& c) {
   if (t.landed) (void)hipEventDestroy(t.landed);
   if (t.ring.alloc) c.bytes -= t.ring.bytes;
   ring_release(t.ring);
+  if (t.tracks.alloc) c.bytes -= t.tracks.bytes;
+  ring_release(t.tracks);
   delete c.tracers;
   c.tracers = nullptr;
 }
@@ -678,6 +825,64 @@ static int tracers_check_advance(double mu, double h, int nsub, std::string& err
   if (!std::isfinite(h)) { err = "tracers: h = " + num(h) + " (must be finite)"; return EKPNP_ERR_INVALID; }
   if (nsub < 1 || nsub > 4096) { err = "tracers: nsub = " + std::to_string(nsub) + " outside 1 .. 4096"; return EKPNP_ERR_INVALID; }
   return EKPNP_OK;
+}
+
+static const char* const kValueNames[TR_MAXV] = {"rho", "c", "cn", "phi", "ux", "uy", "uz", "Ex", "Ey", "Ez", "T", "q"};
+
+// the values of a sample (min_values 1) or of a track (0: positions only)
+static int tracers_check_values(const ekpnp_params& p, int nvalues, const int32_t* values, int min_values, std::string& err) {
+  if (int rc = tracers_check_lattice(p, err)) return rc;
+  if (nvalues < min_values || nvalues > TR_MAXV) { err = "tracers: nvalues = " + std::to_string(nvalues) + " outside " + std::to_string(min_values) + " .. " + std::to_string(TR_MAXV); return EKPNP_ERR_INVALID; }
+  if (nvalues > 0 && !values) { err = "tracers: NULL values"; return EKPNP_ERR_INVALID; }
+  for (int v = 0; v < nvalues; ++v) {
+    if (values[v] < 0 || values[v] > EKPNP_TRACERS_Q) { err = "tracers: value id " + std::to_string(values[v]) + " (place " + std::to_string(v) + ") outside 0 .. " + std::to_string(EKPNP_TRACERS_Q); return EKPNP_ERR_INVALID; }
+    for (int w = 0; w < v; ++w)
+      if (values[w] == values[v]) { err = "tracers: value id " + std::to_string(values[v]) + " is named twice (places " + std::to_string(w) + " and " + std::to_string(v) + ")"; return EKPNP_ERR_INVALID; }
+  }
+  return EKPNP_OK;
+}
+
+static int tracers_check_tracks(const ekpnp_params& p, int64_t n, const ekpnp_tracks_spec* s, std::string& err) {
+  if (!s) { err = "tracers: NULL spec"; return EKPNP_ERR_INVALID; }
+  if (int rc = tracers_check_values(p, s->nvalues, s->values, 0, err)) return rc;
+  if (n < 1 || n > EKPNP_TRACERS_MAX_N) { err = "tracers: n = " + std::to_string((long long)n) + " outside 1 .. " + std::to_string((long long)EKPNP_TRACERS_MAX_N); return EKPNP_ERR_INVALID; }
+  if (s->ntags < 1 || s->ntags > EKPNP_TRACERS_MAX_TRACKS) { err = "tracers: ntags = " + std::to_string(s->ntags) + " outside 1 .. " + std::to_string(EKPNP_TRACERS_MAX_TRACKS); return EKPNP_ERR_INVALID; }
+  std::vector<int32_t> seen(s->ids, s->ids + s->ntags);
+  for (int k = 0; k < s->ntags; ++k)
+    if (s->ids[k] < 0 || (int64_t)s->ids[k] >= n) { err = "tracers: tag " + std::to_string(k) + " is id " + std::to_string(s->ids[k]) + ", outside 0 .. " + std::to_string((long long)n - 1); return EKPNP_ERR_INVALID; }
+  std::sort(seen.begin(), seen.end());
+  for (int k = 1; k < s->ntags; ++k)
+    if (seen[(size_t)k] == seen[(size_t)k - 1]) { err = "tracers: id " + std::to_string(seen[(size_t)k]) + " is tagged twice"; return EKPNP_ERR_INVALID; }
+  return EKPNP_OK;
+}
+
+// the groups of a checked list of values over the arrays fld[EKPNP_NFIELDS]: in slot order, a group is closed when the next
+// value's arrays (q: two) would make more than TR_GROUP
+static TrSample tr_sample_plan(const ekpnp_params& p, int nvalues, const int32_t* values, const double* const* fld) {
+  TrSample a{};
+  a.nvalues = nvalues;
+  a.nx = p.nx;
+  a.ny = p.ny;
+  a.nz = p.nz;
+  for (int v = 0; v < nvalues; ++v) {
+    const bool q = values[v] == EKPNP_TRACERS_Q;
+    const int cost = q ? 2 : 1;
+    if (a.ngroups == 0 || a.g[a.ngroups - 1].narr + cost > TR_GROUP) ++a.ngroups;
+    TrGroup& G = a.g[a.ngroups - 1];
+    const int e = G.narr;
+    G.op[e] = q ? TR_OP_Q : TR_OP_VALUE;
+    G.slot[e] = (int8_t)v;
+    G.p[e] = fld[q ? EKPNP_C : values[v]];
+    if (q) G.p[e + 1] = fld[EKPNP_CN];
+    G.narr = (int16_t)(e + cost);
+  }
+  return a;
+}
+
+static inline bool tr_names_phi_or_e(int nvalues, const int32_t* values) {
+  for (int v = 0; v < nvalues; ++v)
+    if (values[v] == EKPNP_PHI || values[v] == EKPNP_EX || values[v] == EKPNP_EY || values[v] == EKPNP_EZ) return true;
+  return false;
 }
 
 static TrStep tr_step_of(const ekpnp_params& p, double mu, double h, int nsub) {
@@ -799,6 +1004,41 @@ extern "C" int ekpnp_tracers_sort_host(const ekpnp_params* p, int64_t n, const d
   return EKPNP_OK;
 }
 
+extern "C" int ekpnp_tracers_values_check(const ekpnp_params* p, int nvalues, const int32_t* values) {
+  std::string err;
+  int rc = EKPNP_ERR_INVALID;
+  if (!p) err = "tracers: NULL parameters";
+  else rc = tracers_check_values(*p, nvalues, values, 1, err);
+  if (rc) set_create_error(err);
+  return rc;
+}
+
+extern "C" int ekpnp_tracks_spec_check(const ekpnp_params* p, int64_t n, const ekpnp_tracks_spec* spec) {
+  std::string err;
+  int rc = EKPNP_ERR_INVALID;
+  if (!p) err = "tracers: NULL parameters";
+  else rc = tracers_check_tracks(*p, n, spec, err);
+  if (rc) set_create_error(err);
+  return rc;
+}
+
+extern "C" int ekpnp_tracers_sample_host(const ekpnp_params* p, int nvalues, const int32_t* values, const double* const* fields, int64_t n, const double* x,
+                                         const double* y, const double* z, double* out) {
+  if (int rc = ekpnp_tracers_values_check(p, nvalues, values)) return rc;
+  std::string err;
+  if (n < 0 || n > EKPNP_TRACERS_MAX_N) err = "tracers: n = " + std::to_string((long long)n) + " outside 0 .. " + std::to_string((long long)EKPNP_TRACERS_MAX_N);
+  else if (!fields || (n > 0 && (!x || !y || !z || !out))) err = "tracers: NULL pointer";
+  else
+    for (int v = 0; v < nvalues && err.empty(); ++v) {
+      const bool q = values[v] == EKPNP_TRACERS_Q;
+      if (!fields[q ? EKPNP_C : values[v]] || (q && !fields[EKPNP_CN])) err = std::string("tracers: value ") + kValueNames[values[v]] + " is named and its array is NULL";
+    }
+  if (!err.empty()) { set_create_error(err); return EKPNP_ERR_INVALID; }
+  const TrSample a = tr_sample_plan(*p, nvalues, values, fields);
+  for (int64_t i = 0; i < n; ++i) tr_sample(a, x[i], y[i], z[i], out + i, (long long)n);
+  return EKPNP_OK;
+}
+
 // ---- the cloud ---------------------------------------------------------------------------------------------------------------
 
 #define NEEDSINGLE(ctx) \
@@ -839,6 +1079,7 @@ static inline unsigned tr_blocks(long long n, int per) { return (unsigned)((n + 
 static int tracers_upload(Ctx& c, long long n, const double* const pos[6], const int32_t* wx, const int32_t* wy) {
   if (int rc = tracers_alloc(c, n)) return rc;
   c.tracers->has_ids = false;  // a new cloud: slot s holds particle s (a load that carries ids puts them back)
+  c.tracers->tracks.armed = false;  // and the tags of an armed track ring named particles of the old one
   const TrCloud d = c.tracers->dev();
   double* const dst[6] = {d.x, d.y, d.z, d.x0, d.y0, d.z0};
   for (int a = 0; a < 6; ++a) HIPCHK(c, hipMemcpyAsync(dst[a], pos[a], (size_t)n * sizeof(double), hipMemcpyHostToDevice, c.stream));
@@ -858,6 +1099,7 @@ extern "C" int ekpnp_tracers_seed(ekpnp_ctx* ctx, const ekpnp_tracers_spec* spec
   if (int rc = tracers_alloc(c, (long long)spec->n)) return rc;
   TracerState& t = *c.tracers;
   t.has_ids = false;
+  t.tracks.armed = false;  // the tags named particles of the cloud that is replaced here (the rows stay readable)
   TrSeedArgs a{};
   for (int q = 0; q < 3; ++q) {
     a.lo[q] = spec->lo[q];
@@ -1265,5 +1507,156 @@ extern "C" int ekpnp_tracers_ring_save(ekpnp_ctx* ctx, const char* path) {
   }
   const bool bad = std::ferror(f) != 0;
   if (std::fclose(f) != 0 || bad) return fail(c, "write error on tracers file");
+  return EKPNP_OK;
+}
+
+// ---- the fields at the particles ---------------------------------------------------------------------------------------------
+
+// enqueue the sample of a checked list of values into `out` (device memory, [nvalues][n])
+static int tracers_enqueue_sample(Ctx& c, TracerState& t, int nvalues, const int32_t* values, double* out) {
+  if (tr_names_phi_or_e(nvalues, values))
+    if (int rc = ensure_efield(c)) return rc;  // the arrays as ekpnp_get_field would return them (otherwise lazy E is left alone)
+  const TrSample a = tr_sample_plan(c.p, nvalues, values, c.fld);
+  const TrCloud d = t.dev();
+  hipLaunchKernelGGL(k_tracers_sample, dim3(tr_blocks(t.n, TR_THREADS)), dim3(TR_THREADS), 0, c.stream, a, d.x, d.y, d.z, d.n, out);
+  note_launch(c, "k_tracers_sample");
+  if (take_launch_error(c) != hipSuccess) return EKPNP_ERR_HIP;
+  return EKPNP_OK;
+}
+
+extern "C" int ekpnp_tracers_sample_device(ekpnp_ctx* ctx, int nvalues, const int32_t* values, double* device_out) {
+  NEEDSINGLE(ctx);
+  if (!values || !device_out) return fail(c, "NULL pointer");
+  if (int rc = tracers_check_values(c.p, nvalues, values, 1, c.err)) return rc;
+  TracerState* t = cloud_of(c);
+  if (!t) return fail(c, "tracers: no cloud (seed, set or load one first)");
+  return tracers_enqueue_sample(c, *t, nvalues, values, device_out);
+}
+
+extern "C" int ekpnp_tracers_sample(ekpnp_ctx* ctx, int nvalues, const int32_t* values, double* host_out) {
+  NEEDSINGLE(ctx);
+  if (!values || !host_out) return fail(c, "NULL pointer");
+  if (int rc = tracers_check_values(c.p, nvalues, values, 1, c.err)) return rc;
+  TracerState* t = cloud_of(c);
+  if (!t) return fail(c, "tracers: no cloud (seed, set or load one first)");
+  const size_t bytes = (size_t)nvalues * (size_t)t->n * sizeof(double);
+  if (bytes > t->samp_bytes) {
+    HIPCHK(c, hipStreamSynchronize(c.stream));  // an earlier sample may still write the old scratch
+    if (t->samp) { (void)hipFree(t->samp); c.bytes -= t->samp_bytes; t->samp = nullptr; t->samp_bytes = 0; }
+    HIPCHK(c, hipMalloc((void**)&t->samp, bytes));
+    t->samp_bytes = bytes;
+    c.bytes += bytes;
+  }
+  if (int rc = tracers_enqueue_sample(c, *t, nvalues, values, t->samp)) return rc;
+  HIPCHK(c, hipMemcpyAsync(host_out, t->samp, bytes, hipMemcpyDeviceToHost, c.stream));
+  HIPCHK(c, hipStreamSynchronize(c.stream));
+  return EKPNP_OK;
+}
+
+// ---- tracks of tagged particles ----------------------------------------------------------------------------------------------
+
+static inline size_t tracks_header_bytes(int ntags) { return (((size_t)4 * ntags * sizeof(int32_t)) + 15) & ~(size_t)15; }
+static inline int tracks_row_doubles(const ekpnp_tracks_spec& s) { return s.ntags * (5 + s.nvalues); }
+static TrTags tracks_tags(const TracerState& t) {
+  int32_t* h = (int32_t*)t.tracks.alloc;
+  const int m = t.tspec.ntags;
+  return TrTags{h, h + m, h + 2 * m, h + 3 * m, m};
+}
+
+extern "C" int ekpnp_tracks_arm(ekpnp_ctx* ctx, const ekpnp_tracks_spec* spec, int capacity) {
+  NEEDSINGLE(ctx);
+  TracerState* t = cloud_of(c);
+  if (!t) return fail(c, "tracers: no cloud (seed, set or load one first)");
+  if (int rc = tracers_check_tracks(c.p, (int64_t)t->n, spec, c.err)) return rc;
+  if (capacity < 1) { c.err = "tracers: capacity = " + std::to_string(capacity) + " (must be >= 1)"; return EKPNP_ERR_INVALID; }
+  const int m = spec->ntags;
+  if (int rc = ring_arm(c, t->tracks, capacity, (size_t)tracks_row_doubles(*spec) * sizeof(double), tracks_header_bytes(m))) return rc;
+  t->tracks.armed = false;  // until the tables have landed
+  t->tspec = *spec;
+  t->tracks_n = t->n;
+  // the header: ids as given | ids ascending | the place of each of those | the slots (zeros until the first find)
+  std::vector<int32_t> tab((size_t)3 * m);
+  std::vector<std::pair<int32_t, int32_t>> byid((size_t)m);
+  for (int k = 0; k < m; ++k) byid[(size_t)k] = {spec->ids[k], k};
+  std::sort(byid.begin(), byid.end());
+  for (int k = 0; k < m; ++k) {
+    tab[(size_t)k] = spec->ids[k];
+    tab[(size_t)m + k] = byid[(size_t)k].first;
+    tab[(size_t)2 * m + k] = byid[(size_t)k].second;
+  }
+  HIPCHK(c, hipMemcpyAsync(t->tracks.alloc, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice, c.stream));
+  HIPCHK(c, hipStreamSynchronize(c.stream));  // `tab` goes away
+  t->tracks.armed = true;
+  return EKPNP_OK;
+}
+
+extern "C" int ekpnp_tracks_disarm(ekpnp_ctx* ctx) {
+  NEEDSINGLE(ctx);
+  if (c.tracers) c.tracers->tracks.armed = false;  // the ring and its rows stay readable until the next arm
+  return EKPNP_OK;
+}
+
+extern "C" int ekpnp_tracks_record(ekpnp_ctx* ctx, int64_t step, double time) {
+  NEEDSINGLE(ctx);
+  if (!c.tracers || !c.tracers->tracks.armed) return fail(c, "ekpnp_tracks_record: no ring armed");
+  TracerState* t = cloud_of(c);
+  if (!t) return fail(c, "tracers: no cloud (seed, set or load one first)");
+  const ekpnp_tracks_spec& s = t->tspec;
+  if (tr_names_phi_or_e(s.nvalues, s.values))
+    if (int rc = ensure_efield(c)) return rc;
+  const TrTags tags = tracks_tags(*t);
+  if (t->has_ids) {  // a sorted cloud: where is each tagged particle now?
+    const long long quads = (t->n + TK_IDS - 1) / TK_IDS;
+    hipLaunchKernelGGL(k_tracers_track_find, dim3(tr_blocks(quads, TR_THREADS)), dim3(TR_THREADS), 0, c.stream, t->ids, t->n, tags);
+    note_launch(c, "k_tracers_track_find");
+  }
+  const TrSample a = tr_sample_plan(c.p, s.nvalues, s.values, c.fld);
+  hipLaunchKernelGGL(k_tracers_track_row, dim3(tr_blocks(s.ntags, TR_THREADS)), dim3(TR_THREADS), 0, c.stream, a, t->dev(), tags,
+                     t->has_ids ? (const int32_t*)tags.slot : (const int32_t*)nullptr, (double*)ring_next_row(t->tracks));
+  note_launch(c, "k_tracers_track_row");
+  if (take_launch_error(c) != hipSuccess) return EKPNP_ERR_HIP;
+  ring_note_row(t->tracks, step, time);
+  return EKPNP_OK;
+}
+
+extern "C" int ekpnp_tracks_count(ekpnp_ctx* ctx, int64_t* recorded, int64_t* dropped) {
+  NEEDSINGLE(ctx);
+  ring_count(c.tracers ? &c.tracers->tracks : nullptr, recorded, dropped);
+  return EKPNP_OK;
+}
+
+extern "C" int ekpnp_tracks_read(ekpnp_ctx* ctx, int64_t first, int count, int64_t* steps, double* times, double* values) {
+  NEEDSINGLE(ctx);
+  return ring_read(c, c.tracers ? &c.tracers->tracks : nullptr, "ekpnp_tracks_read", first, count, steps, times, values);
+}
+
+extern "C" int ekpnp_tracks_save(ekpnp_ctx* ctx, const char* path) {
+  NEEDSINGLE(ctx);
+  if (!path) return fail(c, "NULL path");
+  if (!c.tracers || !c.tracers->tracks.ever_armed || !c.tracers->tracks.alloc) return fail(c, "ekpnp_tracks_save: no ring was armed");
+  const TracerState& t = *c.tracers;
+  const ekpnp_tracks_spec& s = t.tspec;
+  int64_t rec = 0, dropped = 0;
+  ring_count(&t.tracks, &rec, &dropped);
+  const int n = (int)(rec - dropped), w = 5 + s.nvalues;
+  std::vector<int64_t> steps((size_t)n);
+  std::vector<double> times((size_t)n), values((size_t)n * (size_t)tracks_row_doubles(s));
+  if (int rc = ring_read(c, &t.tracks, "ekpnp_tracks_save", 0, n, steps.data(), times.data(), values.data())) return rc;
+  FILE* f = std::fopen(path, "wb");
+  if (!f) return fail(c, "cannot open tracks file");
+  std::fprintf(f, "# ekpnp tracks nx %d ny %d nz %d n %lld ntags %d nvalues %d recorded %lld dropped %lld\n", c.p.nx, c.p.ny, c.p.nz, t.tracks_n, s.ntags, s.nvalues,
+               (long long)rec, (long long)dropped);
+  std::fprintf(f, "# step time id x y z wx wy");
+  for (int v = 0; v < s.nvalues; ++v) std::fprintf(f, " %s", kValueNames[s.values[v]]);
+  std::fprintf(f, "\n");
+  for (int r = 0; r < n; ++r)
+    for (int k = 0; k < s.ntags; ++k) {
+      const double* q = values.data() + ((size_t)r * s.ntags + k) * w;
+      std::fprintf(f, "%lld %.17g %d %.17g %.17g %.17g %d %d", (long long)steps[(size_t)r], times[(size_t)r], s.ids[k], q[0], q[1], q[2], (int)q[3], (int)q[4]);
+      for (int v = 0; v < s.nvalues; ++v) std::fprintf(f, " %.17g", q[5 + v]);
+      std::fprintf(f, "\n");
+    }
+  const bool bad = std::ferror(f) != 0;
+  if (std::fclose(f) != 0 || bad) return fail(c, "write error on tracks file");
   return EKPNP_OK;
 }

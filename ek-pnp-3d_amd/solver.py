@@ -513,6 +513,81 @@ def tracers_sort_host(p: "Params", x, y, z) -> np.ndarray:
     return perm
 
 
+TRACERS_Q = 11  # include/ekpnp.h: EKPNP_TRACERS_Q, the charge density c - cn as a sampled value
+TRACERS_MAX_VALUES = 12
+TRACERS_MAX_TRACKS = 1024
+TRACERS_VALUES = FIELDS + ["q"]
+TRACERS_VALUE_ID = {n: i for i, n in enumerate(TRACERS_VALUES)}
+
+
+class TracksSpec(C.Structure):
+    """Mirror of `ekpnp_tracks_spec` (include/ekpnp.h): the tagged particle ids, in the order of the rows, and the values sampled
+    at them beside x, y, z, wx, wy."""
+
+    _fields_ = [("ntags", C.c_int32), ("nvalues", C.c_int32), ("values", C.c_int32 * TRACERS_MAX_VALUES), ("ids", C.c_int32 * TRACERS_MAX_TRACKS)]
+
+    def names(self) -> list:
+        return [TRACERS_VALUES[self.values[k]] for k in range(self.nvalues)]
+
+
+def _tracers_values(values) -> np.ndarray:
+    """names (of the fields, or "q") or ids, one or several, as the int32 array the library takes; nothing is checked here"""
+    if isinstance(values, (str, int, np.integer)):
+        values = [values]
+    return np.array([TRACERS_VALUE_ID[v] if isinstance(v, str) else int(v) for v in values], dtype=np.int32)
+
+
+def tracers_values_check(p: "Params", values) -> np.ndarray:
+    """the value ids (int32), or EkpnpError with the library's message (ekpnp_tracers_values_check: host arithmetic, no device)"""
+    L = load_library()
+    ids = _tracers_values(values)
+    rc = L.ekpnp_tracers_values_check(C.byref(p), ids.size, _ptr(ids))
+    if rc:
+        _tracers_fail(L, "ekpnp_tracers_values_check", rc)
+    return ids
+
+
+def tracers_sample_host(p: "Params", values, fields, x, y, z) -> np.ndarray:
+    """[nvalues, n]: the values (names or ids) at the positions x, y, z, interpolated in the arrays fields - a dict name -> [nz, ny,
+    nx] that holds at least the named ones (q needs c and cn): THE definition of a sample (ekpnp_tracers_sample_host, host only)"""
+    L = load_library()
+    ids = _tracers_values(values)
+    shape = (p.nz, p.ny, p.nx)
+    keep = {n: np.ascontiguousarray(a, dtype=np.float64).reshape(shape) for n, a in fields.items()}
+    ptrs = (C.c_void_p * len(FIELDS))(*[keep[n].ctypes.data if n in keep else None for n in FIELDS])
+    x, y, z = (np.ascontiguousarray(a, dtype=np.float64).ravel() for a in (x, y, z))
+    if not (x.size == y.size == z.size):
+        raise ValueError("tracers_sample_host: x, y, z differ in length")
+    out = np.empty((ids.size, x.size), dtype=np.float64)
+    rc = L.ekpnp_tracers_sample_host(C.byref(p), ids.size, _ptr(ids), ptrs, x.size, _ptr(x), _ptr(y), _ptr(z), _ptr(out))
+    if rc:
+        _tracers_fail(L, "ekpnp_tracers_sample_host", rc)
+    return out
+
+
+def tracks_spec(ids, values=()) -> TracksSpec:
+    """the particles with these ids (ekpnp_tracers_ids' numbering; at most TRACERS_MAX_TRACKS, rows keep this order) and the values
+    (names or ids, may be none) sampled at them; nothing is checked here"""
+    ids = [int(i) for i in np.asarray(ids).ravel()]
+    vals = _tracers_values(values)
+    spec = TracksSpec()
+    spec.ntags, spec.nvalues = len(ids), int(vals.size)
+    for k, v in enumerate(vals[:TRACERS_MAX_VALUES]):
+        spec.values[k] = int(v)
+    for k, i in enumerate(ids[:TRACERS_MAX_TRACKS]):
+        spec.ids[k] = i
+    return spec
+
+
+def tracks_spec_check(p: "Params", n: int, spec: TracksSpec) -> TracksSpec:
+    """the spec for a cloud of n particles, or EkpnpError with the library's message (ekpnp_tracks_spec_check: no device)"""
+    L = load_library()
+    rc = L.ekpnp_tracks_spec_check(C.byref(p), int(n), C.byref(spec))
+    if rc:
+        _tracers_fail(L, "ekpnp_tracks_spec_check", rc)
+    return spec
+
+
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
@@ -1015,6 +1090,18 @@ def load_library():
         "ekpnp_tracers_count": (i32, [ctx, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
         "ekpnp_tracers_read": (i32, [ctx, C.c_int64, i32, C.c_void_p, C.c_void_p, C.c_void_p]),
         "ekpnp_tracers_ring_save": (i32, [ctx, C.c_char_p]),
+        # the fields at the particles, and tracks of tagged particles
+        "ekpnp_tracers_values_check": (i32, [C.POINTER(Params), i32, C.c_void_p]),
+        "ekpnp_tracers_sample_host": (i32, [C.POINTER(Params), i32, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 4),
+        "ekpnp_tracers_sample_device": (i32, [ctx, i32, C.c_void_p, C.c_void_p]),
+        "ekpnp_tracers_sample": (i32, [ctx, i32, C.c_void_p, C.c_void_p]),
+        "ekpnp_tracks_spec_check": (i32, [C.POINTER(Params), C.c_int64, C.POINTER(TracksSpec)]),
+        "ekpnp_tracks_arm": (i32, [ctx, C.POINTER(TracksSpec), i32]),
+        "ekpnp_tracks_disarm": (i32, [ctx]),
+        "ekpnp_tracks_record": (i32, [ctx, C.c_int64, dbl]),
+        "ekpnp_tracks_count": (i32, [ctx, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+        "ekpnp_tracks_read": (i32, [ctx, C.c_int64, i32, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "ekpnp_tracks_save": (i32, [ctx, C.c_char_p]),
     }
     # the diagnostics a context and a group both have: ekpnp_<name>(ctx, ...) and ekpnp_group_<name>(group, ...) with the same arguments
     series = {  # the verbs of a time series on a ring (csrc/ring.h)
@@ -1419,6 +1506,58 @@ class Solver(_Diagnostics):
     def tracers_ring_save(self, path: str):
         """the ring as text: two header lines, then one row "step time moments ..." per held sample (ekpnp_tracers_ring_save)"""
         self._call("tracers_ring_save", os.fsencode(path))
+
+    def tracers_sample(self, values, by_id: bool = False) -> np.ndarray:
+        """[nvalues, n]: the values (names of the fields or "q", or ids) at the particles, interpolated as an advance does; complete on
+        return.  Slot order; by_id=True: in the original particle order (un-permuted on the host, like tracers_get)"""
+        ids = _tracers_values(values)
+        out = np.empty((ids.size, self.tracers_size), dtype=np.float64)
+        self._call("tracers_sample", ids.size, _ptr(ids), _ptr(out))
+        if not by_id:
+            return out
+        back = np.empty_like(out)
+        back[:, self.tracers_ids()] = out
+        return back
+
+    def tracers_sample_into(self, values, out):
+        """enqueue the same pass into device memory [nvalues, n] float64, slot order: a contiguous torch tensor on this device, or a raw
+        device pointer (int); nothing is allocated and nothing waits"""
+        ids = _tracers_values(values)
+        if hasattr(out, "data_ptr"):
+            if str(out.dtype) != "torch.float64" or not out.is_contiguous() or out.numel() < ids.size * self.tracers_size:
+                raise ValueError("tracers_sample_into: a contiguous float64 tensor of at least nvalues * n elements is needed")
+            out = out.data_ptr()
+        self._call("tracers_sample_device", ids.size, _ptr(ids), C.c_void_p(int(out)))
+
+    def tracks_arm(self, spec: TracksSpec = None, capacity: int = 1024, **kw):
+        """allocate the ring of rows [ntags, 5 + nvalues]: tracks_arm(spec) or tracks_arm(ids=..., values=...); rows are appended by
+        tracks_record() only"""
+        if spec is None:
+            spec = tracks_spec(**kw)
+        self._call("tracks_arm", C.byref(spec), int(capacity))
+        self._tracks_shape = (int(spec.ntags), 5 + int(spec.nvalues))
+
+    def tracks_disarm(self):
+        self._call("tracks_disarm")
+
+    def tracks_record(self, step: int, time: float):
+        """append x, y, z, wx, wy and the armed values of every tagged particle with the caller's labels; enqueues only"""
+        self._call("tracks_record", int(step), float(time))
+
+    def tracks_count(self):
+        """(rows recorded since arming, rows lost to overflow)"""
+        return self._count("tracks_count")
+
+    def tracks_read(self, first: int = 0, count: int = None):
+        """(steps, times, values [count, ntags, 5 + nvalues]) of the held rows first .. first + count - 1, oldest first"""
+        if count is None:
+            r, d = self.tracks_count()
+            count = r - d - first
+        return self._read("tracks_read", first, count, (getattr(self, "_tracks_shape", (0, 5)), np.float64))
+
+    def tracks_save(self, path: str):
+        """the ring as text: two header lines, then one line "step time id x y z wx wy values ..." per held row and tag (ekpnp_tracks_save)"""
+        self._call("tracks_save", os.fsencode(path))
 
     def tune(self, knob: str, value: int):
         self._ck(self._L.ekpnp_tune(self._h, knob.encode(), int(value)))

@@ -834,6 +834,74 @@ int ekpnp_tracers_record(ekpnp_ctx* ctx, int64_t step, double time);            
 int ekpnp_tracers_count(ekpnp_ctx* ctx, int64_t* recorded, int64_t* dropped);
 int ekpnp_tracers_read(ekpnp_ctx* ctx, int64_t first, int count, int64_t* steps, double* times, double* values);
 int ekpnp_tracers_ring_save(ekpnp_ctx* ctx, const char* path);
+/* THE FIELDS AT THE PARTICLES - what a parcel sees on its way.  ekpnp_tracers_sample_host IS the definition, and the device
+ * leaves exactly its bits.  Values are named as in ekpnp_section and ekpnp_hist: the field ids 0 .. 10, and EKPNP_TRACERS_Q = 11,
+ * the charge density q = c - cn; a call takes 1 .. EKPNP_TRACERS_MAX_VALUES DISTINCT values, in any order.  The value v of an
+ * array a at a particle is steps 2 and 3 of an advance, every operation rounded once, no fused multiply-add: the stencil i0, i1,
+ * fx, j0, j1, fy, k0, k1, fz (k0 clamped to nz-2, z == nz-1 gives fz == 1.0), then with L(p, q, f) meaning d = q - p; t = f*d;
+ * r = p + t: x first, then y, then z - a00 = L(a[k0][j0][i0], a[k0][j0][i1], fx), a10 on row j1, a01 and a11 on plane k1;
+ * b0 = L(a00, a10, fy); b1 = L(a01, a11, fy); v = L(b0, b1, fz).  For q the eight node values are d_m = c_m - cn_m, each a
+ * subtraction of its own, interpolated in the same way.  A LOST particle gives NaN for every value and nothing of the fields is
+ * read for it; a NaN or Inf in a field reaches only the particles whose eight nodes hold it.
+ * sample_host (host only, no device): fields is const double* [EKPNP_NFIELDS], whole-lattice arrays [nz][ny][nx]; only the named
+ * ones need be non-NULL (q needs c and cn); out is [nvalues][n], out[v][i] the value named at place v at particle i.  values_check
+ * is the shared refusal, EKPNP_ERR_INVALID with a message that names the offending number (ekpnp_last_error of NULL): nvalues
+ * outside 1 .. 12, an id outside 0 .. 11, an id named twice, nz < 3.
+ * On the device one thread takes one particle (k_tracers_sample, workgroups of 256): the stencil is formed once, every index
+ * is clamped to the lattice before any load, and the arrays are taken in groups of at most three (q counts as two), so that at
+ * most 24 loads are in flight before the first use - the shape of a passive advance's evaluation; the stores to out[v][i] are
+ * coalesced.  sample_device ENQUEUES ONLY, into the caller's device memory [nvalues][n] in SLOT order (a torch tensor's pointer
+ * will do, as with ekpnp_bind_field), and allocates nothing.  sample runs the same pass into a scratch buffer of the cloud
+ * (grown on demand, counted by ekpnp_device_bytes, freed with the cloud, by ekpnp_tracers_release and by ekpnp_destroy), copies
+ * it to host_out and synchronises.  After ekpnp_tracers_sort, slot s holds the particle ekpnp_tracers_ids names.  The values are
+ * those ekpnp_get_field would return: when phi, Ex, Ey or Ez is named a lazy solve's arrays are brought up to date first, as for
+ * ekpnp_section (SAMPLING phi OR E GIVES UP THE LAZY-E SAVING AT SAMPLED STEPS); otherwise lazy E is left alone.
+ * "batch_moments": as for ekpnp_tracers_advance.  Refusals: no cloud, NULL pointers, the values check, a slab context. */
+#define EKPNP_TRACERS_Q 11
+#define EKPNP_TRACERS_MAX_VALUES 12
+int ekpnp_tracers_values_check(const ekpnp_params* p, int nvalues, const int32_t* values);
+int ekpnp_tracers_sample_host(const ekpnp_params* p, int nvalues, const int32_t* values, const double* const* fields, int64_t n, const double* x,
+                              const double* y, const double* z, double* out);
+int ekpnp_tracers_sample_device(ekpnp_ctx* ctx, int nvalues, const int32_t* values, double* device_out);   /* enqueues only */
+int ekpnp_tracers_sample(ekpnp_ctx* ctx, int nvalues, const int32_t* values, double* host_out);
+/* TRACKS OF TAGGED PARTICLES, kept in a ring on the device: x(t), z(t), T(t), q(t) of chosen beads.  The tags are particle IDS -
+ * the index a particle had when the cloud was last seeded, set or loaded, what ekpnp_tracers_ids reports - distinct, in
+ * 0 .. n-1, in any order; rows keep the order given.  nvalues may be 0: positions only.  The calls are shaped like
+ * ekpnp_section_*.  spec_check (host only; n is the cloud's size) refuses ntags outside 1 .. EKPNP_TRACERS_MAX_TRACKS, an id
+ * outside 0 .. n-1, an id tagged twice, and values as values_check does (nvalues 0 .. 12).  arm needs a cloud and allocates the
+ * ring [capacity] of rows [ntags][5 + nvalues] doubles behind four int32 tables [ntags]; arming again resets it.  For tag t a row
+ * holds x, y, z, (double)wx, (double)wy and the sampled values of the particle whose id is ids[t]: exactly the bits
+ * ekpnp_tracers_get and ekpnp_tracers_sample give for that particle at that moment; a lost particle keeps its image counts and
+ * has NaN elsewhere.  record is an explicit ENQUEUE between two ekpnp_step calls and never waits - nothing is appended from inside
+ * ekpnp_step, so the step graph, "batch_moments" and lazy E are left alone (phi or E among the values: as for a sample).  When the
+ * ring is full the oldest row is overwritten (dropped counts the rows lost); count never synchronises; read synchronises and
+ * returns rows first .. first + count - 1 of those still held, oldest first (values is [count][ntags][5 + nvalues]).  The ring is
+ * NOT part of checkpoint or state files; it is counted by ekpnp_device_bytes and released with the cloud by
+ * ekpnp_tracers_release and ekpnp_destroy.  Replacing the cloud (seed, set, load) DISARMS the tracks: a record then returns
+ * "no ring armed"; the rows stay readable until the next arm.
+ * On the device a cloud that was never sorted has slot == id.  A sorted cloud has an id array, and each record first runs
+ * k_tracers_track_find: one pass over ids[n] (4 B per particle, 16-byte loads) against the tag list, which the host sorted by id
+ * when the ring was armed and the workgroup holds in LDS; each slot's id is looked up by binary search and the finder stores its
+ * slot at the tag's place.  The ids are a permutation, so exactly one thread writes each entry: no atomic, no order decided by a
+ * race.  k_tracers_track_row then takes one thread per tag and writes the row through the functions of a sample.  The find runs
+ * at every record of a sorted cloud rather than being cached across sorts: the state stays small.
+ * save writes text.  Line 1: "# ekpnp tracks nx <nx> ny <ny> nz <nz> n <n> ntags <t> nvalues <v> recorded <r> dropped <d>";
+ * line 2: "# step time id x y z wx wy" and the value names; then one line per held row AND tag: the step as %lld, the time and
+ * the doubles as %.17g, the id, wx and wy as integers, single spaces. */
+#define EKPNP_TRACERS_MAX_TRACKS 1024
+typedef struct ekpnp_tracks_spec {   /* 4152 bytes */
+  int32_t ntags;                            /* 1 .. EKPNP_TRACERS_MAX_TRACKS                          */
+  int32_t nvalues;                          /* 0 .. EKPNP_TRACERS_MAX_VALUES                          */
+  int32_t values[EKPNP_TRACERS_MAX_VALUES]; /* distinct value ids 0 .. 11                            */
+  int32_t ids[EKPNP_TRACERS_MAX_TRACKS];    /* distinct particle ids 0 .. n-1, in the order of the rows */
+} ekpnp_tracks_spec;
+int ekpnp_tracks_spec_check(const ekpnp_params* p, int64_t n, const ekpnp_tracks_spec* spec);
+int ekpnp_tracks_arm(ekpnp_ctx* ctx, const ekpnp_tracks_spec* spec, int capacity);
+int ekpnp_tracks_disarm(ekpnp_ctx* ctx);
+int ekpnp_tracks_record(ekpnp_ctx* ctx, int64_t step, double time);                               /* enqueues only */
+int ekpnp_tracks_count(ekpnp_ctx* ctx, int64_t* recorded, int64_t* dropped);
+int ekpnp_tracks_read(ekpnp_ctx* ctx, int64_t first, int count, int64_t* steps, double* times, double* values);
+int ekpnp_tracks_save(ekpnp_ctx* ctx, const char* path);
 
 /* ---- measurement hooks (bench.py; no reference counterpart) ------------------ */
 /* When enabled, every launch of the bulk collide/stream kernel is bracketed by
