@@ -18,6 +18,7 @@
 // exchange overlapped with the collision of the interior planes); same files, same formats.
 // --devices 0,0,1,1 places the slabs by hand (slabs sharing a device exchange by device copies).
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -99,6 +100,10 @@ int main(int argc, char* argv[]) {
   unsigned long long tracers_advances = 0;
   int tracers_substeps = 1, tracers_cells[3] = {0, 0, 0};
   double tracers_mu = 0.0;
+  // --tracers-diffusivity D [--tracers-noise-seed S]: the advances are Brownian (ekpnp_tracers_advance_brownian)
+  bool tracers_brownian = false, tracers_noise_seed_given = false;
+  double tracers_D = 0.0;
+  unsigned long long tracers_noise_seed = 0;
   // --tracks id,id,... / --tracks-first K: tagged particles of that cloud; after every M-th iteration (--tracks-every M, default --tracers-every) a row
   // of x, y, z, wx, wy and the --tracks-values of each goes to a ring (ekpnp_tracks_*); tracks.dat at the end
   bool tracks = false, tracks_flags = false;
@@ -354,6 +359,18 @@ int main(int argc, char* argv[]) {
       tracers_mu = std::strtod(v, &end);
       if (end == v || *end) { std::fprintf(stderr, "--tracers-mobility wants a number (m^2/V/s), got %s\n", v); return 2; }
     }
+    else if ((v = val("--tracers-diffusivity"))) {
+      char* end = nullptr;
+      tracers_D = std::strtod(v, &end);
+      if (end == v || *end) { std::fprintf(stderr, "--tracers-diffusivity wants a number (m^2/s), got %s\n", v); return 2; }
+      tracers_brownian = true;
+    }
+    else if ((v = val("--tracers-noise-seed"))) {
+      char* end = nullptr;
+      tracers_noise_seed = std::strtoull(v, &end, 10);
+      if (end == v || *end) { std::fprintf(stderr, "--tracers-noise-seed wants a number, got %s\n", v); return 2; }
+      tracers_noise_seed_given = true;
+    }
     else if ((v = val("--tracers-cells"))) {
       int used = 0;
       if (std::sscanf(v, "%d,%d,%d%n", &tracers_cells[0], &tracers_cells[1], &tracers_cells[2], &used) != 3 || v[used]) { std::fprintf(stderr, "--tracers-cells wants bx,by,bz, got %s\n", v); return 2; }
@@ -418,6 +435,7 @@ int main(int argc, char* argv[]) {
                    "                   [--section-range lo,hi] [--section-planes z,z,...]]\n"
                    "                  [--tracers N | --tracers-grid gx,gy,gz  [--tracers-box x0,x1,y0,y1,z0,z1] [--tracers-seed S] [--tracers-every M]\n"
                    "                   [--tracers-substeps k] [--tracers-mobility mu] [--tracers-cells bx,by,bz] [--tracers-sort-every K]\n"
+                   "                   [--tracers-diffusivity D [--tracers-noise-seed S]]\n"
                    "                   [--tracks id,id,... | --tracks-first K  [--tracks-values T,q,...] [--tracks-every M]]]\n"
                    "  --tracers N: N particles at random places (--tracers-seed S, default 1) - or --tracers-grid gx,gy,gz: the centres of a\n"
                    "  gx x gy x gz grid - of the box --tracers-box (lattice units; default the interior 0,nx,0,ny,1,nz-2) are advected on the\n"
@@ -432,6 +450,10 @@ int main(int argc, char* argv[]) {
                    "  --tracers-sort-every K (K >= 1; default: never): before every K-th advance the cloud is sorted into memory order on the\n"
                    "  device (ekpnp_tracers_sort), which keeps a stirred cloud's advance at the cost of an ordered one; no trajectory changes,\n"
                    "  the sums of tracers.dat may differ in their last bits, and tracers_final.bin then carries the particles' ids after wy.\n"
+                   "  --tracers-diffusivity D (m^2/s, >= 0; default: none, a deterministic cloud): every substep also kicks each particle by a\n"
+                   "  uniform increment of variance 2 D h per axis and reflects it at the plates (ekpnp_tracers_advance_brownian); the numbers\n"
+                   "  are those of (--tracers-noise-seed S, default 0; the particle's id; the substep's number), so a sort changes no path and\n"
+                   "  both loops write the same bytes; tracers_final.bin then carries the number of Brownian substeps taken.\n"
                    "  --tracks id,id,... (at most 1024 particle ids of that cloud, the index a particle has when it is seeded) or --tracks-first K\n"
                    "  (ids 0 .. K-1): after every M-th iteration (--tracks-every, default --tracers-every), after that iteration's advance, a row\n"
                    "  of x, y, z, the image counts and the --tracks-values (names out of the fields and q = c - cn, interpolated at the particle\n"
@@ -571,6 +593,9 @@ int main(int argc, char* argv[]) {
     return 2;
   }
   if (tracers_sort_every && !tracers) { std::fprintf(stderr, "ekpnp_main: --tracers-sort-every %u: there is no cloud to sort (give --tracers N or --tracers-grid gx,gy,gz)\n", tracers_sort_every); return 2; }
+  if ((tracers_brownian || tracers_noise_seed_given) && !tracers) { std::fprintf(stderr, "ekpnp_main: --tracers-diffusivity / --tracers-noise-seed: there is no cloud to diffuse (give --tracers N or --tracers-grid gx,gy,gz)\n"); return 2; }
+  if (tracers_noise_seed_given && !tracers_brownian) { std::fprintf(stderr, "ekpnp_main: --tracers-noise-seed %llu: there is no noise to seed (give --tracers-diffusivity D)\n", tracers_noise_seed); return 2; }
+  if (tracers_brownian && (!std::isfinite(tracers_D) || tracers_D < 0.0)) { std::fprintf(stderr, "ekpnp_main: --tracers-diffusivity: tracers: D = %.17g (must be finite and >= 0)\n", tracers_D); return 2; }
   if (tracks_flags) {
     if (gpus > 1 || !devices.empty()) { std::fprintf(stderr, "ekpnp_main: --tracks*: tracers: slab contexts are not supported (one GPU only)\n"); return 2; }
     if (!tracers) { std::fprintf(stderr, "ekpnp_main: --tracks*: there is no cloud to tag (give --tracers N or --tracers-grid gx,gy,gz)\n"); return 2; }
@@ -703,7 +728,8 @@ int main(int argc, char* argv[]) {
     }
     if (tracers && (i + 1) % tracers_every == 0) {  // enqueues only: the cloud moves through the fields of this moment
       if (tracers_sort_every && ++tracers_advances % tracers_sort_every == 0) CK(ekpnp_tracers_sort(ctx));
-      CK(ekpnp_tracers_advance(ctx, tracers_mu, (double)tracers_every * P.dt, tracers_substeps));
+      if (tracers_brownian) CK(ekpnp_tracers_advance_brownian(ctx, tracers_mu, tracers_D, (double)tracers_every * P.dt, tracers_substeps, (uint64_t)tracers_noise_seed));
+      else CK(ekpnp_tracers_advance(ctx, tracers_mu, (double)tracers_every * P.dt, tracers_substeps));
       CK(ekpnp_tracers_record(ctx, (int64_t)(i + 1), t));
     }
     if (tracks && (i + 1) % tracks_every == 0) CK(ekpnp_tracks_record(ctx, (int64_t)(i + 1), t));  // enqueues only: after this iteration's advance

@@ -1,5 +1,5 @@
 // philox.h — the counter-based generator behind ekpnp_seed_uniform (include/ekpnp.h), shared by seed.hip (noise on the fields)
-// and tracers.hip (random start positions).  Host and device run the same integer arithmetic: the same bits everywhere.
+// and tracers.hip (random start positions, and the kicks of Brownian tracers: tr_kick).  Host and device run the same integer arithmetic: the same bits everywhere.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -7,12 +7,17 @@
 //                            midpoint substeps run inside the kernel (the fields are frozen during the call).  An evaluation
 //                            computes the 8-node stencil once and issues its 24 loads (MOB, mu != 0: 48, E beside u) before the
 //                            first is used.  No LDS, no atomics.  Every index is clamped to the lattice before any load.
+//   k_tracers_advance_brownian<MOB>   the same thread per particle, and after every midpoint substep a kick: one Philox4x32-10 call of
+//                            (seed, the particle's ID, the cloud's epoch + the substep), three numbers in (-1, 1) times the kick
+//                            lengths the host formed, x and y folded, z reflected at the plates.  The id array is read only when
+//                            the cloud has one (a wave-uniform branch).  No LDS, no atomics, no scratch, no square root.
 //   k_tracers_seed           a thread per particle: Philox numbers (RANDOM) or three tables the host made (GRID)
 //   k_tracers_cells<LDS>     counts per cell of a bx x by x bz partition: uint32 counters in LDS where the table fits 32 KB, flushed
 //                            with 64-bit integer atomics; 64-bit global integer atomics otherwise.  Counts are integers: exact.
 //   k_tracers_partials / k_tracers_finish   the 12 moments, the scheme of stats.hip over particles: runs of 4096 particles per
 //                            workgroup, thread t adds t, t + 256, ... ascending, reduce.h's trees, partial sums in ascending order
-// ekpnp_tracers_advance_host IS the definition of an advance and ekpnp_tracers_seed_host of a seed; the device leaves their bits by
+// ekpnp_tracers_advance_host IS the definition of an advance, ekpnp_tracers_advance_brownian_host of a Brownian one (both call
+// tr_midpoint, the midpoint substep) and ekpnp_tracers_seed_host of a seed; the device leaves their bits by
 // construction: stencil, interpolation, fold and step are ONE __host__ __device__ function each, the step constants are formed
 // once on the host, and this object is built with -ffp-contract=off (csrc/Makefile, PINNED), so that neither side fuses a
 // multiply-add.  The passive and the mu != 0 kernel are two instantiations of one template; mu alone chooses, not the shape.
@@ -194,39 +199,111 @@ __host__ __device__ __forceinline__ bool tr_fold_z(double& z, double top) {
   return true;
 }
 
+// one midpoint substep (include/ekpnp.h, step 5) of a particle that is not lost: true, and x, y, z and the image counts are the
+// new ones; false: the particle is lost and nothing was written
+template <bool MOB>
+__host__ __device__ __forceinline__ bool tr_midpoint(const TrFields& f, const TrStep& s, double px, double py, double top, double& x, double& y, double& z, int& wx, int& wy) {
+  double w[3];
+  tr_velocity<MOB>(f, s, x, y, z, w);
+  double t = s.ax * w[0];
+  double x1 = x + t;
+  t = s.ay * w[1];
+  double y1 = y + t;
+  t = s.az * w[2];
+  double z1 = z + t;
+  int none = 0;
+  bool ok = tr_fold(x1, px, none);
+  ok = tr_fold(y1, py, none) && ok;
+  ok = tr_fold_z(z1, top) && ok;
+  if (ok) {
+    tr_velocity<MOB>(f, s, x1, y1, z1, w);
+    t = s.hx * w[0];
+    x1 = x + t;
+    t = s.hy * w[1];
+    y1 = y + t;
+    t = s.hz * w[2];
+    z1 = z + t;
+    int nwx = wx, nwy = wy;
+    ok = tr_fold(x1, px, nwx);
+    ok = tr_fold(y1, py, nwy) && ok;
+    ok = tr_fold_z(z1, top) && ok;
+    if (ok) { x = x1; y = y1; z = z1; wx = nwx; wy = nwy; }
+  }
+  return ok;
+}
+
 // nsub midpoint substeps of one particle that is not lost on entry
 template <bool MOB>
 __host__ __device__ __forceinline__ void tr_advance(const TrFields& f, const TrStep& s, double& x, double& y, double& z, int& wx, int& wy) {
   const double px = (double)s.nx, py = (double)s.ny, top = (double)(s.nz - 1);
   for (int it = 0; it < s.nsub; ++it) {
-    double w[3];
-    tr_velocity<MOB>(f, s, x, y, z, w);
-    double t = s.ax * w[0];
-    double x1 = x + t;
-    t = s.ay * w[1];
-    double y1 = y + t;
-    t = s.az * w[2];
-    double z1 = z + t;
-    int none = 0;
-    bool ok = tr_fold(x1, px, none);
-    ok = tr_fold(y1, py, none) && ok;
-    ok = tr_fold_z(z1, top) && ok;
-    if (ok) {
-      tr_velocity<MOB>(f, s, x1, y1, z1, w);
-      t = s.hx * w[0];
-      x1 = x + t;
-      t = s.hy * w[1];
-      y1 = y + t;
-      t = s.hz * w[2];
-      z1 = z + t;
-      int nwx = wx, nwy = wy;
-      ok = tr_fold(x1, px, nwx);
-      ok = tr_fold(y1, py, nwy) && ok;
-      ok = tr_fold_z(z1, top) && ok;
-      if (ok) { x = x1; y = y1; z = z1; wx = nwx; wy = nwy; }
-    }
+    const bool ok = tr_midpoint<MOB>(f, s, px, py, top, x, y, z, wx, wy);
     if (!ok) {  // lost: the image counts stay what they were
       x = y = z = NAN;
+      return;
+    }
+  }
+}
+
+// ---- Brownian substeps (include/ekpnp.h: ekpnp_tracers_advance_brownian_host IS the definition) -------------------------------
+// the noise of a call: the kick lengths in cells, formed once on the host (the device takes no square root), the seed, and the
+// epoch of the call's first substep
+struct TrNoise {
+  double kx, ky, kz;
+  uint64_t seed;
+  int64_t epoch;
+};
+constexpr uint32_t TR_KICK_TAG = 0x80000000u;  // the fourth counter word of a kick is never 0, which is seed_uniform's
+
+// r[0..2] of (seed, id, epoch): one Philox call; ((double)(int32)word + 0.5) * 2^-31 is exact, symmetric, never 0, in (-1, 1)
+__host__ __device__ __forceinline__ void tr_kick(uint64_t seed, int64_t id, int64_t epoch, double r[3]) {
+  const uint64_t i = (uint64_t)id, e = (uint64_t)epoch;
+  uint32_t c[4] = {(uint32_t)(i & 0xffffffffu), (uint32_t)(e & 0xffffffffu), (uint32_t)(e >> 32), TR_KICK_TAG | (uint32_t)(i >> 32)};
+  philox4x32_10(c, (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32));
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const double v = (double)(int32_t)c[a];
+    const double s = v + 0.5;
+    r[a] = s * 0x1.0p-31;
+  }
+}
+
+// z after a kick, reflected at the plates and then held by them (a kick longer than the channel); false (NaN, Inf): lost
+__host__ __device__ __forceinline__ bool tr_reflect_z(double& z, double top) {
+  if (z < 0.0) z = 0.0 - z;
+  if (z > top) {
+    const double d = z - top;
+    z = top - d;
+  }
+  return tr_fold_z(z, top);
+}
+
+// nsub Brownian substeps of the particle `id`, not lost on entry: the midpoint substep, the kick of (seed, id, epoch + it), the
+// fold of x and y with their image counts, the reflection of z
+template <bool MOB>
+__host__ __device__ __forceinline__ void tr_advance_brownian(const TrFields& f, const TrStep& s, const TrNoise& q, int64_t id, double& x, double& y, double& z,
+                                                             int& wx, int& wy) {
+  const double px = (double)s.nx, py = (double)s.ny, top = (double)(s.nz - 1);
+  for (int it = 0; it < s.nsub; ++it) {
+    const int owx = wx, owy = wy;
+    bool ok = tr_midpoint<MOB>(f, s, px, py, top, x, y, z, wx, wy);
+    if (ok) {
+      double r[3];
+      tr_kick(q.seed, id, q.epoch + (int64_t)it, r);
+      double t = q.kx * r[0];
+      x = x + t;
+      t = q.ky * r[1];
+      y = y + t;
+      t = q.kz * r[2];
+      z = z + t;
+      ok = tr_fold(x, px, wx);
+      ok = tr_fold(y, py, wy) && ok;
+      ok = tr_reflect_z(z, top) && ok;
+    }
+    if (!ok) {  // lost: the image counts stay what they were before the substep
+      x = y = z = NAN;
+      wx = owx;
+      wy = owy;
       return;
     }
   }
@@ -264,6 +341,23 @@ __global__ void __launch_bounds__(TR_THREADS) k_tracers_advance(TrFields f, TrSt
   if (tr_lost(x, y, z)) return;  // nothing is read, nothing is written
   int wx = c.wx[i], wy = c.wy[i];
   tr_advance<MOB>(f, s, x, y, z, wx, wy);
+  c.x[i] = x;
+  c.y[i] = y;
+  c.z[i] = z;
+  c.wx[i] = wx;
+  c.wy[i] = wy;
+}
+
+// ids == null: the cloud was never sorted and the id of a particle is its slot (a kernel argument: the branch is wave-uniform)
+template <bool MOB>
+__global__ void __launch_bounds__(TR_THREADS) k_tracers_advance_brownian(TrFields f, TrStep s, TrNoise q, TrCloud c, const int32_t* __restrict__ ids) {
+  const long long i = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
+  if (i >= c.n) return;
+  double x = c.x[i], y = c.y[i], z = c.z[i];
+  if (tr_lost(x, y, z)) return;  // nothing is read, nothing is written
+  const int64_t id = ids ? (int64_t)ids[i] : (int64_t)i;
+  int wx = c.wx[i], wy = c.wy[i];
+  tr_advance_brownian<MOB>(f, s, q, id, x, y, z, wx, wy);
   c.x[i] = x;
   c.y[i] = y;
   c.z[i] = z;
@@ -709,6 +803,7 @@ struct TracerState {
   int32_t* ids = nullptr;
   size_t ids_bytes = 0;
   bool has_ids = false;       // false: the ids are 0 .. n-1, whatever `ids` holds
+  int64_t epoch = 0;          // Brownian substeps taken since the cloud was seeded or set (a load restores it): the noise's clock
   double* samp = nullptr;     // ekpnp_tracers_sample's scratch [nvalues][n], grown on demand, dropped with the cloud
   size_t samp_bytes = 0;
   Ring tracks;                // rows of [ntags][5 + nvalues] doubles behind a header of four int32 tables [ntags] (TrTags)
@@ -827,6 +922,15 @@ static int tracers_check_advance(double mu, double h, int nsub, std::string& err
   return EKPNP_OK;
 }
 
+// the diffusivity of a Brownian advance beside tracers_check_advance: D finite and >= 0, and 6 D h >= 0 and finite (its root is taken)
+static int tracers_check_brownian(double D, double h, std::string& err) {
+  if (!std::isfinite(D) || D < 0.0) { err = "tracers: D = " + num(D) + " (must be finite and >= 0)"; return EKPNP_ERR_INVALID; }
+  const double t = 6.0 * D;
+  const double m = t * h;
+  if (!(m >= 0.0) || !std::isfinite(m)) { err = "tracers: D*h = " + num(D * h) + " (must be >= 0, and 6*D*h finite: diffusion does not run backwards)"; return EKPNP_ERR_INVALID; }
+  return EKPNP_OK;
+}
+
 static const char* const kValueNames[TR_MAXV] = {"rho", "c", "cn", "phi", "ux", "uy", "uz", "Ex", "Ey", "Ez", "T", "q"};
 
 // the values of a sample (min_values 1) or of a track (0: positions only)
@@ -901,6 +1005,20 @@ static TrStep tr_step_of(const ekpnp_params& p, double mu, double h, int nsub) {
   return s;
 }
 
+// the kick lengths sqrt(6 D h) in cells, operation by operation: the host's square root is correctly rounded
+static TrNoise tr_noise_of(const ekpnp_params& p, double D, double h, uint64_t seed, int64_t epoch) {
+  TrNoise q{};
+  const double t = 6.0 * D;
+  const double m = t * h;
+  const double r = std::sqrt(m);
+  q.kx = r / p.dx;
+  q.ky = r / p.dy;
+  q.kz = r / p.dz;
+  q.seed = seed;
+  q.epoch = epoch;
+  return q;
+}
+
 }  // namespace ekpnp
 
 // ---- host only ---------------------------------------------------------------------------------------------------------------
@@ -956,6 +1074,37 @@ extern "C" int ekpnp_tracers_advance_host(const ekpnp_params* p, const double* u
     int a = wx[i], b = wy[i];
     if (mu != 0.0) tr_advance<true>(f, s, x[i], y[i], z[i], a, b);
     else tr_advance<false>(f, s, x[i], y[i], z[i], a, b);
+    wx[i] = a;
+    wy[i] = b;
+  }
+  return EKPNP_OK;
+}
+
+extern "C" void ekpnp_tracers_kick(uint64_t seed, int64_t id, int64_t epoch, double r[3]) {
+  if (r) tr_kick(seed, id, epoch, r);
+}
+
+extern "C" int ekpnp_tracers_advance_brownian_host(const ekpnp_params* p, const double* ux, const double* uy, const double* uz, const double* ex, const double* ey,
+                                                   const double* ez, int64_t n, const int32_t* ids, double* x, double* y, double* z, int32_t* wx, int32_t* wy,
+                                                   double mu, double D, double h, int nsub, uint64_t seed, int64_t epoch) {
+  std::string err;
+  int rc = EKPNP_ERR_INVALID;
+  if (!p) err = "tracers: NULL parameters";
+  else if ((rc = tracers_check_lattice(*p, err)) == EKPNP_OK && (rc = tracers_check_advance(mu, h, nsub, err)) == EKPNP_OK && (rc = tracers_check_brownian(D, h, err)) == EKPNP_OK) {
+    if (n < 0 || n > EKPNP_TRACERS_MAX_N) { err = "tracers: n = " + std::to_string((long long)n) + " outside 0 .. " + std::to_string((long long)EKPNP_TRACERS_MAX_N); rc = EKPNP_ERR_INVALID; }
+    else if (epoch < 0 || epoch > INT64_MAX - nsub) { err = "tracers: epoch = " + std::to_string((long long)epoch) + " (must be >= 0, and epoch + nsub must fit 63 bits)"; rc = EKPNP_ERR_INVALID; }
+    else if (!ux || !uy || !uz || !x || !y || !z || !wx || !wy || (mu != 0.0 && (!ex || !ey || !ez))) { err = "tracers: NULL pointer"; rc = EKPNP_ERR_INVALID; }
+  }
+  if (rc) { set_create_error(err); return rc; }
+  const TrFields f{{ux, uy, uz}, {ex, ey, ez}};
+  const TrStep s = tr_step_of(*p, mu, h, nsub);
+  const TrNoise q = tr_noise_of(*p, D, h, seed, epoch);
+  for (int64_t i = 0; i < n; ++i) {
+    if (tr_lost(x[i], y[i], z[i])) continue;
+    const int64_t id = ids ? (int64_t)ids[i] : i;
+    int a = wx[i], b = wy[i];
+    if (mu != 0.0) tr_advance_brownian<true>(f, s, q, id, x[i], y[i], z[i], a, b);
+    else tr_advance_brownian<false>(f, s, q, id, x[i], y[i], z[i], a, b);
     wx[i] = a;
     wy[i] = b;
   }
@@ -1079,6 +1228,7 @@ static inline unsigned tr_blocks(long long n, int per) { return (unsigned)((n + 
 static int tracers_upload(Ctx& c, long long n, const double* const pos[6], const int32_t* wx, const int32_t* wy) {
   if (int rc = tracers_alloc(c, n)) return rc;
   c.tracers->has_ids = false;  // a new cloud: slot s holds particle s (a load that carries ids puts them back)
+  c.tracers->epoch = 0;        // and no Brownian substep was taken (a load puts its file's epoch back)
   c.tracers->tracks.armed = false;  // and the tags of an armed track ring named particles of the old one
   const TrCloud d = c.tracers->dev();
   double* const dst[6] = {d.x, d.y, d.z, d.x0, d.y0, d.z0};
@@ -1099,6 +1249,7 @@ extern "C" int ekpnp_tracers_seed(ekpnp_ctx* ctx, const ekpnp_tracers_spec* spec
   if (int rc = tracers_alloc(c, (long long)spec->n)) return rc;
   TracerState& t = *c.tracers;
   t.has_ids = false;
+  t.epoch = 0;
   t.tracks.armed = false;  // the tags named particles of the cloud that is replaced here (the rows stay readable)
   TrSeedArgs a{};
   for (int q = 0; q < 3; ++q) {
@@ -1202,6 +1353,37 @@ extern "C" int ekpnp_tracers_advance(ekpnp_ctx* ctx, double mu, double h, int ns
   else hipLaunchKernelGGL((k_tracers_advance<false>), grid, block, 0, c.stream, f, s, t->dev());
   note_launch(c, "k_tracers_advance");
   if (take_launch_error(c) != hipSuccess) return EKPNP_ERR_HIP;
+  return EKPNP_OK;
+}
+
+extern "C" int ekpnp_tracers_advance_brownian(ekpnp_ctx* ctx, double mu, double D, double h, int nsub, uint64_t seed) {
+  NEEDSINGLE(ctx);
+  if (int rc = tracers_check_advance(mu, h, nsub, c.err)) return rc;
+  if (int rc = tracers_check_brownian(D, h, c.err)) return rc;
+  TracerState* t = cloud_of(c);
+  if (!t) return fail(c, "tracers: no cloud (seed, set or load one first)");
+  if (t->epoch > INT64_MAX - nsub) { c.err = "tracers: epoch = " + std::to_string((long long)t->epoch) + " (epoch + nsub must fit 63 bits)"; return EKPNP_ERR_INVALID; }
+  const bool mob = mu != 0.0;
+  if (mob)
+    if (int rc = ensure_efield(c)) return rc;  // as ekpnp_tracers_advance (mu == 0: lazy E is left alone)
+  const TrFields f{{c.fld[EKPNP_UX], c.fld[EKPNP_UY], c.fld[EKPNP_UZ]}, {c.fld[EKPNP_EX], c.fld[EKPNP_EY], c.fld[EKPNP_EZ]}};
+  const TrStep s = tr_step_of(c.p, mu, h, nsub);
+  const TrNoise q = tr_noise_of(c.p, D, h, seed, t->epoch);
+  const int32_t* ids = t->has_ids ? t->ids : nullptr;
+  const dim3 grid(tr_blocks(t->n, TR_THREADS)), block(TR_THREADS);
+  if (mob) hipLaunchKernelGGL((k_tracers_advance_brownian<true>), grid, block, 0, c.stream, f, s, q, t->dev(), ids);
+  else hipLaunchKernelGGL((k_tracers_advance_brownian<false>), grid, block, 0, c.stream, f, s, q, t->dev(), ids);
+  note_launch(c, "k_tracers_advance_brownian");
+  if (take_launch_error(c) != hipSuccess) return EKPNP_ERR_HIP;
+  t->epoch += nsub;  // every Brownian advance, whether or not particles were lost
+  return EKPNP_OK;
+}
+
+extern "C" int ekpnp_tracers_epoch(ekpnp_ctx* ctx, int64_t* epoch) {
+  NEEDSINGLE(ctx);
+  if (!epoch) return fail(c, "NULL pointer");
+  TracerState* t = cloud_of(c);
+  *epoch = t ? t->epoch : 0;
   return EKPNP_OK;
 }
 
@@ -1321,6 +1503,7 @@ extern "C" int ekpnp_tracers_save(ekpnp_ctx* ctx, const char* path, double time)
   h.n = (int64_t)n;
   h.time = time;
   h.reserved = t->has_ids ? 1 : 0;  // a cloud that was never sorted writes the file it always wrote
+  h.reserved2 = t->epoch;           // and so does one that never took a Brownian substep: 0
   bool ok = std::fwrite(&h, sizeof h, 1, f) == 1;
   std::vector<double> buf(n);
   const TrCloud d = t->dev();
@@ -1357,6 +1540,7 @@ extern "C" int ekpnp_tracers_load(ekpnp_ctx* ctx, const char* path, double* time
   }
   if (h.n < 1 || h.n > EKPNP_TRACERS_MAX_N) { std::fclose(f); c.err = "tracers: n = " + std::to_string((long long)h.n) + " in the file, outside 1 .. " + std::to_string((long long)EKPNP_TRACERS_MAX_N); return EKPNP_ERR_INVALID; }
   if (h.reserved != 0 && h.reserved != 1) { std::fclose(f); c.err = "tracers: reserved = " + std::to_string(h.reserved) + " in the file (0: no ids, 1: ids follow; nothing else is known)"; return EKPNP_ERR_INVALID; }
+  if (h.reserved2 < 0) { std::fclose(f); c.err = "tracers: reserved2 = " + std::to_string((long long)h.reserved2) + " in the file (the epoch of the noise: must be >= 0)"; return EKPNP_ERR_INVALID; }
   const size_t n = (size_t)h.n;
   std::vector<double> pos[6];
   std::vector<int32_t> w[2], ids;
@@ -1391,6 +1575,7 @@ extern "C" int ekpnp_tracers_load(ekpnp_ctx* ctx, const char* path, double* time
     HIPCHK(c, hipMemcpy(t.ids, ids.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
     t.has_ids = true;
   }
+  c.tracers->epoch = h.reserved2;
   *time = h.time;
   return EKPNP_OK;
 }

@@ -466,6 +466,38 @@ def tracers_advance_host(p: "Params", u, x, y, z, wx=None, wy=None, E=None, mu: 
     return x, y, z, wx, wy
 
 
+def tracers_kick(seed: int, id: int, epoch: int) -> np.ndarray:
+    """r[0..2] in (-1, 1): the draw of particle `id` at substep `epoch` of a Brownian advance - one Philox4x32-10 call, exact in
+    FP64 (ekpnp_tracers_kick, host only)"""
+    r = np.empty(3, dtype=np.float64)
+    load_library().ekpnp_tracers_kick(int(seed), int(id), int(epoch), _ptr(r))
+    return r
+
+
+def tracers_advance_brownian_host(p: "Params", u, x, y, z, wx=None, wy=None, E=None, mu: float = 0.0, D: float = 0.0, h: float = 0.0, nsub: int = 1,
+                                  seed: int = 0, epoch: int = 0, ids=None):
+    """nsub Brownian substeps of h seconds - the midpoint substep of tracers_advance_host, a uniform kick of variance 2 D h, x and y
+    folded, z reflected at the plates - with the numbers of (seed, ids[i] or i, epoch .. epoch + nsub - 1): THE definition of a
+    Brownian advance (ekpnp_tracers_advance_brownian_host, host only).  Returns new (x, y, z, wx, wy)."""
+    L = load_library()
+    shape = (p.nz, p.ny, p.nx)
+    u = [np.ascontiguousarray(a, dtype=np.float64).reshape(shape) for a in u]
+    e = [None] * 3 if E is None else [np.ascontiguousarray(a, dtype=np.float64).reshape(shape) for a in E]
+    x, y, z = (np.array(a, dtype=np.float64).ravel() for a in (x, y, z))
+    n = x.size
+    wx = np.zeros(n, dtype=np.int32) if wx is None else np.array(wx, dtype=np.int32).ravel()
+    wy = np.zeros(n, dtype=np.int32) if wy is None else np.array(wy, dtype=np.int32).ravel()
+    ids = None if ids is None else np.ascontiguousarray(ids, dtype=np.int32).ravel()
+    if not (y.size == z.size == wx.size == wy.size == n) or (ids is not None and ids.size != n):
+        raise ValueError("tracers_advance_brownian_host: x, y, z, wx, wy, ids differ in length")
+    rc = L.ekpnp_tracers_advance_brownian_host(C.byref(p), *[_ptr(a) for a in u], *[None if a is None else _ptr(a) for a in e], n,
+                                               None if ids is None else _ptr(ids), _ptr(x), _ptr(y), _ptr(z), _ptr(wx), _ptr(wy),
+                                               float(mu), float(D), float(h), int(nsub), int(seed), int(epoch))
+    if rc:
+        _tracers_fail(L, "ekpnp_tracers_advance_brownian_host", rc)
+    return x, y, z, wx, wy
+
+
 def tracers_cell(p: "Params", cells, x, y, z) -> np.ndarray:
     """the cell (cz*by + cy)*bx + cx of every position in a cells = (bx, by, bz) partition, -1 for a lost particle: THE definition
     (ekpnp_tracers_cell, host only)"""
@@ -1080,6 +1112,10 @@ def load_library():
         "ekpnp_tracers_size": (i32, [ctx, C.POINTER(C.c_int64)]),
         "ekpnp_tracers_release": (i32, [ctx]),
         "ekpnp_tracers_advance": (i32, [ctx, dbl, dbl, i32]),
+        "ekpnp_tracers_kick": (None, [C.c_uint64, C.c_int64, C.c_int64, C.c_void_p]),
+        "ekpnp_tracers_advance_brownian_host": (i32, [C.POINTER(Params)] + [C.c_void_p] * 6 + [C.c_int64] + [C.c_void_p] * 6 + [dbl, dbl, dbl, i32, C.c_uint64, C.c_int64]),
+        "ekpnp_tracers_advance_brownian": (i32, [ctx, dbl, dbl, dbl, i32, C.c_uint64]),
+        "ekpnp_tracers_epoch": (i32, [ctx, C.POINTER(C.c_int64)]),
         "ekpnp_tracers_save": (i32, [ctx, C.c_char_p, dbl]),
         "ekpnp_tracers_load": (i32, [ctx, C.c_char_p, pd]),
         "ekpnp_tracers_cell_counts": (i32, [ctx, i32, i32, i32, C.c_void_p, C.POINTER(C.c_int64)]),
@@ -1455,10 +1491,21 @@ class Solver(_Diagnostics):
     def tracers_release(self):
         self._call("tracers_release")
 
-    def tracers_advance(self, h: float, nsub: int = 1, mu: float = 0.0):
+    def tracers_advance(self, h: float, nsub: int = 1, mu: float = 0.0, D: float = None, seed: int = 0):
         """nsub midpoint substeps of h seconds through the current, frozen fields with velocity u + mu E; enqueues only (place it
-        between two step() calls).  mu != 0 brings a lazy solve's E arrays up to date first."""
-        self._call("tracers_advance", float(mu), float(h), int(nsub))
+        between two step() calls).  mu != 0 brings a lazy solve's E arrays up to date first.  With a diffusivity D (m^2/s, 0.0
+        allowed) every substep also kicks the particle by the numbers of (seed, its id, the cloud's epoch) and reflects it at the
+        plates (ekpnp_tracers_advance_brownian); D=None is the deterministic advance."""
+        if D is None:
+            self._call("tracers_advance", float(mu), float(h), int(nsub))
+        else:
+            self._call("tracers_advance_brownian", float(mu), float(D), float(h), int(nsub), int(seed))
+
+    def tracers_epoch(self) -> int:
+        """Brownian substeps taken since the cloud was seeded or set (a load restores the file's): the clock of the noise"""
+        e = C.c_int64()
+        self._call("tracers_epoch", C.byref(e))
+        return int(e.value)
 
     def tracers_save(self, path: str, time: float = 0.0):
         self._call("tracers_save", os.fsencode(path), float(time))

@@ -785,6 +785,49 @@ int ekpnp_tracers_get(ekpnp_ctx* ctx, double* x, double* y, double* z, int32_t* 
 int ekpnp_tracers_size(ekpnp_ctx* ctx, int64_t* n);
 int ekpnp_tracers_release(ekpnp_ctx* ctx);
 int ekpnp_tracers_advance(ekpnp_ctx* ctx, double mu, double h, int nsub);                          /* enqueues only */
+/* BROWNIAN TRACERS - particles that diffuse as well as drift.  A particle with mobility mu and diffusivity D (m^2/s) is a
+ * Lagrangian ion (Einstein: D = mu kT/e): its cell counts relax to the Boltzmann profile of a Debye layer, its mean squared
+ * displacement in a roll is the effective dispersion.  ekpnp_tracers_advance_brownian_host IS the definition of a Brownian
+ * advance, and the device leaves exactly its bits; like the advance it is written operation by operation, every operation
+ * rounded once, no fused multiply-add.
+ * THE DRAW, kick: one Philox4x32-10 call with the counter {low word of id, low word of epoch, high word of epoch,
+ * 0x80000000 | high word of id} and the key {low word of seed, high word of seed}.  The fourth counter word is never 0, which is
+ * what every counter of ekpnp_seed_uniform has there: no draw of a kick repeats a number of a seed.  An id of a cloud is below
+ * 2^28, so for a cloud the fourth word is the fixed tag 0x80000000.  With w[0..3] the output words:
+ *   r[a] = ((double)(int32_t)w[a] + 0.5) * 2^-31   for a = 0, 1, 2   (v = (double)(int32_t)w[a]; s = v + 0.5; r = s * 2^-31)
+ * exact in FP64, symmetric about 0, never 0, inside (-1, 1).  No log, cos or sqrt runs per particle: nothing depends on a math
+ * library.  THE INCREMENT IS UNIFORM, with the variance of the Gaussian it replaces (k*r with k = sqrt(6 D h) has variance
+ * k^2/3 = 2 D h): the usual weak first-order scheme - means, variances and stationary profiles converge as with Gaussian
+ * increments, single paths do not look Gaussian below a few substeps.
+ * THE STEP CONSTANTS, formed once on the host: those of an advance, and t = 6.0*D; m = t*h; q = sqrt(m) (correctly rounded);
+ * kx = q/dx; ky = q/dy; kz = q/dz - the kick lengths in cells.  The device never takes a square root.
+ * A BROWNIAN SUBSTEP `it` (0 .. nsub-1) of a particle that is not lost:
+ *  (a) exactly the midpoint substep of ekpnp_tracers_advance_host (steps 2 - 6 above: both evaluations, both folds, z held by
+ *      the plates): x1, y1, z1 and the image counts; a particle lost there is lost.
+ *  (b) the kick: r = kick(seed, id, epoch + it); t = kx*r[0]; x2 = x1 + t; likewise y with ky and r[1], z with kz and r[2].
+ *  (c) x2 and y2 are folded as in step 6, the image counts go on counting; more than a period loses the particle.
+ *  (d) z is REFLECTED at the plates: if (z < 0.0) z = 0.0 - z; if (z > top) { d = z - top; z = top - d; } with
+ *      top = (double)(nz-1); then the hold of step 6 (a NaN or infinite z loses the particle; z < 0.0 becomes 0.0, z > top becomes
+ *      top), which also catches a kick longer than the channel.  Holding alone would pile a diffusing cloud onto the wall.
+ *  A lost particle: as step 7.  D == 0.0 is allowed: the kick is +-0.0 and the numbers are those of ekpnp_tracers_advance_host
+ *  (equal as numbers; a coordinate of -0.0 may come out as +0.0).
+ * WHICH NUMBERS A PARTICLE GETS: id is the particle's id - its slot in a cloud that was never sorted, what ekpnp_tracers_ids
+ * reports otherwise (advance_brownian_host: ids[i], or i when ids is NULL) - so A SORT CHANGES NO TRAJECTORY.  epoch belongs to the
+ * cloud: 0 after seed and set, and every ekpnp_tracers_advance_brownian adds nsub to it, whether or not particles were lost
+ * (D == 0.0 included); ekpnp_tracers_epoch reads it (0 without a cloud).  It travels in the cloud's file (below), so that save,
+ * load and continue draws the numbers of not having stopped.  Two calls of nsub = a and b equal one of a + b.
+ * Refusals (EKPNP_ERR_INVALID, the message gives the number; ekpnp_last_error of NULL for the host function): those of an advance
+ * (mu, h not finite, nsub outside 1 .. 4096, NULL E arrays with mu != 0.0), D negative or not finite, D*h < 0 (diffusion does
+ * not run backwards; also 6*D*h not finite), a negative epoch, n outside 0 .. 2^28.
+ * On the device: k_tracers_advance_brownian, one thread per particle, workgroups of 256, the nsub loop inside, the functions of
+ * the host; the id array is read only when the cloud has one; no atomics, no LDS, no scratch.  ekpnp_tracers_advance_brownian
+ * ENQUEUES ONLY; lazy E, the step graph and "batch_moments": as for ekpnp_tracers_advance. */
+void ekpnp_tracers_kick(uint64_t seed, int64_t id, int64_t epoch, double r[3]);                    /* host only */
+int ekpnp_tracers_advance_brownian_host(const ekpnp_params* p, const double* ux, const double* uy, const double* uz, const double* ex, const double* ey,
+                                        const double* ez, int64_t n, const int32_t* ids /* NULL: 0 .. n-1 */, double* x, double* y, double* z, int32_t* wx,
+                                        int32_t* wy, double mu, double D, double h, int nsub, uint64_t seed, int64_t epoch);
+int ekpnp_tracers_advance_brownian(ekpnp_ctx* ctx, double mu, double D, double h, int nsub, uint64_t seed);   /* enqueues only */
+int ekpnp_tracers_epoch(ekpnp_ctx* ctx, int64_t* epoch);
 /* sort ENQUEUES ONLY: it permutes all eight arrays of the cloud (x, y, z, x0, y0, z0, wx, wy) by the perm ekpnp_tracers_sort_host
  * gives for the current positions, and composes the ids: id_new[s] = id_old[perm[s]].  id[s] is the index the particle in slot s
  * had when the cloud was last seeded, set or loaded; seed, set and a load of a file without ids reset the ids to 0 .. n-1.  A
@@ -800,11 +843,13 @@ int ekpnp_tracers_advance(ekpnp_ctx* ctx, double mu, double h, int nsub);       
 int ekpnp_tracers_sort(ekpnp_ctx* ctx);                                                            /* enqueues only */
 int ekpnp_tracers_ids(ekpnp_ctx* ctx, int32_t* id);
 /* The cloud's own file, raw little-endian: a 48-byte header {"EKPNPTR1", int32 nx, ny, nz, reserved, int64 n, double time,
- * int64 reserved 0}, then x, y, z, x0, y0, z0 as FP64 [n] each, then wx, wy as int32 [n] each: 48 + 56 n bytes with reserved 0,
+ * int64 reserved2}, then x, y, z, x0, y0, z0 as FP64 [n] each, then wx, wy as int32 [n] each: 48 + 56 n bytes with reserved 0,
  * what a cloud that was never sorted writes.  A sorted cloud writes reserved 1 and the ids as int32 [n] after wy: 48 + 60 n bytes.
- * load accepts both and refuses any other reserved value, ids that are not a permutation of 0 .. n-1 (the message names the
- * first offending slot), another lattice, a short file and a position outside the invariant; loading and continuing equals not
- * having stopped, bit for bit, ids included. */
+ * reserved2 is the cloud's epoch (ekpnp_tracers_epoch): 0 for a cloud that never took a Brownian substep, which so writes the
+ * bytes it always wrote.  load accepts both and refuses any other reserved value, a negative reserved2 (the message gives it),
+ * ids that are not a permutation of 0 .. n-1 (the message names the first offending slot), another lattice, a short file and a
+ * position outside the invariant; it restores the epoch; loading and continuing equals not having stopped, bit for bit, ids
+ * and noise included. */
 int ekpnp_tracers_save(ekpnp_ctx* ctx, const char* path, double time);
 int ekpnp_tracers_load(ekpnp_ctx* ctx, const char* path, double* time);
 /* Cell counts (synchronous): counts[bz][by][bx] of the alive particles by ekpnp_tracers_cell, and the number of lost ones;
