@@ -104,6 +104,9 @@ int main(int argc, char* argv[]) {
   bool tracers_brownian = false, tracers_noise_seed_given = false;
   double tracers_D = 0.0;
   unsigned long long tracers_noise_seed = 0;
+  // --tracers-absorb bottom|top|both [--arrivals-bins N] [--deposit-cells bx,by]: the advances are absorbing (ekpnp_tracers_advance_absorbing;
+  // D from --tracers-diffusivity, else 0); landings.bin, arrivals.dat and deposit.dat at the end
+  int tracers_absorb = 0, arrivals_bins = 0, deposit_cells[2] = {0, 0};
   // --tracks id,id,... / --tracks-first K: tagged particles of that cloud; after every M-th iteration (--tracks-every M, default --tracers-every) a row
   // of x, y, z, wx, wy and the --tracks-values of each goes to a ring (ekpnp_tracks_*); tracks.dat at the end
   bool tracks = false, tracks_flags = false;
@@ -371,6 +374,18 @@ int main(int argc, char* argv[]) {
       if (end == v || *end) { std::fprintf(stderr, "--tracers-noise-seed wants a number, got %s\n", v); return 2; }
       tracers_noise_seed_given = true;
     }
+    else if ((v = val("--tracers-absorb"))) {
+      tracers_absorb = !std::strcmp(v, "bottom") ? 1 : !std::strcmp(v, "top") ? 2 : !std::strcmp(v, "both") ? 3 : 0;
+      if (!tracers_absorb) { std::fprintf(stderr, "--tracers-absorb wants bottom, top or both, got %s\n", v); return 2; }
+    }
+    else if ((v = val("--arrivals-bins"))) {
+      arrivals_bins = std::atoi(v);
+      if (arrivals_bins < 1 || arrivals_bins > 4096) { std::fprintf(stderr, "--arrivals-bins wants 1 .. 4096, got %s\n", v); return 2; }
+    }
+    else if ((v = val("--deposit-cells"))) {
+      int used = 0;
+      if (std::sscanf(v, "%d,%d%n", &deposit_cells[0], &deposit_cells[1], &used) != 2 || v[used]) { std::fprintf(stderr, "--deposit-cells wants bx,by, got %s\n", v); return 2; }
+    }
     else if ((v = val("--tracers-cells"))) {
       int used = 0;
       if (std::sscanf(v, "%d,%d,%d%n", &tracers_cells[0], &tracers_cells[1], &tracers_cells[2], &used) != 3 || v[used]) { std::fprintf(stderr, "--tracers-cells wants bx,by,bz, got %s\n", v); return 2; }
@@ -436,6 +451,7 @@ int main(int argc, char* argv[]) {
                    "                  [--tracers N | --tracers-grid gx,gy,gz  [--tracers-box x0,x1,y0,y1,z0,z1] [--tracers-seed S] [--tracers-every M]\n"
                    "                   [--tracers-substeps k] [--tracers-mobility mu] [--tracers-cells bx,by,bz] [--tracers-sort-every K]\n"
                    "                   [--tracers-diffusivity D [--tracers-noise-seed S]]\n"
+                   "                   [--tracers-absorb bottom|top|both [--arrivals-bins N] [--deposit-cells bx,by]]\n"
                    "                   [--tracks id,id,... | --tracks-first K  [--tracks-values T,q,...] [--tracks-every M]]]\n"
                    "  --tracers N: N particles at random places (--tracers-seed S, default 1) - or --tracers-grid gx,gy,gz: the centres of a\n"
                    "  gx x gy x gz grid - of the box --tracers-box (lattice units; default the interior 0,nx,0,ny,1,nz-2) are advected on the\n"
@@ -454,6 +470,11 @@ int main(int argc, char* argv[]) {
                    "  uniform increment of variance 2 D h per axis and reflects it at the plates (ekpnp_tracers_advance_brownian); the numbers\n"
                    "  are those of (--tracers-noise-seed S, default 0; the particle's id; the substep's number), so a sort changes no path and\n"
                    "  both loops write the same bytes; tracers_final.bin then carries the number of Brownian substeps taken.\n"
+                   "  --tracers-absorb bottom|top|both: those plates keep what reaches them (ekpnp_tracers_advance_absorbing; D from\n"
+                   "  --tracers-diffusivity, else 0: drift alone deposits) and every particle's first arrival is recorded on the device.  At\n"
+                   "  the end landings.bin (ekpnp_landings_save), arrivals.dat - per wall the histogram of the arrival epochs 0 .. final in\n"
+                   "  --arrivals-bins N cells (default 16) - and deposit.dat - both plates' maps in --deposit-cells bx,by cells (default 8,8,\n"
+                   "  clipped to the lattice) - are written; the same bytes from both loops.\n"
                    "  --tracks id,id,... (at most 1024 particle ids of that cloud, the index a particle has when it is seeded) or --tracks-first K\n"
                    "  (ids 0 .. K-1): after every M-th iteration (--tracks-every, default --tracers-every), after that iteration's advance, a row\n"
                    "  of x, y, z, the image counts and the --tracks-values (names out of the fields and q = c - cn, interpolated at the particle\n"
@@ -596,6 +617,13 @@ int main(int argc, char* argv[]) {
   if ((tracers_brownian || tracers_noise_seed_given) && !tracers) { std::fprintf(stderr, "ekpnp_main: --tracers-diffusivity / --tracers-noise-seed: there is no cloud to diffuse (give --tracers N or --tracers-grid gx,gy,gz)\n"); return 2; }
   if (tracers_noise_seed_given && !tracers_brownian) { std::fprintf(stderr, "ekpnp_main: --tracers-noise-seed %llu: there is no noise to seed (give --tracers-diffusivity D)\n", tracers_noise_seed); return 2; }
   if (tracers_brownian && (!std::isfinite(tracers_D) || tracers_D < 0.0)) { std::fprintf(stderr, "ekpnp_main: --tracers-diffusivity: tracers: D = %.17g (must be finite and >= 0)\n", tracers_D); return 2; }
+  if ((arrivals_bins || deposit_cells[0]) && !tracers_absorb) { std::fprintf(stderr, "ekpnp_main: --arrivals-bins / --deposit-cells: no plate absorbs (give --tracers-absorb bottom|top|both)\n"); return 2; }
+  if (tracers_absorb) {
+    if (!tracers) { std::fprintf(stderr, "ekpnp_main: --tracers-absorb: there is no cloud to deposit (give --tracers N or --tracers-grid gx,gy,gz)\n"); return 2; }
+    if (!arrivals_bins) arrivals_bins = 16;
+    if (!deposit_cells[0]) { deposit_cells[0] = nx < 8 ? nx : 8; deposit_cells[1] = ny < 8 ? ny : 8; }
+    if (ekpnp_tracers_cell(&P, deposit_cells[0], deposit_cells[1], 1, 0.0, 0.0, 0.0) < -1) { std::fprintf(stderr, "ekpnp_main: --deposit-cells: %s\n", ekpnp_last_error(nullptr)); return 2; }
+  }
   if (tracks_flags) {
     if (gpus > 1 || !devices.empty()) { std::fprintf(stderr, "ekpnp_main: --tracks*: tracers: slab contexts are not supported (one GPU only)\n"); return 2; }
     if (!tracers) { std::fprintf(stderr, "ekpnp_main: --tracks*: there is no cloud to tag (give --tracers N or --tracers-grid gx,gy,gz)\n"); return 2; }
@@ -728,7 +756,8 @@ int main(int argc, char* argv[]) {
     }
     if (tracers && (i + 1) % tracers_every == 0) {  // enqueues only: the cloud moves through the fields of this moment
       if (tracers_sort_every && ++tracers_advances % tracers_sort_every == 0) CK(ekpnp_tracers_sort(ctx));
-      if (tracers_brownian) CK(ekpnp_tracers_advance_brownian(ctx, tracers_mu, tracers_D, (double)tracers_every * P.dt, tracers_substeps, (uint64_t)tracers_noise_seed));
+      if (tracers_absorb) CK(ekpnp_tracers_advance_absorbing(ctx, tracers_mu, tracers_D, (double)tracers_every * P.dt, tracers_substeps, (uint64_t)tracers_noise_seed, tracers_absorb));
+      else if (tracers_brownian) CK(ekpnp_tracers_advance_brownian(ctx, tracers_mu, tracers_D, (double)tracers_every * P.dt, tracers_substeps, (uint64_t)tracers_noise_seed));
       else CK(ekpnp_tracers_advance(ctx, tracers_mu, (double)tracers_every * P.dt, tracers_substeps));
       CK(ekpnp_tracers_record(ctx, (int64_t)(i + 1), t));
     }
@@ -765,6 +794,43 @@ int main(int argc, char* argv[]) {
     CK(ekpnp_tracers_ring_save(ctx, (out + "/tracers.dat").c_str()));
     CK(ekpnp_tracers_save(ctx, (out + "/tracers_final.bin").c_str(), t));
     if (tracks) CK(ekpnp_tracks_save(ctx, (out + "/tracks.dat").c_str()));
+    if (tracers_absorb) {
+      int64_t final_epoch = 0;
+      CK(ekpnp_tracers_epoch(ctx, &final_epoch));
+      if (final_epoch == 0) CK(ekpnp_tracers_advance_absorbing(ctx, 0.0, 0.0, 0.0, 1, 0, tracers_absorb));  // (no advance fell into the run: a step of no length makes the record)
+      CK(ekpnp_landings_save(ctx, (out + "/landings.bin").c_str()));
+      CK(ekpnp_tracers_epoch(ctx, &final_epoch));
+      const int64_t width = final_epoch / arrivals_bins + 1;  // cells 1 .. N cover the epochs 0 .. final
+      FILE* f = std::fopen((out + "/arrivals.dat").c_str(), "wb");
+      if (!f) { std::fprintf(stderr, "ekpnp_main: cannot open arrivals.dat\n"); ekpnp_destroy(ctx); return 1; }
+      std::fprintf(f, "# ekpnp arrivals nx %d ny %d nz %d n %lld epoch %lld e0 0 width %lld nbins %d: per wall (1 bottom, 2 top) the wall, none, and the nbins + 2 counts\n", nx, ny, nz,
+                   (long long)tracers_spec.n, (long long)final_epoch, (long long)width, arrivals_bins);
+      std::vector<int64_t> counts((size_t)arrivals_bins + 2);
+      for (int wall = 1; wall <= 2; ++wall) {
+        int64_t none = 0;
+        CK(ekpnp_landings_hist(ctx, wall, 0, width, arrivals_bins, counts.data(), &none));
+        std::fprintf(f, "%d %lld", wall, (long long)none);
+        for (int64_t v : counts) std::fprintf(f, " %lld", (long long)v);
+        std::fprintf(f, "\n");
+      }
+      std::fclose(f);
+      const int bx = deposit_cells[0], by = deposit_cells[1];
+      f = std::fopen((out + "/deposit.dat").c_str(), "wb");
+      if (!f) { std::fprintf(stderr, "ekpnp_main: cannot open deposit.dat\n"); ekpnp_destroy(ctx); return 1; }
+      std::fprintf(f, "# ekpnp deposit nx %d ny %d nz %d bx %d by %d n %lld epoch %lld: per wall (1 bottom, 2 top) a line `wall elsewhere`, then by rows of bx counts\n", nx, ny, nz, bx, by,
+                   (long long)tracers_spec.n, (long long)final_epoch);
+      counts.assign((size_t)bx * by, 0);
+      for (int wall = 1; wall <= 2; ++wall) {
+        int64_t elsewhere = 0;
+        CK(ekpnp_landings_map(ctx, wall, bx, by, 0, final_epoch, counts.data(), &elsewhere));
+        std::fprintf(f, "%d %lld\n", wall, (long long)elsewhere);
+        for (int r = 0; r < by; ++r) {
+          for (int k = 0; k < bx; ++k) std::fprintf(f, "%s%lld", k ? " " : "", (long long)counts[(size_t)r * bx + k]);
+          std::fprintf(f, "\n");
+        }
+      }
+      std::fclose(f);
+    }
     if (tracers_cells[0]) {
       const int bx = tracers_cells[0], by = tracers_cells[1], bz = tracers_cells[2];
       std::vector<int64_t> counts((size_t)bx * by * bz);

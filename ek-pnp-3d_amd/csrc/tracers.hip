@@ -11,13 +11,22 @@
 //                            (seed, the particle's ID, the cloud's epoch + the substep), three numbers in (-1, 1) times the kick
 //                            lengths the host formed, x and y folded, z reflected at the plates.  The id array is read only when
 //                            the cloud has one (a wave-uniform branch).  No LDS, no atomics, no scratch, no square root.
+//   k_tracers_advance_absorbing<MOB>   the Brownian thread per particle with plates that ABSORB (a mask names them; the other reflects):
+//                            a particle found on an absorbing plate stays there and its first arrival - the substep's number, the
+//                            wall, x, y and the image counts - goes into the landing record, six arrays indexed by the particle's ID,
+//                            so that exactly one thread ever touches an entry: no atomic.  A particle on such a plate at entry takes
+//                            no substep and draws nothing: a wavefront of them leaves after the position loads.
+//   k_landings_hist / k_landings_map<LDS>   the arrival-time histogram and the deposit map of a plate: the record read in id order,
+//                            the counting of k_tracers_cells (uint32 counters in LDS, equal cells of a wavefront merged, 64-bit
+//                            integer atomics to flush; a map beyond the LDS table counts with 64-bit global integer atomics)
 //   k_tracers_seed           a thread per particle: Philox numbers (RANDOM) or three tables the host made (GRID)
 //   k_tracers_cells<LDS>     counts per cell of a bx x by x bz partition: uint32 counters in LDS where the table fits 32 KB, flushed
 //                            with 64-bit integer atomics; 64-bit global integer atomics otherwise.  Counts are integers: exact.
 //   k_tracers_partials / k_tracers_finish   the 12 moments, the scheme of stats.hip over particles: runs of 4096 particles per
 //                            workgroup, thread t adds t, t + 256, ... ascending, reduce.h's trees, partial sums in ascending order
-// ekpnp_tracers_advance_host IS the definition of an advance, ekpnp_tracers_advance_brownian_host of a Brownian one (both call
-// tr_midpoint, the midpoint substep) and ekpnp_tracers_seed_host of a seed; the device leaves their bits by
+// ekpnp_tracers_advance_host IS the definition of an advance, ekpnp_tracers_advance_brownian_host of a Brownian one,
+// ekpnp_tracers_advance_absorbing_host of an absorbing one (all call tr_midpoint, the midpoint substep; the last two tr_kick) and
+// ekpnp_tracers_seed_host of a seed; the device leaves their bits by
 // construction: stencil, interpolation, fold and step are ONE __host__ __device__ function each, the step constants are formed
 // once on the host, and this object is built with -ffp-contract=off (csrc/Makefile, PINNED), so that neither side fuses a
 // multiply-add.  The passive and the mu != 0 kernel are two instantiations of one template; mu alone chooses, not the shape.
@@ -309,6 +318,85 @@ __host__ __device__ __forceinline__ void tr_advance_brownian(const TrFields& f, 
   }
 }
 
+// ---- absorbing plates (include/ekpnp.h: ekpnp_tracers_advance_absorbing_host IS the definition) ------------------------------
+// the landing record: six arrays [n] indexed by the particle's ID, one allocation in the order of the record's file
+struct TrLand {
+  int64_t* epoch;  // -1: not landed
+  double *x, *y;   // NaN: not landed
+  int32_t *wall, *wx, *wy;
+};
+
+// the absorbing plate a height lies on: 1 (bottom), 2 (top), 0: none
+__host__ __device__ __forceinline__ int tr_on_plate(int walls, double z, double top) {
+  if ((walls & 1) && z <= 0.0) return 1;
+  if ((walls & 2) && z >= top) return 2;
+  return 0;
+}
+
+// z after a kick: an absorbing plate keeps what went through it, the other reflects it (tr_reflect_z); then the hold; false: lost
+__host__ __device__ __forceinline__ bool tr_absorb_z(double& z, double top, int walls) {
+  if (!(z >= -1.7976931348623157e308 && z <= 1.7976931348623157e308)) return false;
+  if (z < 0.0) z = (walls & 1) ? 0.0 : 0.0 - z;
+  if (z > top) {
+    if (walls & 2) {
+      z = top;
+    } else {
+      const double d = z - top;
+      z = top - d;
+    }
+  }
+  return tr_fold_z(z, top);
+}
+
+// nsub absorbing substeps of the particle `id`, neither lost nor on an absorbing plate on entry: tr_advance_brownian until the
+// particle is found on an absorbing plate - after the midpoint substep (drift into the wall: no kick follows) or after the kick.
+// Returns that wall (0: none) and in `at` the substep; x, y, z and the image counts are then the landing place.
+template <bool MOB>
+__host__ __device__ __forceinline__ int tr_advance_absorbing(const TrFields& f, const TrStep& s, const TrNoise& q, int walls, int64_t id, double& x, double& y,
+                                                             double& z, int& wx, int& wy, int& at) {
+  const double px = (double)s.nx, py = (double)s.ny, top = (double)(s.nz - 1);
+  for (int it = 0; it < s.nsub; ++it) {
+    const int owx = wx, owy = wy;
+    bool ok = tr_midpoint<MOB>(f, s, px, py, top, x, y, z, wx, wy);
+    int wall = 0;
+    if (ok) {
+      wall = tr_on_plate(walls, z, top);
+      if (!wall) {
+        double r[3];
+        tr_kick(q.seed, id, q.epoch + (int64_t)it, r);
+        double t = q.kx * r[0];
+        x = x + t;
+        t = q.ky * r[1];
+        y = y + t;
+        t = q.kz * r[2];
+        z = z + t;
+        ok = tr_fold(x, px, wx);
+        ok = tr_fold(y, py, wy) && ok;
+        ok = tr_absorb_z(z, top, walls) && ok;
+        if (ok) wall = tr_on_plate(walls, z, top);
+      }
+    }
+    if (!ok) {  // lost: the image counts stay what they were before the substep, and no landing is recorded
+      x = y = z = NAN;
+      wx = owx;
+      wy = owy;
+      return 0;
+    }
+    if (wall) {
+      at = it;
+      return wall;
+    }
+  }
+  return 0;
+}
+
+// the cell of an arrival-time histogram (include/ekpnp.h: ekpnp_landings_bin), 64-bit integer arithmetic; e0 >= 0, width >= 1
+__host__ __device__ __forceinline__ int tr_land_bin(int64_t e0, int64_t width, int nbins, int64_t epoch) {
+  if (epoch < e0) return 0;
+  const int64_t d = (epoch - e0) / width;
+  return d >= (int64_t)nbins ? nbins + 1 : 1 + (int)d;
+}
+
 // the cell of a position (include/ekpnp.h: ekpnp_tracers_cell), -1 for a lost particle
 __host__ __device__ __forceinline__ int tr_cell(int nx, int ny, int nz, int bx, int by, int bz, double x, double y, double z) {
   if (tr_lost(x, y, z)) return -1;
@@ -363,6 +451,45 @@ __global__ void __launch_bounds__(TR_THREADS) k_tracers_advance_brownian(TrField
   c.z[i] = z;
   c.wx[i] = wx;
   c.wy[i] = wy;
+}
+
+// A particle on an absorbing plate at entry (stuck) reads its record entry and, if that is empty, its image counts; everybody else
+// is a Brownian thread that may end early.  The record is indexed by id and the ids are a permutation: one thread per entry.
+template <bool MOB>
+__global__ void __launch_bounds__(TR_THREADS) k_tracers_advance_absorbing(TrFields f, TrStep s, TrNoise q, int walls, TrCloud c, const int32_t* __restrict__ ids, TrLand L) {
+  const long long i = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
+  if (i >= c.n) return;
+  double x = c.x[i], y = c.y[i], z = c.z[i];
+  if (tr_lost(x, y, z)) return;  // nothing is read, nothing is written
+  int wall = tr_on_plate(walls, z, (double)(s.nz - 1));
+  const int64_t id = ids ? (int64_t)ids[i] : (int64_t)i;
+  if (id < 0 || id >= c.n) return;  // (a permutation of ids never comes here)
+  int64_t when = q.epoch;
+  int wx, wy;
+  if (wall) {  // stuck: no substep, no draw, no store to the cloud
+    if (L.epoch[id] >= 0) return;
+    wx = c.wx[i];
+    wy = c.wy[i];
+  } else {
+    wx = c.wx[i];
+    wy = c.wy[i];
+    int at = 0;
+    wall = tr_advance_absorbing<MOB>(f, s, q, walls, id, x, y, z, wx, wy, at);
+    c.x[i] = x;
+    c.y[i] = y;
+    c.z[i] = z;
+    c.wx[i] = wx;
+    c.wy[i] = wy;
+    if (!wall) return;
+    when = q.epoch + (int64_t)at + 1;
+    if (L.epoch[id] >= 0) return;  // a FIRST-passage record
+  }
+  L.epoch[id] = when;
+  L.wall[id] = wall;
+  L.x[id] = x;
+  L.y[id] = y;
+  L.wx[id] = wx;
+  L.wy[id] = wy;
 }
 
 // out[v][i] = value v at the particle in slot i: the stores of a wavefront are coalesced
@@ -510,6 +637,90 @@ __global__ void __launch_bounds__(TR_THREADS) k_tracers_cells(const double* __re
       const unsigned v = tr_cnt[i];
       if (v) atomicAdd(&total[i], (unsigned long long)v);
     }
+  }
+}
+
+// total[cell of ekpnp_landings_bin] += the workgroup's landings on a wall of the mask; total[nbins + 2] counts everybody else.
+// The table has at most 4099 counters: it always fits the LDS.  12 B per particle, in id order.
+__global__ void __launch_bounds__(TR_THREADS) k_landings_hist(const int64_t* __restrict__ epoch, const int32_t* __restrict__ wall, long long n, int walls, int64_t e0,
+                                                              int64_t width, int nbins, unsigned long long* __restrict__ total) {
+  extern __shared__ unsigned tr_cnt[];
+  const int cells = nbins + 2;
+  for (int i = threadIdx.x; i <= cells; i += TR_THREADS) tr_cnt[i] = 0u;
+  __syncthreads();
+  const long long first = (long long)blockIdx.x * (TR_THREADS * TR_CELL_PER_THREAD) + threadIdx.x;
+  for (int k0 = 0; k0 < TR_CELL_PER_THREAD; k0 += 8) {
+    int64_t e[8];
+    int32_t w[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const long long i = first + (long long)(k0 + k) * TR_THREADS;
+      const bool in = i < n;
+      e[k] = in ? epoch[i] : -1;
+      w[k] = in ? wall[i] : 0;
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const long long i = first + (long long)(k0 + k) * TR_THREADS;
+      const bool counted = (w[k] == 1 || w[k] == 2) && (walls & w[k]) && e[k] >= 0;
+      int cell = counted ? tr_land_bin(e0, width, nbins, e[k]) : cells;
+      if (i >= n) cell = -1;
+      tr_count_add(tr_cnt, cell);
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i <= cells; i += TR_THREADS) {
+    const unsigned v = tr_cnt[i];
+    if (v) atomicAdd(&total[i], (unsigned long long)v);
+  }
+}
+
+// total[cell of ekpnp_tracers_cell(bx, by, 1)] += the workgroup's landings on `wall` with e_lo <= epoch <= e_hi; total[cells] counts
+// everybody else.  28 B per particle, in id order.
+template <bool LDS>
+__global__ void __launch_bounds__(TR_THREADS) k_landings_map(TrLand L, long long n, int wall, int64_t e_lo, int64_t e_hi, int nx, int ny, int nz, int bx, int by,
+                                                             int cells, unsigned long long* __restrict__ total) {
+  extern __shared__ unsigned tr_cnt[];
+  if constexpr (LDS) {
+    for (int i = threadIdx.x; i <= cells; i += TR_THREADS) tr_cnt[i] = 0u;
+    __syncthreads();
+  }
+  const long long first = (long long)blockIdx.x * (TR_THREADS * TR_CELL_PER_THREAD) + threadIdx.x;
+  unsigned other = 0u;  // (the global table only) this thread's particles that count elsewhere
+  for (int k0 = 0; k0 < TR_CELL_PER_THREAD; k0 += 8) {
+    int64_t e[8];
+    int32_t w[8];
+    double px[8], py[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const long long i = first + (long long)(k0 + k) * TR_THREADS;
+      const bool in = i < n;
+      e[k] = in ? L.epoch[i] : -1;
+      w[k] = in ? L.wall[i] : 0;
+      px[k] = in ? L.x[i] : 0.0;
+      py[k] = in ? L.y[i] : 0.0;
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const long long i = first + (long long)(k0 + k) * TR_THREADS;
+      int cell = (w[k] == wall && e[k] >= e_lo && e[k] <= e_hi) ? tr_cell(nx, ny, nz, bx, by, 1, px[k], py[k], 0.0) : cells;
+      if (cell < 0 || cell > cells) cell = cells;  // (a landing place is never NaN)
+      if (i >= n) cell = -1;
+      if constexpr (LDS) tr_count_add(tr_cnt, cell);
+      else if (cell == cells) ++other;
+      else if (cell >= 0) atomicAdd(&total[cell], 1ull);
+    }
+  }
+  if constexpr (LDS) {
+    __syncthreads();
+    for (int i = threadIdx.x; i <= cells; i += TR_THREADS) {
+      const unsigned v = tr_cnt[i];
+      if (v) atomicAdd(&total[i], (unsigned long long)v);
+    }
+  } else {  // "elsewhere" is ONE counter and may be most of the cloud: summed over the wavefront first, one atomic per wave
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) other += __shfl_down(other, o);
+    if ((threadIdx.x & 63) == 0 && other) atomicAdd(&total[cells], (unsigned long long)other);
   }
 }
 
@@ -809,6 +1020,17 @@ struct TracerState {
   Ring tracks;                // rows of [ntags][5 + nvalues] doubles behind a header of four int32 tables [ntags] (TrTags)
   ekpnp_tracks_spec tspec{};  // the spec of the last ekpnp_tracks_arm and the size of the cloud it tagged (for the file)
   long long tracks_n = 0;
+  // the landing record of the absorbing advance, made and cleared by the first ekpnp_tracers_advance_absorbing (or a load of its
+  // file), dropped with the cloud it belongs to and by seed, set and load: 36 B per particle in the order of its file
+  void* land = nullptr;
+  size_t land_bytes = 0;
+  TrLand land_dev() const {
+    const size_t m = (size_t)n;
+    int64_t* e = (int64_t*)land;
+    double* d = (double*)(e + m);
+    int32_t* w = (int32_t*)(d + 2 * m);
+    return TrLand{e, d, d + m, w, w + m, w + 2 * m};
+  }
   TrCloud dev() const {
     double* d = (double*)cloud;
     const size_t m = (size_t)n;
@@ -824,6 +1046,18 @@ static void tracers_sort_release(Ctx& c, TracerState& t) {
   if (t.ids) { (void)hipFree(t.ids); c.bytes -= t.ids_bytes; t.ids = nullptr; t.ids_bytes = 0; }
   t.has_ids = false;
   if (t.samp) { (void)hipFree(t.samp); c.bytes -= t.samp_bytes; t.samp = nullptr; t.samp_bytes = 0; }  // and so does the sample scratch
+  if (t.land) { (void)hipFree(t.land); c.bytes -= t.land_bytes; t.land = nullptr; t.land_bytes = 0; }  // and the landing record
+}
+
+// a new cloud has no landings (seed, set, load): the stream is waited for, an absorbing advance may still write the record
+static int tracers_land_drop(Ctx& c, TracerState& t) {
+  if (!t.land) return EKPNP_OK;
+  HIPCHK(c, hipStreamSynchronize(c.stream));
+  (void)hipFree(t.land);
+  c.bytes -= t.land_bytes;
+  t.land = nullptr;
+  t.land_bytes = 0;
+  return EKPNP_OK;
 }
 
 void tracers_release(Ctx& c) {
@@ -1111,6 +1345,77 @@ extern "C" int ekpnp_tracers_advance_brownian_host(const ekpnp_params* p, const 
   return EKPNP_OK;
 }
 
+static int tracers_check_walls(int walls, std::string& err) {
+  if (walls < 1 || walls > 3) { err = "tracers: walls = " + std::to_string(walls) + " outside 1 .. 3 (1: the bottom plate absorbs, 2: the top plate, 3: both)"; return EKPNP_ERR_INVALID; }
+  return EKPNP_OK;
+}
+
+extern "C" int ekpnp_tracers_advance_absorbing_host(const ekpnp_params* p, const double* ux, const double* uy, const double* uz, const double* ex, const double* ey,
+                                                    const double* ez, int64_t n, const int32_t* ids, double* x, double* y, double* z, int32_t* wx, int32_t* wy,
+                                                    double mu, double D, double h, int nsub, uint64_t seed, int64_t epoch, int walls, int64_t* land_epoch,
+                                                    int32_t* land_wall, double* land_x, double* land_y, int32_t* land_wx, int32_t* land_wy) {
+  std::string err;
+  int rc = EKPNP_ERR_INVALID;
+  if (!p) err = "tracers: NULL parameters";
+  else if ((rc = tracers_check_lattice(*p, err)) == EKPNP_OK && (rc = tracers_check_advance(mu, h, nsub, err)) == EKPNP_OK && (rc = tracers_check_brownian(D, h, err)) == EKPNP_OK &&
+           (rc = tracers_check_walls(walls, err)) == EKPNP_OK) {
+    if (n < 0 || n > EKPNP_TRACERS_MAX_N) { err = "tracers: n = " + std::to_string((long long)n) + " outside 0 .. " + std::to_string((long long)EKPNP_TRACERS_MAX_N); rc = EKPNP_ERR_INVALID; }
+    else if (epoch < 0 || epoch > INT64_MAX - nsub) { err = "tracers: epoch = " + std::to_string((long long)epoch) + " (must be >= 0, and epoch + nsub must fit 63 bits)"; rc = EKPNP_ERR_INVALID; }
+    else if (!ux || !uy || !uz || !x || !y || !z || !wx || !wy || (mu != 0.0 && (!ex || !ey || !ez)) || !land_epoch || !land_wall || !land_x || !land_y || !land_wx || !land_wy) {
+      err = "tracers: NULL pointer";
+      rc = EKPNP_ERR_INVALID;
+    }
+    for (int64_t i = 0; i < n && rc == EKPNP_OK; ++i) {
+      if (ids && (ids[i] < 0 || (int64_t)ids[i] >= n)) { err = "tracers: slot " + std::to_string((long long)i) + " holds id " + std::to_string(ids[i]) + ", outside 0 .. " + std::to_string((long long)n - 1); rc = EKPNP_ERR_INVALID; }
+      else if (land_wall[i] < 0 || land_wall[i] > 2) { err = "tracers: landing record of id " + std::to_string((long long)i) + ": wall = " + std::to_string(land_wall[i]) + " outside 0 .. 2"; rc = EKPNP_ERR_INVALID; }
+      else if (land_epoch[i] < 0 && land_wall[i] != 0) { err = "tracers: landing record of id " + std::to_string((long long)i) + ": epoch = " + std::to_string((long long)land_epoch[i]) + " with wall = " + std::to_string(land_wall[i]) + " (no landing has wall 0)"; rc = EKPNP_ERR_INVALID; }
+    }
+  }
+  if (rc) { set_create_error(err); return rc; }
+  const TrFields f{{ux, uy, uz}, {ex, ey, ez}};
+  const TrStep s = tr_step_of(*p, mu, h, nsub);
+  const TrNoise q = tr_noise_of(*p, D, h, seed, epoch);
+  const double top = (double)(p->nz - 1);
+  for (int64_t i = 0; i < n; ++i) {
+    if (tr_lost(x[i], y[i], z[i])) continue;
+    const int64_t id = ids ? (int64_t)ids[i] : i;
+    int wall = tr_on_plate(walls, z[i], top);
+    int64_t when = epoch;
+    int a = wx[i], b = wy[i];
+    if (!wall) {  // (a stuck particle: no substep, no draw, no store to the cloud)
+      int at = 0;
+      if (mu != 0.0) wall = tr_advance_absorbing<true>(f, s, q, walls, id, x[i], y[i], z[i], a, b, at);
+      else wall = tr_advance_absorbing<false>(f, s, q, walls, id, x[i], y[i], z[i], a, b, at);
+      wx[i] = a;
+      wy[i] = b;
+      when = epoch + (int64_t)at + 1;
+    }
+    if (wall && land_epoch[id] < 0) {  // a FIRST-passage record
+      land_epoch[id] = when;
+      land_wall[id] = wall;
+      land_x[id] = x[i];
+      land_y[id] = y[i];
+      land_wx[id] = a;
+      land_wy[id] = b;
+    }
+  }
+  return EKPNP_OK;
+}
+
+static int landings_check_hist(int walls, int64_t e0, int64_t width, int nbins, std::string& err) {
+  if (int rc = tracers_check_walls(walls, err)) return rc;
+  if (e0 < 0) { err = "tracers: e0 = " + std::to_string((long long)e0) + " (must be >= 0)"; return EKPNP_ERR_INVALID; }
+  if (width < 1) { err = "tracers: width = " + std::to_string((long long)width) + " (must be >= 1)"; return EKPNP_ERR_INVALID; }
+  if (nbins < 1 || nbins > 4096) { err = "tracers: nbins = " + std::to_string(nbins) + " outside 1 .. 4096"; return EKPNP_ERR_INVALID; }
+  return EKPNP_OK;
+}
+
+extern "C" int ekpnp_landings_bin(int64_t e0, int64_t width, int nbins, int64_t epoch) {
+  std::string err;
+  if (landings_check_hist(3, e0, width, nbins, err)) { set_create_error(err); return -1; }
+  return tr_land_bin(e0, width, nbins, epoch);
+}
+
 extern "C" int ekpnp_tracers_cell(const ekpnp_params* p, int bx, int by, int bz, double x, double y, double z) {
   std::string err;
   if (!p) { set_create_error("tracers: NULL parameters"); return -2; }
@@ -1227,6 +1532,7 @@ static inline unsigned tr_blocks(long long n, int per) { return (unsigned)((n + 
 // upload a whole cloud from host arrays (synchronous)
 static int tracers_upload(Ctx& c, long long n, const double* const pos[6], const int32_t* wx, const int32_t* wy) {
   if (int rc = tracers_alloc(c, n)) return rc;
+  if (int rc = tracers_land_drop(c, *c.tracers)) return rc;
   c.tracers->has_ids = false;  // a new cloud: slot s holds particle s (a load that carries ids puts them back)
   c.tracers->epoch = 0;        // and no Brownian substep was taken (a load puts its file's epoch back)
   c.tracers->tracks.armed = false;  // and the tags of an armed track ring named particles of the old one
@@ -1248,6 +1554,7 @@ extern "C" int ekpnp_tracers_seed(ekpnp_ctx* ctx, const ekpnp_tracers_spec* spec
   if (int rc = tracers_check_spec(c.p, spec, c.err)) return rc;
   if (int rc = tracers_alloc(c, (long long)spec->n)) return rc;
   TracerState& t = *c.tracers;
+  if (int rc = tracers_land_drop(c, t)) return rc;
   t.has_ids = false;
   t.epoch = 0;
   t.tracks.armed = false;  // the tags named particles of the cloud that is replaced here (the rows stay readable)
@@ -1376,6 +1683,49 @@ extern "C" int ekpnp_tracers_advance_brownian(ekpnp_ctx* ctx, double mu, double 
   note_launch(c, "k_tracers_advance_brownian");
   if (take_launch_error(c) != hipSuccess) return EKPNP_ERR_HIP;
   t->epoch += nsub;  // every Brownian advance, whether or not particles were lost
+  return EKPNP_OK;
+}
+
+// the record cleared (enqueues only): epoch -1 and x, y NaN are all bits set (24 B per particle), wall and the image counts 0
+static int tracers_land_clear(Ctx& c, TracerState& t) {
+  const size_t n = (size_t)t.n;
+  HIPCHK(c, hipMemsetAsync(t.land, 0xFF, 24 * n, c.stream));
+  HIPCHK(c, hipMemsetAsync((char*)t.land + 24 * n, 0, 12 * n, c.stream));
+  return EKPNP_OK;
+}
+
+// the record of the cloud, made (and cleared, if asked) on first use
+static int tracers_land_alloc(Ctx& c, TracerState& t, bool clear) {
+  if (t.land) return EKPNP_OK;
+  const size_t bytes = (size_t)t.n * 36;
+  HIPCHK(c, hipMalloc(&t.land, bytes));
+  t.land_bytes = bytes;
+  c.bytes += bytes;
+  return clear ? tracers_land_clear(c, t) : EKPNP_OK;
+}
+
+extern "C" int ekpnp_tracers_advance_absorbing(ekpnp_ctx* ctx, double mu, double D, double h, int nsub, uint64_t seed, int walls) {
+  NEEDSINGLE(ctx);
+  if (int rc = tracers_check_advance(mu, h, nsub, c.err)) return rc;
+  if (int rc = tracers_check_brownian(D, h, c.err)) return rc;
+  if (int rc = tracers_check_walls(walls, c.err)) return rc;
+  TracerState* t = cloud_of(c);
+  if (!t) return fail(c, "tracers: no cloud (seed, set or load one first)");
+  if (t->epoch > INT64_MAX - nsub) { c.err = "tracers: epoch = " + std::to_string((long long)t->epoch) + " (epoch + nsub must fit 63 bits)"; return EKPNP_ERR_INVALID; }
+  const bool mob = mu != 0.0;
+  if (mob)
+    if (int rc = ensure_efield(c)) return rc;  // as ekpnp_tracers_advance (mu == 0: lazy E is left alone)
+  if (int rc = tracers_land_alloc(c, *t, true)) return rc;
+  const TrFields f{{c.fld[EKPNP_UX], c.fld[EKPNP_UY], c.fld[EKPNP_UZ]}, {c.fld[EKPNP_EX], c.fld[EKPNP_EY], c.fld[EKPNP_EZ]}};
+  const TrStep s = tr_step_of(c.p, mu, h, nsub);
+  const TrNoise q = tr_noise_of(c.p, D, h, seed, t->epoch);
+  const int32_t* ids = t->has_ids ? t->ids : nullptr;
+  const dim3 grid(tr_blocks(t->n, TR_THREADS)), block(TR_THREADS);
+  if (mob) hipLaunchKernelGGL((k_tracers_advance_absorbing<true>), grid, block, 0, c.stream, f, s, q, walls, t->dev(), ids, t->land_dev());
+  else hipLaunchKernelGGL((k_tracers_advance_absorbing<false>), grid, block, 0, c.stream, f, s, q, walls, t->dev(), ids, t->land_dev());
+  note_launch(c, "k_tracers_advance_absorbing");
+  if (take_launch_error(c) != hipSuccess) return EKPNP_ERR_HIP;
+  t->epoch += nsub;  // as a Brownian advance
   return EKPNP_OK;
 }
 
@@ -1582,18 +1932,23 @@ extern "C" int ekpnp_tracers_load(ekpnp_ctx* ctx, const char* path, double* time
 
 // ---- cell counts and moments -------------------------------------------------------------------------------------------------
 
+// the table of the cell counts, which serves the two reductions of the landing record as well (made by whichever comes first)
+static int tracers_cells_alloc(Ctx& c, TracerState& t) {
+  if (t.cells) return EKPNP_OK;
+  const size_t bytes = ((size_t)EKPNP_TRACERS_MAX_CELLS + 1) * sizeof(unsigned long long);
+  HIPCHK(c, hipMalloc((void**)&t.cells, bytes));
+  t.cells_bytes = bytes;
+  c.bytes += bytes;
+  return EKPNP_OK;
+}
+
 extern "C" int ekpnp_tracers_cell_counts(ekpnp_ctx* ctx, int bx, int by, int bz, int64_t* counts, int64_t* lost) {
   NEEDSINGLE(ctx);
   if (!counts || !lost) return fail(c, "NULL pointer");
   if (int rc = tracers_check_cells(c.p, bx, by, bz, c.err)) return rc;
   TracerState* t = cloud_of(c);
   if (!t) return fail(c, "tracers: no cloud (seed, set or load one first)");
-  if (!t->cells) {
-    const size_t bytes = ((size_t)EKPNP_TRACERS_MAX_CELLS + 1) * sizeof(unsigned long long);
-    HIPCHK(c, hipMalloc((void**)&t->cells, bytes));
-    t->cells_bytes = bytes;
-    c.bytes += bytes;
-  }
+  if (int rc = tracers_cells_alloc(c, *t)) return rc;
   const int cells = bx * by * bz;
   HIPCHK(c, hipMemsetAsync(t->cells, 0, ((size_t)cells + 1) * sizeof(unsigned long long), c.stream));
   const TrCloud d = t->dev();
@@ -1609,6 +1964,161 @@ extern "C" int ekpnp_tracers_cell_counts(ekpnp_ctx* ctx, int bx, int by, int bz,
   HIPCHK(c, hipStreamSynchronize(c.stream));
   for (int k = 0; k < cells; ++k) counts[k] = h[(size_t)k];
   *lost = h[(size_t)cells];
+  return EKPNP_OK;
+}
+
+// ---- the landing record: reset, get, the two reductions, the record's file ---------------------------------------------------
+
+static inline TracerState* record_of(Ctx& c) { return c.tracers && c.tracers->cloud && c.tracers->land ? c.tracers : nullptr; }
+constexpr const char* kNoRecordMsg = "tracers: no landing record (ekpnp_tracers_advance_absorbing or ekpnp_landings_load makes one)";
+
+extern "C" int ekpnp_landings_reset(ekpnp_ctx* ctx) {
+  NEEDSINGLE(ctx);
+  if (!cloud_of(c)) return fail(c, "tracers: no cloud (seed, set or load one first)");
+  TracerState* t = record_of(c);
+  return t ? tracers_land_clear(c, *t) : EKPNP_OK;  // no record: nothing to clear, and nothing is allocated
+}
+
+extern "C" int ekpnp_landings_get(ekpnp_ctx* ctx, int64_t* epoch, int32_t* wall, double* x, double* y, int32_t* wx, int32_t* wy) {
+  NEEDSINGLE(ctx);
+  if (!cloud_of(c)) return fail(c, "tracers: no cloud (seed, set or load one first)");
+  TracerState* t = record_of(c);
+  if (!t) return fail(c, kNoRecordMsg);
+  const TrLand d = t->land_dev();
+  const size_t n = (size_t)t->n;
+  if (epoch) HIPCHK(c, hipMemcpyAsync(epoch, d.epoch, n * sizeof(int64_t), hipMemcpyDeviceToHost, c.stream));
+  if (wall) HIPCHK(c, hipMemcpyAsync(wall, d.wall, n * sizeof(int32_t), hipMemcpyDeviceToHost, c.stream));
+  if (x) HIPCHK(c, hipMemcpyAsync(x, d.x, n * sizeof(double), hipMemcpyDeviceToHost, c.stream));
+  if (y) HIPCHK(c, hipMemcpyAsync(y, d.y, n * sizeof(double), hipMemcpyDeviceToHost, c.stream));
+  if (wx) HIPCHK(c, hipMemcpyAsync(wx, d.wx, n * sizeof(int32_t), hipMemcpyDeviceToHost, c.stream));
+  if (wy) HIPCHK(c, hipMemcpyAsync(wy, d.wy, n * sizeof(int32_t), hipMemcpyDeviceToHost, c.stream));
+  HIPCHK(c, hipStreamSynchronize(c.stream));
+  return EKPNP_OK;
+}
+
+extern "C" int ekpnp_landings_hist(ekpnp_ctx* ctx, int walls, int64_t e0, int64_t width, int nbins, int64_t* counts, int64_t* none) {
+  NEEDSINGLE(ctx);
+  if (!counts || !none) return fail(c, "NULL pointer");
+  if (int rc = landings_check_hist(walls, e0, width, nbins, c.err)) return rc;
+  if (!cloud_of(c)) return fail(c, "tracers: no cloud (seed, set or load one first)");
+  TracerState* t = record_of(c);
+  if (!t) return fail(c, kNoRecordMsg);
+  if (int rc = tracers_cells_alloc(c, *t)) return rc;
+  const size_t cells = (size_t)nbins + 2;
+  HIPCHK(c, hipMemsetAsync(t->cells, 0, (cells + 1) * sizeof(unsigned long long), c.stream));
+  const TrLand d = t->land_dev();
+  hipLaunchKernelGGL(k_landings_hist, dim3(tr_blocks(t->n, TR_THREADS * TR_CELL_PER_THREAD)), dim3(TR_THREADS), (cells + 1) * sizeof(unsigned), c.stream, d.epoch, d.wall, t->n,
+                     walls, e0, width, nbins, t->cells);
+  note_launch(c, "k_landings_hist");
+  if (take_launch_error(c) != hipSuccess) return EKPNP_ERR_HIP;
+  std::vector<int64_t> h(cells + 1);
+  HIPCHK(c, hipMemcpyAsync(h.data(), t->cells, h.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c.stream));
+  HIPCHK(c, hipStreamSynchronize(c.stream));
+  for (size_t k = 0; k < cells; ++k) counts[k] = h[k];
+  *none = h[cells];
+  return EKPNP_OK;
+}
+
+extern "C" int ekpnp_landings_map(ekpnp_ctx* ctx, int wall, int bx, int by, int64_t e_lo, int64_t e_hi, int64_t* counts, int64_t* elsewhere) {
+  NEEDSINGLE(ctx);
+  if (!counts || !elsewhere) return fail(c, "NULL pointer");
+  if (wall < 1 || wall > 2) { c.err = "tracers: wall = " + std::to_string(wall) + " (must be 1, the bottom plate, or 2, the top plate)"; return EKPNP_ERR_INVALID; }
+  if (int rc = tracers_check_cells(c.p, bx, by, 1, c.err)) return rc;
+  if (!cloud_of(c)) return fail(c, "tracers: no cloud (seed, set or load one first)");
+  TracerState* t = record_of(c);
+  if (!t) return fail(c, kNoRecordMsg);
+  if (int rc = tracers_cells_alloc(c, *t)) return rc;
+  const int cells = bx * by;
+  HIPCHK(c, hipMemsetAsync(t->cells, 0, ((size_t)cells + 1) * sizeof(unsigned long long), c.stream));
+  const dim3 grid(tr_blocks(t->n, TR_THREADS * TR_CELL_PER_THREAD)), block(TR_THREADS);
+  if (cells + 1 <= TR_LDS_CELLS)
+    hipLaunchKernelGGL((k_landings_map<true>), grid, block, ((size_t)cells + 1) * sizeof(unsigned), c.stream, t->land_dev(), t->n, wall, e_lo, e_hi, c.p.nx, c.p.ny, c.p.nz, bx, by, cells, t->cells);
+  else
+    hipLaunchKernelGGL((k_landings_map<false>), grid, block, 0, c.stream, t->land_dev(), t->n, wall, e_lo, e_hi, c.p.nx, c.p.ny, c.p.nz, bx, by, cells, t->cells);
+  note_launch(c, "k_landings_map");
+  if (take_launch_error(c) != hipSuccess) return EKPNP_ERR_HIP;
+  std::vector<int64_t> h((size_t)cells + 1);
+  HIPCHK(c, hipMemcpyAsync(h.data(), t->cells, h.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c.stream));
+  HIPCHK(c, hipStreamSynchronize(c.stream));
+  for (int k = 0; k < cells; ++k) counts[k] = h[(size_t)k];
+  *elsewhere = h[(size_t)cells];
+  return EKPNP_OK;
+}
+
+namespace {
+struct LandHeader {
+  char magic[8];
+  int32_t nx, ny, nz, reserved;
+  int64_t n, landed, epoch;
+};
+static_assert(sizeof(LandHeader) == 48, "landing file header layout");
+constexpr char kLandMagic[9] = "EKPNPLD1";
+}  // namespace
+
+extern "C" int ekpnp_landings_save(ekpnp_ctx* ctx, const char* path) {
+  NEEDSINGLE(ctx);
+  if (!path) return fail(c, "NULL path");
+  if (!cloud_of(c)) return fail(c, "tracers: no cloud (seed, set or load one first)");
+  TracerState* t = record_of(c);
+  if (!t) return fail(c, kNoRecordMsg);
+  const size_t n = (size_t)t->n;
+  HIPCHK(c, hipStreamSynchronize(c.stream));
+  std::vector<int64_t> buf((36 * n + 7) / 8);  // the record lies in memory as in the file
+  HIPCHK(c, hipMemcpy(buf.data(), t->land, 36 * n, hipMemcpyDeviceToHost));
+  const int32_t* wall = (const int32_t*)((const char*)buf.data() + 24 * n);
+  LandHeader h{};
+  std::memcpy(h.magic, kLandMagic, 8);
+  h.nx = c.p.nx; h.ny = c.p.ny; h.nz = c.p.nz;
+  h.n = (int64_t)n;
+  h.epoch = t->epoch;
+  for (size_t i = 0; i < n; ++i) h.landed += wall[i] != 0;
+  FILE* f = std::fopen(path, "wb");
+  if (!f) return fail(c, "cannot open landing file");
+  const bool ok = std::fwrite(&h, sizeof h, 1, f) == 1 && std::fwrite(buf.data(), 1, 36 * n, f) == 36 * n;
+  if (std::fclose(f) != 0 || !ok) return fail(c, "write error on landing file");
+  return EKPNP_OK;
+}
+
+extern "C" int ekpnp_landings_load(ekpnp_ctx* ctx, const char* path) {
+  NEEDSINGLE(ctx);
+  if (!path) return fail(c, "NULL path");
+  TracerState* t = cloud_of(c);
+  if (!t) return fail(c, "tracers: no cloud (seed, set or load one first)");
+  FILE* f = std::fopen(path, "rb");
+  if (!f) return fail(c, "cannot open landing file");
+  LandHeader h{};
+  if (std::fread(&h, sizeof h, 1, f) != 1 || std::memcmp(h.magic, kLandMagic, 8) != 0) { std::fclose(f); return fail(c, "tracers: not a landing file (EKPNPLD1)"); }
+  if (h.nx != c.p.nx || h.ny != c.p.ny || h.nz != c.p.nz) {
+    std::fclose(f);
+    c.err = "tracers: the file holds a landing record of lattice " + std::to_string(h.nx) + " x " + std::to_string(h.ny) + " x " + std::to_string(h.nz) + ", not of " +
+            std::to_string(c.p.nx) + " x " + std::to_string(c.p.ny) + " x " + std::to_string(c.p.nz);
+    return EKPNP_ERR_INVALID;
+  }
+  if (h.n != (int64_t)t->n) { std::fclose(f); c.err = "tracers: n = " + std::to_string((long long)h.n) + " in the landing file, the cloud has " + std::to_string(t->n) + " particles"; return EKPNP_ERR_INVALID; }
+  if (h.reserved != 0) { std::fclose(f); c.err = "tracers: reserved = " + std::to_string(h.reserved) + " in the landing file (must be 0)"; return EKPNP_ERR_INVALID; }
+  if (h.epoch < 0) { std::fclose(f); c.err = "tracers: epoch = " + std::to_string((long long)h.epoch) + " in the landing file (must be >= 0)"; return EKPNP_ERR_INVALID; }
+  const size_t n = (size_t)h.n;
+  std::vector<int64_t> buf((36 * n + 7) / 8);
+  const bool ok = std::fread(buf.data(), 1, 36 * n, f) == 36 * n;
+  std::fclose(f);
+  if (!ok) { c.err = "tracers: the landing file is shorter than its " + std::to_string((long long)h.n) + " entries"; return EKPNP_ERR_INVALID; }
+  const int64_t* epoch = buf.data();
+  const int32_t* wall = (const int32_t*)((const char*)buf.data() + 24 * n);
+  int64_t landed = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const std::string w = "tracers: landing file, id " + std::to_string(i) + ": ";
+    if (wall[i] < 0 || wall[i] > 2) { c.err = w + "wall = " + std::to_string(wall[i]) + " outside 0 .. 2"; return EKPNP_ERR_INVALID; }
+    if (epoch[i] < -1 || (epoch[i] == -1) != (wall[i] == 0)) {
+      c.err = w + "epoch = " + std::to_string((long long)epoch[i]) + " with wall = " + std::to_string(wall[i]) + " (epoch -1 and wall 0 go together: no landing)";
+      return EKPNP_ERR_INVALID;
+    }
+    if (epoch[i] > h.epoch) { c.err = w + "epoch = " + std::to_string((long long)epoch[i]) + " above the file's epoch " + std::to_string((long long)h.epoch); return EKPNP_ERR_INVALID; }
+    landed += wall[i] != 0;
+  }
+  if (landed != h.landed) { c.err = "tracers: landed = " + std::to_string((long long)h.landed) + " in the landing file, which holds " + std::to_string((long long)landed) + " entries with a wall"; return EKPNP_ERR_INVALID; }
+  HIPCHK(c, hipStreamSynchronize(c.stream));  // an absorbing advance may still write the record
+  if (int rc = tracers_land_alloc(c, *t, false)) return rc;
+  HIPCHK(c, hipMemcpy(t->land, buf.data(), 36 * n, hipMemcpyHostToDevice));
   return EKPNP_OK;
 }
 

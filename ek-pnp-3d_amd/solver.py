@@ -498,6 +498,67 @@ def tracers_advance_brownian_host(p: "Params", u, x, y, z, wx=None, wy=None, E=N
     return x, y, z, wx, wy
 
 
+ABSORB_WALLS = {"bottom": 1, "top": 2, "both": 3}
+
+
+def _absorb_walls(absorb) -> int:
+    """the mask of ekpnp_tracers_advance_absorbing: "bottom" (1), "top" (2), "both" (3), or the number itself"""
+    if isinstance(absorb, str):
+        if absorb not in ABSORB_WALLS:
+            raise ValueError(f"absorb = {absorb!r}: expected one of {sorted(ABSORB_WALLS)}")
+        return ABSORB_WALLS[absorb]
+    return int(absorb)
+
+
+def landings_empty(n: int):
+    """(land_epoch, land_wall, land_x, land_y, land_wx, land_wy) of n particles that never landed"""
+    return (np.full(n, -1, dtype=np.int64), np.zeros(n, dtype=np.int32), np.full(n, np.nan), np.full(n, np.nan), np.zeros(n, dtype=np.int32),
+            np.zeros(n, dtype=np.int32))
+
+
+def tracers_advance_absorbing_host(p: "Params", u, x, y, z, wx=None, wy=None, E=None, mu: float = 0.0, D: float = 0.0, h: float = 0.0, nsub: int = 1,
+                                   seed: int = 0, epoch: int = 0, ids=None, walls=3, record=None):
+    """nsub absorbing substeps of h seconds - Brownian substeps whose plates in `walls` (1: bottom, 2: top, 3: both, or their names)
+    keep what reaches them and write its first arrival into the landing record, six arrays indexed by the particle's id (record:
+    an earlier record to go on from, never overwritten; None: nobody has landed): THE definition of an absorbing advance
+    (ekpnp_tracers_advance_absorbing_host, host only).  Returns new (x, y, z, wx, wy, land_epoch, land_wall, land_x, land_y,
+    land_wx, land_wy)."""
+    L = load_library()
+    shape = (p.nz, p.ny, p.nx)
+    u = [np.ascontiguousarray(a, dtype=np.float64).reshape(shape) for a in u]
+    e = [None] * 3 if E is None else [np.ascontiguousarray(a, dtype=np.float64).reshape(shape) for a in E]
+    x, y, z = (np.array(a, dtype=np.float64).ravel() for a in (x, y, z))
+    n = x.size
+    wx = np.zeros(n, dtype=np.int32) if wx is None else np.array(wx, dtype=np.int32).ravel()
+    wy = np.zeros(n, dtype=np.int32) if wy is None else np.array(wy, dtype=np.int32).ravel()
+    ids = None if ids is None else np.ascontiguousarray(ids, dtype=np.int32).ravel()
+    if record is None:
+        rec = landings_empty(n)
+    else:
+        rec = tuple(np.array(a, dtype=t).ravel() for a, t in zip(record, (np.int64, np.int32, np.float64, np.float64, np.int32, np.int32)))
+    if not (y.size == z.size == wx.size == wy.size == n) or (ids is not None and ids.size != n) or len(rec) != 6 or any(a.size != n for a in rec):
+        raise ValueError("tracers_advance_absorbing_host: x, y, z, wx, wy, ids and the six record arrays differ in length")
+    rc = L.ekpnp_tracers_advance_absorbing_host(C.byref(p), *[_ptr(a) for a in u], *[None if a is None else _ptr(a) for a in e], n,
+                                                None if ids is None else _ptr(ids), _ptr(x), _ptr(y), _ptr(z), _ptr(wx), _ptr(wy),
+                                                float(mu), float(D), float(h), int(nsub), int(seed), int(epoch), _absorb_walls(walls), *[_ptr(a) for a in rec])
+    if rc:
+        _tracers_fail(L, "ekpnp_tracers_advance_absorbing_host", rc)
+    return (x, y, z, wx, wy, *rec)
+
+
+def landings_bin(e0: int, width: int, nbins: int, epoch):
+    """the cell of an arrival-time histogram: 0 below e0, 1 + (epoch - e0) // width, nbins + 1 from e0 + nbins*width on: THE
+    definition (ekpnp_landings_bin, host only, 64-bit integer arithmetic).  An int for a scalar epoch, else an int64 array."""
+    L = load_library()
+    ep = np.asarray(epoch, dtype=np.int64)
+    out = np.empty(ep.size, dtype=np.int64)
+    for i, v in enumerate(ep.ravel()):
+        out[i] = L.ekpnp_landings_bin(int(e0), int(width), int(nbins), int(v))
+    if L.ekpnp_landings_bin(int(e0), int(width), int(nbins), 0) < 0:
+        _tracers_fail(L, "ekpnp_landings_bin", 1)
+    return int(out[0]) if ep.ndim == 0 else out.reshape(ep.shape)
+
+
 def tracers_cell(p: "Params", cells, x, y, z) -> np.ndarray:
     """the cell (cz*by + cy)*bx + cx of every position in a cells = (bx, by, bz) partition, -1 for a lost particle: THE definition
     (ekpnp_tracers_cell, host only)"""
@@ -1116,6 +1177,16 @@ def load_library():
         "ekpnp_tracers_advance_brownian_host": (i32, [C.POINTER(Params)] + [C.c_void_p] * 6 + [C.c_int64] + [C.c_void_p] * 6 + [dbl, dbl, dbl, i32, C.c_uint64, C.c_int64]),
         "ekpnp_tracers_advance_brownian": (i32, [ctx, dbl, dbl, dbl, i32, C.c_uint64]),
         "ekpnp_tracers_epoch": (i32, [ctx, C.POINTER(C.c_int64)]),
+        # absorbing plates: the advance, the landing record and its reductions and file
+        "ekpnp_tracers_advance_absorbing_host": (i32, [C.POINTER(Params)] + [C.c_void_p] * 6 + [C.c_int64] + [C.c_void_p] * 6 + [dbl, dbl, dbl, i32, C.c_uint64, C.c_int64, i32] + [C.c_void_p] * 6),
+        "ekpnp_tracers_advance_absorbing": (i32, [ctx, dbl, dbl, dbl, i32, C.c_uint64, i32]),
+        "ekpnp_landings_reset": (i32, [ctx]),
+        "ekpnp_landings_get": (i32, [ctx] + [C.c_void_p] * 6),
+        "ekpnp_landings_bin": (i32, [C.c_int64, C.c_int64, i32, C.c_int64]),
+        "ekpnp_landings_hist": (i32, [ctx, i32, C.c_int64, C.c_int64, i32, C.c_void_p, C.POINTER(C.c_int64)]),
+        "ekpnp_landings_map": (i32, [ctx, i32, i32, i32, C.c_int64, C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]),
+        "ekpnp_landings_save": (i32, [ctx, C.c_char_p]),
+        "ekpnp_landings_load": (i32, [ctx, C.c_char_p]),
         "ekpnp_tracers_save": (i32, [ctx, C.c_char_p, dbl]),
         "ekpnp_tracers_load": (i32, [ctx, C.c_char_p, pd]),
         "ekpnp_tracers_cell_counts": (i32, [ctx, i32, i32, i32, C.c_void_p, C.POINTER(C.c_int64)]),
@@ -1491,15 +1562,58 @@ class Solver(_Diagnostics):
     def tracers_release(self):
         self._call("tracers_release")
 
-    def tracers_advance(self, h: float, nsub: int = 1, mu: float = 0.0, D: float = None, seed: int = 0):
+    def tracers_advance(self, h: float, nsub: int = 1, mu: float = 0.0, D: float = None, seed: int = 0, absorb=None):
         """nsub midpoint substeps of h seconds through the current, frozen fields with velocity u + mu E; enqueues only (place it
         between two step() calls).  mu != 0 brings a lazy solve's E arrays up to date first.  With a diffusivity D (m^2/s, 0.0
         allowed) every substep also kicks the particle by the numbers of (seed, its id, the cloud's epoch) and reflects it at the
-        plates (ekpnp_tracers_advance_brownian); D=None is the deterministic advance."""
-        if D is None:
+        plates (ekpnp_tracers_advance_brownian); D=None is the deterministic advance.  absorb="bottom", "top" or "both": those
+        plates keep what reaches them and the first arrival of every particle goes into the landing record (landings_*;
+        ekpnp_tracers_advance_absorbing; D=None then means 0.0: drift alone deposits)."""
+        if absorb is not None:
+            self._call("tracers_advance_absorbing", float(mu), 0.0 if D is None else float(D), float(h), int(nsub), int(seed), _absorb_walls(absorb))
+        elif D is None:
             self._call("tracers_advance", float(mu), float(h), int(nsub))
         else:
             self._call("tracers_advance_brownian", float(mu), float(D), float(h), int(nsub), int(seed))
+
+    def landings_get(self, by_id: bool = True):
+        """(land_epoch, land_wall, land_x, land_y, land_wx, land_wy): the first arrival of every particle at an absorbing plate (-1,
+        0, NaN, NaN, 0, 0: none yet); synchronises.  The record is kept by particle id; by_id=False gives it in slot order, the
+        order of tracers_get()."""
+        n = self.tracers_size
+        rec = (np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int32), np.empty(n, dtype=np.float64), np.empty(n, dtype=np.float64),
+               np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32))
+        self._call("landings_get", *[_ptr(a) for a in rec])
+        if by_id:
+            return rec
+        ids = self.tracers_ids()
+        return tuple(a[ids] for a in rec)
+
+    def landings_hist(self, e0: int = 0, width: int = 1, nbins: int = 1, absorb="both"):
+        """(counts [nbins + 2] int64, none): the landings on the plates of `absorb` per cell of landings_bin(e0, width, nbins, epoch),
+        and everybody else; exact, counts.sum() + none == n"""
+        counts, none = np.zeros(max(int(nbins), 0) + 2, dtype=np.int64), C.c_int64()
+        self._call("landings_hist", _absorb_walls(absorb), int(e0), int(width), int(nbins), _ptr(counts), C.byref(none))
+        return counts, int(none.value)
+
+    def landings_map(self, wall, cells, e_lo: int = 0, e_hi: int = 2 ** 63 - 1):
+        """(counts [by, bx] int64, elsewhere): the landings on one plate ("bottom" / 1 or "top" / 2) with e_lo <= epoch <= e_hi per
+        cell of a cells = (bx, by) partition of the plate, by tracers_cell's rule; exact, counts.sum() + elsewhere == n"""
+        bx, by = (int(b) for b in cells)
+        counts, other = np.zeros((max(by, 0), max(bx, 0)), dtype=np.int64), C.c_int64()
+        self._call("landings_map", _absorb_walls(wall), bx, by, int(e_lo), int(e_hi), _ptr(counts), C.byref(other))
+        return counts, int(other.value)
+
+    def landings_save(self, path: str):
+        self._call("landings_save", os.fsencode(path))
+
+    def landings_load(self, path: str):
+        """after tracers_load of the cloud it belongs to (which drops the record)"""
+        self._call("landings_load", os.fsencode(path))
+
+    def landings_reset(self):
+        """nobody has landed; enqueues only"""
+        self._call("landings_reset")
 
     def tracers_epoch(self) -> int:
         """Brownian substeps taken since the cloud was seeded or set (a load restores the file's): the clock of the noise"""

@@ -828,6 +828,86 @@ int ekpnp_tracers_advance_brownian_host(const ekpnp_params* p, const double* ux,
                                         int32_t* wy, double mu, double D, double h, int nsub, uint64_t seed, int64_t epoch);
 int ekpnp_tracers_advance_brownian(ekpnp_ctx* ctx, double mu, double D, double h, int nsub, uint64_t seed);   /* enqueues only */
 int ekpnp_tracers_epoch(ekpnp_ctx* ctx, int64_t* epoch);
+/* ABSORBING PLATES - the first arrival of a Lagrangian ion at a plate is what a deposition experiment measures: the flux onto an
+ * electrode, the first-passage-time distribution, the deposit under the rolls, the splitting probability between the plates.  A
+ * plain advance HOLDS a particle at a plate, a Brownian one REFLECTS it; the absorbing advance KEEPS it there and writes down where
+ * and when it arrived.  ekpnp_tracers_advance_absorbing_host IS the definition, written operation by operation like its two
+ * siblings, and the device leaves exactly its bits.  The step constants, the draw kick(seed, id, epoch + it) and the midpoint
+ * substep are the Brownian advance's (one function each, shared, not copied).
+ * walls is a mask: 1 - the bottom plate (z = 0) absorbs, 2 - the top plate (z = top = (double)(nz-1)) absorbs, 3 - both.  A plate
+ * outside the mask reflects as in the Brownian advance.  "On an absorbing plate" means (walls & 1) && z <= 0.0 (wall 1), else
+ * (walls & 2) && z >= top (wall 2).
+ * THE LANDING RECORD: six arrays, 36 B per particle, indexed by the particle's ID (what ekpnp_tracers_ids reports; the slot in a
+ * cloud that was never sorted), not by its slot: land_epoch (int64; -1: not landed), land_wall (int32: 0 not landed / 1 / 2),
+ * land_x, land_y (doubles, folded, lattice units; NaN: not landed - on the device all bits set), land_wx, land_wy (int32, the image
+ * counts at the landing; 0).  The ids are a permutation, so exactly one thread ever touches entry id: no atomic, no race; and
+ * ekpnp_tracers_sort does not touch the record.
+ * AN ABSORBING CALL:
+ *  - a lost particle is skipped (step 1 of an advance) and records nothing.
+ *  - a particle that is on an absorbing plate on entry is STUCK: no substep is taken, nothing is drawn, its eight cloud entries
+ *    are not written.  Only if land_epoch[id] < 0 is a landing recorded, with epoch = the call's epoch, the wall it is on, its x, y
+ *    and image counts as they stand; land_epoch[id] is read for such particles only (and at a landing, below).
+ *  - AN ABSORBING SUBSTEP `it` (0 .. nsub-1) of a particle that is neither lost nor stuck:
+ *    (a) the midpoint substep, exactly as (a) of a Brownian substep; a particle lost there is lost.  If the hold of step 6 left it
+ *        on an absorbing plate it has LANDED - drift into the wall, electrophoretic deposition, which works with D == 0.0 - and
+ *        gets no kick.
+ *    (b) the kick and (c) the folds of x and y: as in a Brownian substep.
+ *    (d) z: a NaN or infinite z loses the particle.  if (z < 0.0) z = (the bottom absorbs) ? 0.0 : 0.0 - z;
+ *        if (z > top) { if (the top absorbs) z = top; else { d = z - top; z = top - d; } }  then the hold of step 6; then, if it is
+ *        on an absorbing plate, it has landed.  A particle lost in (c) or (d) is lost, whatever its z.
+ *  - a landing in substep `it` has epoch = (the call's epoch) + it + 1: the number of Brownian substeps the cloud had taken when
+ *    the particle was first found on a plate.  The particle's cloud entries become the landing place - x and y as folded, z
+ *    exactly 0.0 or top, the image counts - and its remaining substeps are not taken.  The record entry is written only if
+ *    land_epoch[id] < 0: it is a FIRST-passage record.
+ *  - a lost particle follows step 7 and records no landing.  The cloud's epoch grows by nsub per call, as for a Brownian advance.
+ * CONSEQUENCES.  Until a particle first touches an absorbing plate its bits are those of ekpnp_tracers_advance_brownian with the
+ * same seed: after a call that starts from particles strictly between the plates, every particle without a landing has the
+ * Brownian advance's eight entries, bit for bit.  Two calls of a and b substeps equal one of a + b, for the cloud and the
+ * record.  A stuck particle stays "alive" to ekpnp_tracers_moments, ekpnp_tracers_cell_counts, ekpnp_tracers_sample,
+ * ekpnp_tracks_* and the sort, all unchanged; a plain or Brownian advance moves it again, while the record keeps the first landing.
+ * Refusals (EKPNP_ERR_INVALID, the message gives the number): those of a Brownian advance; walls outside 1 .. 3; for the host
+ * function also an id outside 0 .. n-1, a record entry with a wall outside 0 .. 2, or with epoch < 0 but wall != 0.
+ * On the device: k_tracers_advance_absorbing, one thread per particle, workgroups of 256, the nsub loop inside, 24 / 48 loads in
+ * flight as in the sibling kernels; no LDS, no atomics, no scratch; the id array is read only when the cloud has one; the six
+ * record stores happen only at a landing (scattered, rare); a wavefront whose particles are all stuck leaves after the position
+ * loads and the look at their entries.  ENQUEUES ONLY; lazy E, the step graph and "batch_moments": as for ekpnp_tracers_advance.
+ * THE RECORD'S LIFE: allocated and cleared by the first absorbing advance (or made by ekpnp_landings_load), counted by
+ * ekpnp_device_bytes, freed by ekpnp_tracers_release and ekpnp_destroy, DROPPED by ekpnp_tracers_seed, _set and _load (a new
+ * cloud has no landings); ekpnp_landings_reset clears it (enqueues only; without a record it does nothing).  A context that never
+ * calls the absorbing advance allocates nothing new and launches nothing new. */
+int ekpnp_tracers_advance_absorbing_host(const ekpnp_params* p, const double* ux, const double* uy, const double* uz, const double* ex, const double* ey,
+                                         const double* ez, int64_t n, const int32_t* ids /* NULL: 0 .. n-1 */, double* x, double* y, double* z, int32_t* wx,
+                                         int32_t* wy, double mu, double D, double h, int nsub, uint64_t seed, int64_t epoch, int walls, int64_t* land_epoch,
+                                         int32_t* land_wall, double* land_x, double* land_y, int32_t* land_wx, int32_t* land_wy);
+int ekpnp_tracers_advance_absorbing(ekpnp_ctx* ctx, double mu, double D, double h, int nsub, uint64_t seed, int walls);   /* enqueues only */
+int ekpnp_landings_reset(ekpnp_ctx* ctx);                                                          /* enqueues only */
+/* READING THE RECORD (synchronous; every count is an integer: exact).  Without a record each is refused: "tracers: no landing
+ * record".  get: the six arrays by id; any pointer may be NULL.
+ * hist - the arrival-time histogram; its running sum is the deposited fraction and n minus that the survival curve, so no ring is
+ * needed.  e0 >= 0, width >= 1, 1 <= nbins <= 4096; counts is [nbins + 2].  The host-only ekpnp_landings_bin IS the definition of
+ * a cell, 64-bit integer arithmetic: 0 for epoch < e0; 1 + (epoch - e0)/width by integer division; nbins + 1 from e0 + nbins*width
+ * on (-1 and a message for arguments hist would refuse).  Only landings whose wall is in the mask `walls` (1 .. 3) count; none is
+ * everybody else: sum(counts) + none == n.
+ * map - the deposition map of one plate (wall 1 or 2): the landings there with e_lo <= epoch <= e_hi, counts [by][bx], the cell
+ * being ekpnp_tracers_cell of (bx, by, 1) at (land_x, land_y, 0.0), the rule the cell counts define; 1 <= bx <= nx, 1 <= by <= ny,
+ * bx*by <= EKPNP_TRACERS_MAX_CELLS; sum(counts) + elsewhere == n.
+ * Both read the record in id order (coalesced, 12 B and 28 B per particle) and count like ekpnp_tracers_cell_counts, into its
+ * table (8 B x 65537, made by whichever of the three comes first): uint32 counters in LDS where the table fits (a histogram
+ * always does; a map of up to 8191 cells), equal cells of a wavefront merged before the atomic, flushed with 64-bit integer
+ * atomics; a larger map counts with 64-bit global integer atomics.  No float atomic anywhere. */
+int ekpnp_landings_get(ekpnp_ctx* ctx, int64_t* epoch, int32_t* wall, double* x, double* y, int32_t* wx, int32_t* wy);
+int ekpnp_landings_bin(int64_t e0, int64_t width, int nbins, int64_t epoch);                       /* host only */
+int ekpnp_landings_hist(ekpnp_ctx* ctx, int walls, int64_t e0, int64_t width, int nbins, int64_t* counts /* [nbins+2] */, int64_t* none);
+int ekpnp_landings_map(ekpnp_ctx* ctx, int wall /* 1 or 2 */, int bx, int by, int64_t e_lo, int64_t e_hi, int64_t* counts /* [by][bx] */, int64_t* elsewhere);
+/* The record's own file (the cloud's file EKPNPTR1 is unchanged), raw little-endian: a 48-byte header {"EKPNPLD1", int32 nx, ny,
+ * nz, reserved = 0, int64 n, int64 landed, int64 epoch} - landed the number of entries with a wall, epoch the cloud's epoch at the
+ * save - then land_epoch as int64 [n], land_x, land_y as FP64 [n], land_wall, land_wx, land_wy as int32 [n]: 48 + 36 n bytes.
+ * load needs a cloud of n particles (it comes after ekpnp_tracers_load, which drops the record) and refuses, each with a message
+ * that gives the number or the first offending id: another lattice or another n, a short file, a non-zero reserved, a wall
+ * outside 0 .. 2, an entry where epoch == -1 and wall == 0 do not go together, an epoch above the header's, a landed that is
+ * not the number of entries with a wall.  Saving both files, loading both and continuing is not having stopped, bit for bit. */
+int ekpnp_landings_save(ekpnp_ctx* ctx, const char* path);
+int ekpnp_landings_load(ekpnp_ctx* ctx, const char* path);
 /* sort ENQUEUES ONLY: it permutes all eight arrays of the cloud (x, y, z, x0, y0, z0, wx, wy) by the perm ekpnp_tracers_sort_host
  * gives for the current positions, and composes the ids: id_new[s] = id_old[perm[s]].  id[s] is the index the particle in slot s
  * had when the cloud was last seeded, set or loaded; seed, set and a load of a file without ids reset the ids to 0 .. n-1.  A
