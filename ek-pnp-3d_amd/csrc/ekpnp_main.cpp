@@ -107,6 +107,10 @@ int main(int argc, char* argv[]) {
   // --tracers-absorb bottom|top|both [--arrivals-bins N] [--deposit-cells bx,by]: the advances are absorbing (ekpnp_tracers_advance_absorbing;
   // D from --tracers-diffusivity, else 0); landings.bin, arrivals.dat and deposit.dat at the end
   int tracers_absorb = 0, arrivals_bins = 0, deposit_cells[2] = {0, 0};
+  // --tracers-stretch [--stretch-levels l_lo,n]: the advances carry the flow-map gradient (ekpnp_tracers_advance_tangent); stretch.bin and,
+  // with --stretch-levels, stretch_levels.dat at the end
+  bool tracers_stretch = false, stretch_levels_given = false;
+  int stretch_levels[2] = {0, 0};
   // --tracks id,id,... / --tracks-first K: tagged particles of that cloud; after every M-th iteration (--tracks-every M, default --tracers-every) a row
   // of x, y, z, wx, wy and the --tracks-values of each goes to a ring (ekpnp_tracks_*); tracks.dat at the end
   bool tracks = false, tracks_flags = false;
@@ -378,6 +382,13 @@ int main(int argc, char* argv[]) {
       tracers_absorb = !std::strcmp(v, "bottom") ? 1 : !std::strcmp(v, "top") ? 2 : !std::strcmp(v, "both") ? 3 : 0;
       if (!tracers_absorb) { std::fprintf(stderr, "--tracers-absorb wants bottom, top or both, got %s\n", v); return 2; }
     }
+    else if (std::strcmp(argv[i], "--tracers-stretch") == 0) tracers_stretch = true;  // (a flag: it takes no value)
+    else if ((v = val("--stretch-levels"))) {
+      int used = 0;
+      if (std::sscanf(v, "%d,%d%n", &stretch_levels[0], &stretch_levels[1], &used) != 2 || v[used]) { std::fprintf(stderr, "--stretch-levels wants l_lo,n, got %s\n", v); return 2; }
+      if (stretch_levels[1] < 1 || stretch_levels[1] > 4096) { std::fprintf(stderr, "--stretch-levels wants 1 .. 4096 levels, got %s\n", v); return 2; }
+      stretch_levels_given = true;
+    }
     else if ((v = val("--arrivals-bins"))) {
       arrivals_bins = std::atoi(v);
       if (arrivals_bins < 1 || arrivals_bins > 4096) { std::fprintf(stderr, "--arrivals-bins wants 1 .. 4096, got %s\n", v); return 2; }
@@ -452,6 +463,7 @@ int main(int argc, char* argv[]) {
                    "                   [--tracers-substeps k] [--tracers-mobility mu] [--tracers-cells bx,by,bz] [--tracers-sort-every K]\n"
                    "                   [--tracers-diffusivity D [--tracers-noise-seed S]]\n"
                    "                   [--tracers-absorb bottom|top|both [--arrivals-bins N] [--deposit-cells bx,by]]\n"
+                   "                   [--tracers-stretch [--stretch-levels l_lo,n]]\n"
                    "                   [--tracks id,id,... | --tracks-first K  [--tracks-values T,q,...] [--tracks-every M]]]\n"
                    "  --tracers N: N particles at random places (--tracers-seed S, default 1) - or --tracers-grid gx,gy,gz: the centres of a\n"
                    "  gx x gy x gz grid - of the box --tracers-box (lattice units; default the interior 0,nx,0,ny,1,nz-2) are advected on the\n"
@@ -475,6 +487,11 @@ int main(int argc, char* argv[]) {
                    "  the end landings.bin (ekpnp_landings_save), arrivals.dat - per wall the histogram of the arrival epochs 0 .. final in\n"
                    "  --arrivals-bins N cells (default 16) - and deposit.dat - both plates' maps in --deposit-cells bx,by cells (default 8,8,\n"
                    "  clipped to the lattice) - are written; the same bytes from both loops.\n"
+                   "  --tracers-stretch (a flag; not with --tracers-diffusivity or --tracers-absorb): the advances also carry every particle's\n"
+                   "  flow-map gradient F * 2^e along (ekpnp_tracers_stretch_begin after the seed, ekpnp_tracers_advance_tangent for every\n"
+                   "  advance; the positions are those of the plain advance, bit for bit).  At the end stretch.bin (ekpnp_tracers_stretch_save) is\n"
+                   "  written, and with --stretch-levels l_lo,n (1 <= n <= 4096) stretch_levels.dat: the particles without a level and the n + 2\n"
+                   "  counts of floor(log2 |F 2^e|^2) below l_lo, at l_lo .. l_lo + n - 1 and above; the same bytes from both loops.\n"
                    "  --tracks id,id,... (at most 1024 particle ids of that cloud, the index a particle has when it is seeded) or --tracks-first K\n"
                    "  (ids 0 .. K-1): after every M-th iteration (--tracks-every, default --tracers-every), after that iteration's advance, a row\n"
                    "  of x, y, z, the image counts and the --tracks-values (names out of the fields and q = c - cn, interpolated at the particle\n"
@@ -618,6 +635,11 @@ int main(int argc, char* argv[]) {
   if (tracers_noise_seed_given && !tracers_brownian) { std::fprintf(stderr, "ekpnp_main: --tracers-noise-seed %llu: there is no noise to seed (give --tracers-diffusivity D)\n", tracers_noise_seed); return 2; }
   if (tracers_brownian && (!std::isfinite(tracers_D) || tracers_D < 0.0)) { std::fprintf(stderr, "ekpnp_main: --tracers-diffusivity: tracers: D = %.17g (must be finite and >= 0)\n", tracers_D); return 2; }
   if ((arrivals_bins || deposit_cells[0]) && !tracers_absorb) { std::fprintf(stderr, "ekpnp_main: --arrivals-bins / --deposit-cells: no plate absorbs (give --tracers-absorb bottom|top|both)\n"); return 2; }
+  if (stretch_levels_given && !tracers_stretch) { std::fprintf(stderr, "ekpnp_main: --stretch-levels: nothing is stretched (give --tracers-stretch)\n"); return 2; }
+  if (tracers_stretch) {
+    if (!tracers) { std::fprintf(stderr, "ekpnp_main: --tracers-stretch: there is no cloud to stretch (give --tracers N or --tracers-grid gx,gy,gz)\n"); return 2; }
+    if (tracers_brownian || tracers_absorb) { std::fprintf(stderr, "ekpnp_main: --tracers-stretch goes with the deterministic advance only, not with --tracers-diffusivity or --tracers-absorb\n"); return 2; }
+  }
   if (tracers_absorb) {
     if (!tracers) { std::fprintf(stderr, "ekpnp_main: --tracers-absorb: there is no cloud to deposit (give --tracers N or --tracers-grid gx,gy,gz)\n"); return 2; }
     if (!arrivals_bins) arrivals_bins = 16;
@@ -712,6 +734,7 @@ int main(int argc, char* argv[]) {
   if (section_every) CK(RUN(section_arm, &section_spec, (int)((nsteps + section_every - 1) / section_every ? (nsteps + section_every - 1) / section_every : 1)));  // a ring that holds the whole run
   if (tracers) {  // the cloud at its start positions and a ring that holds the whole run
     CK(ekpnp_tracers_seed(ctx, &tracers_spec));
+    if (tracers_stretch) CK(ekpnp_tracers_stretch_begin(ctx));
     CK(ekpnp_tracers_arm(ctx, (int)(nsteps / tracers_every ? nsteps / tracers_every : 1)));
     if (tracks) CK(ekpnp_tracks_arm(ctx, &tracks_spec, (int)(nsteps / tracks_every ? nsteps / tracks_every : 1)));
   }
@@ -758,6 +781,7 @@ int main(int argc, char* argv[]) {
       if (tracers_sort_every && ++tracers_advances % tracers_sort_every == 0) CK(ekpnp_tracers_sort(ctx));
       if (tracers_absorb) CK(ekpnp_tracers_advance_absorbing(ctx, tracers_mu, tracers_D, (double)tracers_every * P.dt, tracers_substeps, (uint64_t)tracers_noise_seed, tracers_absorb));
       else if (tracers_brownian) CK(ekpnp_tracers_advance_brownian(ctx, tracers_mu, tracers_D, (double)tracers_every * P.dt, tracers_substeps, (uint64_t)tracers_noise_seed));
+      else if (tracers_stretch) CK(ekpnp_tracers_advance_tangent(ctx, tracers_mu, (double)tracers_every * P.dt, tracers_substeps));
       else CK(ekpnp_tracers_advance(ctx, tracers_mu, (double)tracers_every * P.dt, tracers_substeps));
       CK(ekpnp_tracers_record(ctx, (int64_t)(i + 1), t));
     }
@@ -830,6 +854,23 @@ int main(int argc, char* argv[]) {
         }
       }
       std::fclose(f);
+    }
+    if (tracers_stretch) {
+      CK(ekpnp_tracers_stretch_save(ctx, (out + "/stretch.bin").c_str()));
+      if (stretch_levels_given) {
+        const int l_lo = stretch_levels[0], nlevels = stretch_levels[1];
+        std::vector<int64_t> counts((size_t)nlevels + 2);
+        int64_t none = 0;
+        CK(ekpnp_tracers_stretch_levels(ctx, l_lo, nlevels, counts.data(), &none));
+        FILE* f = std::fopen((out + "/stretch_levels.dat").c_str(), "wb");
+        if (!f) { std::fprintf(stderr, "ekpnp_main: cannot open stretch_levels.dat\n"); ekpnp_destroy(ctx); return 1; }
+        std::fprintf(f, "# ekpnp stretch levels nx %d ny %d nz %d n %lld l_lo %d nlevels %d time %.17g: none, then the nlevels + 2 counts (below, l_lo .., at or above l_lo + nlevels)\n",
+                     nx, ny, nz, (long long)tracers_spec.n, l_lo, nlevels, t);
+        std::fprintf(f, "%lld", (long long)none);
+        for (int64_t v : counts) std::fprintf(f, " %lld", (long long)v);
+        std::fprintf(f, "\n");
+        std::fclose(f);
+      }
     }
     if (tracers_cells[0]) {
       const int bx = tracers_cells[0], by = tracers_cells[1], bz = tracers_cells[2];

@@ -16,6 +16,13 @@
 //                            wall, x, y and the image counts - goes into the landing record, six arrays indexed by the particle's ID,
 //                            so that exactly one thread ever touches an entry: no atomic.  A particle on such a plate at entry takes
 //                            no substep and draws nothing: a wavefront of them leaves after the position loads.
+//   k_tracers_advance_tangent<MOB>   the plain thread per particle (its positions, bit for bit) that also carries the flow-map gradient:
+//                            F[9] and its exponent e, loaded once before the substeps and stored once after them from the stretch
+//                            record ([9][n] doubles, then e: coalesced), F <- J F per substep with J the Jacobian of the midpoint
+//                            substep, formed from the gradient of the interpolant - the SAME 24 / 48 loads, not one more - and
+//                            renormalised by 2^+-64.  M1 = I + a G1 is formed before the second evaluation, so the two gradients are
+//                            never both live.  No LDS, no atomics, no scratch.  k_stretch_begin makes the identity record and
+//                            k_stretch_levels counts floor(log2 |F 2^e|^2) per level as k_landings_hist counts epochs.
 //   k_landings_hist / k_landings_map<LDS>   the arrival-time histogram and the deposit map of a plate: the record read in id order,
 //                            the counting of k_tracers_cells (uint32 counters in LDS, equal cells of a wavefront merged, 64-bit
 //                            integer atomics to flush; a map beyond the LDS table counts with 64-bit global integer atomics)
@@ -25,7 +32,8 @@
 //   k_tracers_partials / k_tracers_finish   the 12 moments, the scheme of stats.hip over particles: runs of 4096 particles per
 //                            workgroup, thread t adds t, t + 256, ... ascending, reduce.h's trees, partial sums in ascending order
 // ekpnp_tracers_advance_host IS the definition of an advance, ekpnp_tracers_advance_brownian_host of a Brownian one,
-// ekpnp_tracers_advance_absorbing_host of an absorbing one (all call tr_midpoint, the midpoint substep; the last two tr_kick) and
+// ekpnp_tracers_advance_absorbing_host of an absorbing one (all call tr_midpoint, the midpoint substep; the last two tr_kick),
+// ekpnp_tracers_advance_tangent_host of a tangent one (tr_midpoint_tangent: tr_midpoint's operations on the positions, and J) and
 // ekpnp_tracers_seed_host of a seed; the device leaves their bits by
 // construction: stencil, interpolation, fold and step are ONE __host__ __device__ function each, the step constants are formed
 // once on the host, and this object is built with -ffp-contract=off (csrc/Makefile, PINNED), so that neither side fuses a
@@ -252,6 +260,167 @@ __host__ __device__ __forceinline__ void tr_advance(const TrFields& f, const TrS
       return;
     }
   }
+}
+
+// ---- the flow-map gradient (include/ekpnp.h: ekpnp_tracers_advance_tangent_host IS the definition) -----------------------------
+// tr_interp's value (its bits) and the three derivatives per cell of the interpolant, from the same eight nodes
+__host__ __device__ __forceinline__ double tr_interp_grad(const double a[8], double fx, double fy, double fz, double g[3]) {
+  const double a00 = tr_lerp(a[0], a[1], fx), a10 = tr_lerp(a[2], a[3], fx);
+  const double a01 = tr_lerp(a[4], a[5], fx), a11 = tr_lerp(a[6], a[7], fx);
+  const double b0 = tr_lerp(a00, a10, fy), b1 = tr_lerp(a01, a11, fy);
+  const double d0 = a[1] - a[0], d1 = a[3] - a[2], d2 = a[5] - a[4], d3 = a[7] - a[6];
+  g[0] = tr_lerp(tr_lerp(d0, d1, fy), tr_lerp(d2, d3, fy), fz);
+  const double e0 = a10 - a00, e1 = a11 - a01;
+  g[1] = tr_lerp(e0, e1, fz);
+  g[2] = b1 - b0;
+  return tr_lerp(b0, b1, fz);
+}
+
+// tr_velocity and beside it G[3c + r] = the derivative of w[c] along r: the stencil once, every load before the first use
+template <bool MOB>
+__host__ __device__ __forceinline__ void tr_velocity_grad(const TrFields& f, const TrStep& s, double x, double y, double z, double w[3], double G[9]) {
+  const TrStencil st = tr_stencil(s.nx, s.ny, s.nz, x, y, z);
+  constexpr int NA = MOB ? 6 : 3;
+  double a[NA][8];
+#pragma unroll
+  for (int q = 0; q < NA; ++q) tr_load8(q < 3 ? f.u[q] : f.e[q - 3], st, a[q]);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    w[c] = tr_interp_grad(a[c], st.fx, st.fy, st.fz, G + 3 * c);
+    if constexpr (MOB) {
+      double ge[3];
+      const double t = s.mu * tr_interp_grad(a[3 + c], st.fx, st.fy, st.fz, ge);
+      w[c] = w[c] + t;
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        const double tg = s.mu * ge[r];
+        G[3 * c + r] = G[3 * c + r] + tg;
+      }
+    }
+  }
+}
+
+// tr_midpoint (its positions, image counts and verdict, operation by operation) and F <- J F, J the Jacobian of the substep.  M1 is
+// formed before the second evaluation: the two gradients are never both live.  false: the particle is lost, F is not written.
+template <bool MOB>
+__host__ __device__ __forceinline__ bool tr_midpoint_tangent(const TrFields& f, const TrStep& s, double px, double py, double top, double& x, double& y, double& z, int& wx,
+                                                             int& wy, double F[9]) {
+  double w[3], G[9], M[9];
+  tr_velocity_grad<MOB>(f, s, x, y, z, w, G);
+  double t = s.ax * w[0];
+  double x1 = x + t;
+  t = s.ay * w[1];
+  double y1 = y + t;
+  t = s.az * w[2];
+  double z1 = z + t;
+  const double a[3] = {s.ax, s.ay, s.az}, h[3] = {s.hx, s.hy, s.hz};
+#pragma unroll
+  for (int q = 0; q < 3; ++q)
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      const double m = a[q] * G[3 * q + r];
+      M[3 * q + r] = q == r ? 1.0 + m : m;
+    }
+  int none = 0;
+  bool ok = tr_fold(x1, px, none);
+  ok = tr_fold(y1, py, none) && ok;
+  ok = tr_fold_z(z1, top) && ok;
+  if (ok) {
+    tr_velocity_grad<MOB>(f, s, x1, y1, z1, w, G);
+    t = s.hx * w[0];
+    x1 = x + t;
+    t = s.hy * w[1];
+    y1 = y + t;
+    t = s.hz * w[2];
+    z1 = z + t;
+    int nwx = wx, nwy = wy;
+    ok = tr_fold(x1, px, nwx);
+    ok = tr_fold(y1, py, nwy) && ok;
+    ok = tr_fold_z(z1, top) && ok;
+    if (ok) {
+      x = x1; y = y1; z = z1; wx = nwx; wy = nwy;
+      double J[9];
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+          const double t0 = G[3 * c] * M[r], t1 = G[3 * c + 1] * M[3 + r], t2 = G[3 * c + 2] * M[6 + r];
+          const double u01 = t0 + t1;
+          const double S = u01 + t2;
+          const double j = h[c] * S;
+          J[3 * c + r] = c == r ? 1.0 + j : j;
+        }
+      double N[9];
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+          const double t0 = J[3 * c] * F[r], t1 = J[3 * c + 1] * F[3 + r], t2 = J[3 * c + 2] * F[6 + r];
+          const double u01 = t0 + t1;
+          N[3 * c + r] = u01 + t2;
+        }
+#pragma unroll
+      for (int q = 0; q < 9; ++q) F[q] = N[q];
+    }
+  }
+  return ok;
+}
+
+// the renormalisation after a substep: the largest |F[q]| kept inside [2^-64, 2^64) by exact multiplications, e counts them
+__host__ __device__ __forceinline__ void tr_renormalise(double F[9], int& e) {
+  double m = 0.0;
+#pragma unroll
+  for (int q = 0; q < 9; ++q) {
+    const double a = F[q] < 0.0 ? 0.0 - F[q] : F[q];
+    if (a > m) m = a;
+  }
+  if (m >= 0x1.0p64) {
+#pragma unroll
+    for (int q = 0; q < 9; ++q) F[q] = F[q] * 0x1.0p-64;
+    e += 64;
+  } else if (m > 0.0 && m < 0x1.0p-64) {
+#pragma unroll
+    for (int q = 0; q < 9; ++q) F[q] = F[q] * 0x1.0p64;
+    e -= 64;
+  }
+}
+
+// nsub tangent substeps of one particle that is not lost on entry
+template <bool MOB>
+__host__ __device__ __forceinline__ void tr_advance_tangent(const TrFields& f, const TrStep& s, double& x, double& y, double& z, int& wx, int& wy, double F[9], int& e) {
+  const double px = (double)s.nx, py = (double)s.ny, top = (double)(s.nz - 1);
+  for (int it = 0; it < s.nsub; ++it) {
+    const bool ok = tr_midpoint_tangent<MOB>(f, s, px, py, top, x, y, z, wx, wy, F);
+    if (!ok) {  // lost: the image counts and e stay what they were
+      x = y = z = NAN;
+#pragma unroll
+      for (int q = 0; q < 9; ++q) F[q] = NAN;
+      return;
+    }
+    tr_renormalise(F, e);
+  }
+}
+
+// the level of a particle (include/ekpnp.h: ekpnp_stretch_level): floor(log2 |F 2^e|^2), the exponent from trC's bit pattern
+constexpr int32_t TR_NO_LEVEL = INT32_MIN;
+__host__ __device__ __forceinline__ int32_t tr_stretch_level(const double F[9], int32_t e) {
+  double trc = F[0] * F[0];
+#pragma unroll
+  for (int q = 1; q < 9; ++q) {
+    const double p = F[q] * F[q];
+    trc = trc + p;
+  }
+  if (trc != trc || trc == 0.0) return TR_NO_LEVEL;
+  int bias = 0;
+  union { double d; uint64_t u; } v;
+  v.d = trc;
+  if (((v.u >> 52) & 0x7ffu) == 0) {  // subnormal: scaled into the normal range, exactly
+    v.d = trc * 0x1.0p54;
+    bias = -54;
+  }
+  const int E = (int)((v.u >> 52) & 0x7ffu) - 1022 + bias;  // trC = f * 2^E, 0.5 <= f < 1
+  const long long l = 2ll * (long long)e + (long long)E - 1ll;
+  return l <= (long long)INT32_MIN ? INT32_MIN + 1 : l > (long long)INT32_MAX ? INT32_MAX : (int32_t)l;
 }
 
 // ---- Brownian substeps (include/ekpnp.h: ekpnp_tracers_advance_brownian_host IS the definition) -------------------------------
@@ -492,6 +661,45 @@ __global__ void __launch_bounds__(TR_THREADS) k_tracers_advance_absorbing(TrFiel
   L.wy[id] = wy;
 }
 
+// the stretch record in slot order: F[q][n] (entry q of the particle in slot i at F[q * n + i]) and e[n]
+struct TrStretch {
+  double* F;
+  int32_t* e;
+};
+
+// F and e are loaded once before the substeps and stored once after them: the loads and stores of a wavefront are coalesced
+template <bool MOB>
+__global__ void __launch_bounds__(TR_THREADS) k_tracers_advance_tangent(TrFields f, TrStep s, TrCloud c, TrStretch r) {
+  const long long i = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
+  if (i >= c.n) return;
+  double x = c.x[i], y = c.y[i], z = c.z[i];
+  if (tr_lost(x, y, z)) return;  // nothing is read, nothing is written
+  int wx = c.wx[i], wy = c.wy[i];
+  double F[9];
+#pragma unroll
+  for (int q = 0; q < 9; ++q) F[q] = r.F[(long long)q * c.n + i];
+  int e = r.e[i];
+  tr_advance_tangent<MOB>(f, s, x, y, z, wx, wy, F, e);
+  c.x[i] = x;
+  c.y[i] = y;
+  c.z[i] = z;
+  c.wx[i] = wx;
+  c.wy[i] = wy;
+#pragma unroll
+  for (int q = 0; q < 9; ++q) r.F[(long long)q * c.n + i] = F[q];
+  r.e[i] = e;
+}
+
+// a new record: F = the identity and e = 0; F = NaN for a particle that is already lost
+__global__ void __launch_bounds__(TR_THREADS) k_stretch_begin(const double* __restrict__ x, const double* __restrict__ y, const double* __restrict__ z, long long n, TrStretch r) {
+  const long long i = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
+  if (i >= n) return;
+  const bool lost = tr_lost(x[i], y[i], z[i]);
+#pragma unroll
+  for (int q = 0; q < 9; ++q) r.F[(long long)q * n + i] = lost ? NAN : (q % 4 == 0 ? 1.0 : 0.0);
+  r.e[i] = 0;
+}
+
 // out[v][i] = value v at the particle in slot i: the stores of a wavefront are coalesced
 __global__ void __launch_bounds__(TR_THREADS) k_tracers_sample(TrSample a, const double* __restrict__ x, const double* __restrict__ y, const double* __restrict__ z,
                                                                long long n, double* __restrict__ out) {
@@ -664,6 +872,44 @@ __global__ void __launch_bounds__(TR_THREADS) k_landings_hist(const int64_t* __r
       const long long i = first + (long long)(k0 + k) * TR_THREADS;
       const bool counted = (w[k] == 1 || w[k] == 2) && (walls & w[k]) && e[k] >= 0;
       int cell = counted ? tr_land_bin(e0, width, nbins, e[k]) : cells;
+      if (i >= n) cell = -1;
+      tr_count_add(tr_cnt, cell);
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i <= cells; i += TR_THREADS) {
+    const unsigned v = tr_cnt[i];
+    if (v) atomicAdd(&total[i], (unsigned long long)v);
+  }
+}
+
+constexpr int TR_LEVEL_BATCH = 4;  // particles of a thread in flight: 36 doubles and 4 int32
+
+// total[cell of the level] += the workgroup's particles: cell 0 below l_lo, 1 + k for level l_lo + k, nlevels + 1 at or above
+// l_lo + nlevels, nlevels + 2 for those without a level.  At most 4099 counters: the table always fits the LDS.  76 B per particle.
+__global__ void __launch_bounds__(TR_THREADS) k_stretch_levels(TrStretch r, long long n, int l_lo, int nlevels, unsigned long long* __restrict__ total) {
+  extern __shared__ unsigned tr_cnt[];
+  const int cells = nlevels + 2;
+  for (int i = threadIdx.x; i <= cells; i += TR_THREADS) tr_cnt[i] = 0u;
+  __syncthreads();
+  const long long first = (long long)blockIdx.x * (TR_THREADS * TR_CELL_PER_THREAD) + threadIdx.x;
+  for (int k0 = 0; k0 < TR_CELL_PER_THREAD; k0 += TR_LEVEL_BATCH) {
+    double F[TR_LEVEL_BATCH][9];
+    int32_t e[TR_LEVEL_BATCH];
+#pragma unroll
+    for (int k = 0; k < TR_LEVEL_BATCH; ++k) {
+      const long long i = first + (long long)(k0 + k) * TR_THREADS;
+      const bool in = i < n;
+#pragma unroll
+      for (int q = 0; q < 9; ++q) F[k][q] = in ? r.F[(long long)q * n + i] : 0.0;
+      e[k] = in ? r.e[i] : 0;
+    }
+#pragma unroll
+    for (int k = 0; k < TR_LEVEL_BATCH; ++k) {
+      const long long i = first + (long long)(k0 + k) * TR_THREADS;
+      const int32_t level = tr_stretch_level(F[k], e[k]);
+      const long long d = (long long)level - (long long)l_lo;
+      int cell = level == TR_NO_LEVEL ? cells : d < 0 ? 0 : d >= (long long)nlevels ? nlevels + 1 : 1 + (int)d;
       if (i >= n) cell = -1;
       tr_count_add(tr_cnt, cell);
     }
@@ -1031,6 +1277,14 @@ struct TracerState {
     int32_t* w = (int32_t*)(d + 2 * m);
     return TrLand{e, d, d + m, w, w + m, w + 2 * m};
   }
+  // the stretch record of the tangent advance, made by ekpnp_tracers_stretch_begin (or a load of its file), dropped like the landing
+  // record: F [9][n] doubles, then e [n] int32, 76 B per particle, in slot order
+  void* stretch = nullptr;
+  size_t stretch_bytes = 0;
+  TrStretch stretch_dev() const {
+    double* F = (double*)stretch;
+    return TrStretch{F, (int32_t*)(F + 9 * (size_t)n)};
+  }
   TrCloud dev() const {
     double* d = (double*)cloud;
     const size_t m = (size_t)n;
@@ -1047,6 +1301,7 @@ static void tracers_sort_release(Ctx& c, TracerState& t) {
   t.has_ids = false;
   if (t.samp) { (void)hipFree(t.samp); c.bytes -= t.samp_bytes; t.samp = nullptr; t.samp_bytes = 0; }  // and so does the sample scratch
   if (t.land) { (void)hipFree(t.land); c.bytes -= t.land_bytes; t.land = nullptr; t.land_bytes = 0; }  // and the landing record
+  if (t.stretch) { (void)hipFree(t.stretch); c.bytes -= t.stretch_bytes; t.stretch = nullptr; t.stretch_bytes = 0; }  // and the stretch record
 }
 
 // a new cloud has no landings (seed, set, load): the stream is waited for, an absorbing advance may still write the record
@@ -1057,6 +1312,17 @@ static int tracers_land_drop(Ctx& c, TracerState& t) {
   c.bytes -= t.land_bytes;
   t.land = nullptr;
   t.land_bytes = 0;
+  return EKPNP_OK;
+}
+
+// nor a stretch record (seed, set, load, ekpnp_tracers_stretch_end): the stream is waited for, a tangent advance may still write it
+static int tracers_stretch_drop(Ctx& c, TracerState& t) {
+  if (!t.stretch) return EKPNP_OK;
+  HIPCHK(c, hipStreamSynchronize(c.stream));
+  (void)hipFree(t.stretch);
+  c.bytes -= t.stretch_bytes;
+  t.stretch = nullptr;
+  t.stretch_bytes = 0;
   return EKPNP_OK;
 }
 
@@ -1314,6 +1580,38 @@ extern "C" int ekpnp_tracers_advance_host(const ekpnp_params* p, const double* u
   return EKPNP_OK;
 }
 
+extern "C" int ekpnp_tracers_advance_tangent_host(const ekpnp_params* p, const double* ux, const double* uy, const double* uz, const double* ex, const double* ey,
+                                                  const double* ez, double mu, double h, int nsub, int64_t n, double* x, double* y, double* z, int32_t* wx, int32_t* wy,
+                                                  double* F, int32_t* e) {
+  std::string err;
+  int rc = EKPNP_ERR_INVALID;
+  if (!p) err = "tracers: NULL parameters";
+  else if ((rc = tracers_check_lattice(*p, err)) == EKPNP_OK && (rc = tracers_check_advance(mu, h, nsub, err)) == EKPNP_OK) {
+    if (n < 0 || n > EKPNP_TRACERS_MAX_N) { err = "tracers: n = " + std::to_string((long long)n) + " outside 0 .. " + std::to_string((long long)EKPNP_TRACERS_MAX_N); rc = EKPNP_ERR_INVALID; }
+    else if (!ux || !uy || !uz || !x || !y || !z || !wx || !wy || !F || !e || (mu != 0.0 && (!ex || !ey || !ez))) { err = "tracers: NULL pointer"; rc = EKPNP_ERR_INVALID; }
+  }
+  if (rc) { set_create_error(err); return rc; }
+  const TrFields f{{ux, uy, uz}, {ex, ey, ez}};
+  const TrStep s = tr_step_of(*p, mu, h, nsub);
+  for (int64_t i = 0; i < n; ++i) {
+    if (tr_lost(x[i], y[i], z[i])) continue;
+    int a = wx[i], b = wy[i], lev = e[i];
+    double Fi[9];
+    for (int q = 0; q < 9; ++q) Fi[q] = F[(size_t)q * (size_t)n + (size_t)i];
+    if (mu != 0.0) tr_advance_tangent<true>(f, s, x[i], y[i], z[i], a, b, Fi, lev);
+    else tr_advance_tangent<false>(f, s, x[i], y[i], z[i], a, b, Fi, lev);
+    wx[i] = a;
+    wy[i] = b;
+    for (int q = 0; q < 9; ++q) F[(size_t)q * (size_t)n + (size_t)i] = Fi[q];
+    e[i] = lev;
+  }
+  return EKPNP_OK;
+}
+
+extern "C" int32_t ekpnp_stretch_level(const double F[9], int32_t e) {
+  return F ? tr_stretch_level(F, e) : TR_NO_LEVEL;
+}
+
 extern "C" void ekpnp_tracers_kick(uint64_t seed, int64_t id, int64_t epoch, double r[3]) {
   if (r) tr_kick(seed, id, epoch, r);
 }
@@ -1533,6 +1831,7 @@ static inline unsigned tr_blocks(long long n, int per) { return (unsigned)((n + 
 static int tracers_upload(Ctx& c, long long n, const double* const pos[6], const int32_t* wx, const int32_t* wy) {
   if (int rc = tracers_alloc(c, n)) return rc;
   if (int rc = tracers_land_drop(c, *c.tracers)) return rc;
+  if (int rc = tracers_stretch_drop(c, *c.tracers)) return rc;
   c.tracers->has_ids = false;  // a new cloud: slot s holds particle s (a load that carries ids puts them back)
   c.tracers->epoch = 0;        // and no Brownian substep was taken (a load puts its file's epoch back)
   c.tracers->tracks.armed = false;  // and the tags of an armed track ring named particles of the old one
@@ -1555,6 +1854,7 @@ extern "C" int ekpnp_tracers_seed(ekpnp_ctx* ctx, const ekpnp_tracers_spec* spec
   if (int rc = tracers_alloc(c, (long long)spec->n)) return rc;
   TracerState& t = *c.tracers;
   if (int rc = tracers_land_drop(c, t)) return rc;
+  if (int rc = tracers_stretch_drop(c, t)) return rc;
   t.has_ids = false;
   t.epoch = 0;
   t.tracks.armed = false;  // the tags named particles of the cloud that is replaced here (the rows stay readable)
@@ -1804,6 +2104,18 @@ extern "C" int ekpnp_tracers_sort(ekpnp_ctx* ctx) {
   hipLaunchKernelGGL((k_tracers_sort_gather<int32_t>), per_particle, block, 0, c.stream, a, t->has_ids ? t->ids : nullptr, tmp, n);
   note_launch(c, "k_tracers_sort_gather");
   HIPCHK(c, hipMemcpyAsync(t->ids, tmp, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, c.stream));
+  if (t->stretch) {  // the stretch record is kept in slot order: its nine F arrays and e go with the particles
+    const TrStretch r = t->stretch_dev();
+    for (int q = 0; q < 9; ++q) {
+      double* const Fq = r.F + (size_t)q * (size_t)n;
+      hipLaunchKernelGGL((k_tracers_sort_gather<double>), per_particle, block, 0, c.stream, a, Fq, (double*)b, n);
+      note_launch(c, "k_tracers_sort_gather");
+      HIPCHK(c, hipMemcpyAsync(Fq, b, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, c.stream));
+    }
+    hipLaunchKernelGGL((k_tracers_sort_gather<int32_t>), per_particle, block, 0, c.stream, a, r.e, tmp, n);
+    note_launch(c, "k_tracers_sort_gather");
+    HIPCHK(c, hipMemcpyAsync(r.e, tmp, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, c.stream));
+  }
   if (take_launch_error(c) != hipSuccess) return EKPNP_ERR_HIP;
   t->has_ids = true;
   return EKPNP_OK;
@@ -2119,6 +2431,155 @@ extern "C" int ekpnp_landings_load(ekpnp_ctx* ctx, const char* path) {
   HIPCHK(c, hipStreamSynchronize(c.stream));  // an absorbing advance may still write the record
   if (int rc = tracers_land_alloc(c, *t, false)) return rc;
   HIPCHK(c, hipMemcpy(t->land, buf.data(), 36 * n, hipMemcpyHostToDevice));
+  return EKPNP_OK;
+}
+
+// ---- the stretch record: begin, end, the tangent advance, get, the histogram of levels, the record's file ----------------------
+
+static inline TracerState* stretch_of(Ctx& c) { return c.tracers && c.tracers->cloud && c.tracers->stretch ? c.tracers : nullptr; }
+constexpr const char* kNoStretchMsg = "tracers: no stretch record (ekpnp_tracers_stretch_begin or ekpnp_tracers_stretch_load makes one)";
+
+static int tracers_stretch_alloc(Ctx& c, TracerState& t) {
+  if (t.stretch) return EKPNP_OK;
+  const size_t bytes = (size_t)t.n * 76;
+  HIPCHK(c, hipMalloc(&t.stretch, bytes));
+  t.stretch_bytes = bytes;
+  c.bytes += bytes;
+  return EKPNP_OK;
+}
+
+extern "C" int ekpnp_tracers_stretch_begin(ekpnp_ctx* ctx) {
+  NEEDSINGLE(ctx);
+  TracerState* t = cloud_of(c);
+  if (!t) return fail(c, "tracers: no cloud (seed, set or load one first)");
+  if (int rc = tracers_stretch_alloc(c, *t)) return rc;
+  const TrCloud d = t->dev();
+  hipLaunchKernelGGL(k_stretch_begin, dim3(tr_blocks(t->n, TR_THREADS)), dim3(TR_THREADS), 0, c.stream, d.x, d.y, d.z, t->n, t->stretch_dev());
+  note_launch(c, "k_stretch_begin");
+  if (take_launch_error(c) != hipSuccess) return EKPNP_ERR_HIP;
+  return EKPNP_OK;
+}
+
+extern "C" int ekpnp_tracers_stretch_end(ekpnp_ctx* ctx) {
+  NEEDSINGLE(ctx);
+  if (!c.tracers) return EKPNP_OK;
+  return tracers_stretch_drop(c, *c.tracers);
+}
+
+extern "C" int ekpnp_tracers_advance_tangent(ekpnp_ctx* ctx, double mu, double h, int nsub) {
+  NEEDSINGLE(ctx);
+  if (int rc = tracers_check_advance(mu, h, nsub, c.err)) return rc;
+  if (!cloud_of(c)) return fail(c, "tracers: no cloud (seed, set or load one first)");
+  TracerState* t = stretch_of(c);
+  if (!t) return fail(c, kNoStretchMsg);
+  const bool mob = mu != 0.0;
+  if (mob)
+    if (int rc = ensure_efield(c)) return rc;  // as ekpnp_tracers_advance (mu == 0: lazy E is left alone)
+  const TrFields f{{c.fld[EKPNP_UX], c.fld[EKPNP_UY], c.fld[EKPNP_UZ]}, {c.fld[EKPNP_EX], c.fld[EKPNP_EY], c.fld[EKPNP_EZ]}};
+  const TrStep s = tr_step_of(c.p, mu, h, nsub);
+  const dim3 grid(tr_blocks(t->n, TR_THREADS)), block(TR_THREADS);
+  if (mob) hipLaunchKernelGGL((k_tracers_advance_tangent<true>), grid, block, 0, c.stream, f, s, t->dev(), t->stretch_dev());
+  else hipLaunchKernelGGL((k_tracers_advance_tangent<false>), grid, block, 0, c.stream, f, s, t->dev(), t->stretch_dev());
+  note_launch(c, "k_tracers_advance_tangent");
+  if (take_launch_error(c) != hipSuccess) return EKPNP_ERR_HIP;
+  return EKPNP_OK;
+}
+
+extern "C" int ekpnp_tracers_stretch_get(ekpnp_ctx* ctx, double* F, int32_t* e) {
+  NEEDSINGLE(ctx);
+  if (!cloud_of(c)) return fail(c, "tracers: no cloud (seed, set or load one first)");
+  TracerState* t = stretch_of(c);
+  if (!t) return fail(c, kNoStretchMsg);
+  const TrStretch r = t->stretch_dev();
+  const size_t n = (size_t)t->n;
+  if (F) HIPCHK(c, hipMemcpyAsync(F, r.F, 9 * n * sizeof(double), hipMemcpyDeviceToHost, c.stream));
+  if (e) HIPCHK(c, hipMemcpyAsync(e, r.e, n * sizeof(int32_t), hipMemcpyDeviceToHost, c.stream));
+  HIPCHK(c, hipStreamSynchronize(c.stream));
+  return EKPNP_OK;
+}
+
+extern "C" int ekpnp_tracers_stretch_levels(ekpnp_ctx* ctx, int l_lo, int nlevels, int64_t* counts, int64_t* none) {
+  NEEDSINGLE(ctx);
+  if (!counts || !none) return fail(c, "NULL pointer");
+  if (nlevels < 1 || nlevels > 4096) { c.err = "tracers: nlevels = " + std::to_string(nlevels) + " outside 1 .. 4096"; return EKPNP_ERR_INVALID; }
+  if (!cloud_of(c)) return fail(c, "tracers: no cloud (seed, set or load one first)");
+  TracerState* t = stretch_of(c);
+  if (!t) return fail(c, kNoStretchMsg);
+  if (int rc = tracers_cells_alloc(c, *t)) return rc;
+  const size_t cells = (size_t)nlevels + 2;
+  HIPCHK(c, hipMemsetAsync(t->cells, 0, (cells + 1) * sizeof(unsigned long long), c.stream));
+  hipLaunchKernelGGL(k_stretch_levels, dim3(tr_blocks(t->n, TR_THREADS * TR_CELL_PER_THREAD)), dim3(TR_THREADS), (cells + 1) * sizeof(unsigned), c.stream, t->stretch_dev(), t->n,
+                     l_lo, nlevels, t->cells);
+  note_launch(c, "k_stretch_levels");
+  if (take_launch_error(c) != hipSuccess) return EKPNP_ERR_HIP;
+  std::vector<int64_t> h(cells + 1);
+  HIPCHK(c, hipMemcpyAsync(h.data(), t->cells, h.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c.stream));
+  HIPCHK(c, hipStreamSynchronize(c.stream));
+  for (size_t k = 0; k < cells; ++k) counts[k] = h[k];
+  *none = h[cells];
+  return EKPNP_OK;
+}
+
+namespace {
+struct StretchHeader {
+  char magic[8];
+  int32_t nx, ny, nz, reserved;
+  int64_t n, reserved2, reserved3;
+};
+static_assert(sizeof(StretchHeader) == 48, "stretch file header layout");
+constexpr char kStretchMagic[9] = "EKPNPSF1";
+}  // namespace
+
+extern "C" int ekpnp_tracers_stretch_save(ekpnp_ctx* ctx, const char* path) {
+  NEEDSINGLE(ctx);
+  if (!path) return fail(c, "NULL path");
+  if (!cloud_of(c)) return fail(c, "tracers: no cloud (seed, set or load one first)");
+  TracerState* t = stretch_of(c);
+  if (!t) return fail(c, kNoStretchMsg);
+  const size_t n = (size_t)t->n;
+  HIPCHK(c, hipStreamSynchronize(c.stream));
+  std::vector<double> buf((76 * n + 7) / 8);  // in memory F comes first, in the file e
+  HIPCHK(c, hipMemcpy(buf.data(), t->stretch, 76 * n, hipMemcpyDeviceToHost));
+  StretchHeader h{};
+  std::memcpy(h.magic, kStretchMagic, 8);
+  h.nx = c.p.nx; h.ny = c.p.ny; h.nz = c.p.nz;
+  h.n = (int64_t)n;
+  FILE* f = std::fopen(path, "wb");
+  if (!f) return fail(c, "cannot open stretch file");
+  const bool ok = std::fwrite(&h, sizeof h, 1, f) == 1 && std::fwrite((const char*)buf.data() + 72 * n, 1, 4 * n, f) == 4 * n && std::fwrite(buf.data(), 1, 72 * n, f) == 72 * n;
+  if (std::fclose(f) != 0 || !ok) return fail(c, "write error on stretch file");
+  return EKPNP_OK;
+}
+
+extern "C" int ekpnp_tracers_stretch_load(ekpnp_ctx* ctx, const char* path) {
+  NEEDSINGLE(ctx);
+  if (!path) return fail(c, "NULL path");
+  TracerState* t = cloud_of(c);
+  if (!t) return fail(c, "tracers: no cloud (seed, set or load one first)");
+  FILE* f = std::fopen(path, "rb");
+  if (!f) return fail(c, "cannot open stretch file");
+  StretchHeader h{};
+  if (std::fread(&h, sizeof h, 1, f) != 1 || std::memcmp(h.magic, kStretchMagic, 8) != 0) { std::fclose(f); return fail(c, "tracers: not a stretch file (EKPNPSF1)"); }
+  if (h.nx != c.p.nx || h.ny != c.p.ny || h.nz != c.p.nz) {
+    std::fclose(f);
+    c.err = "tracers: the file holds a stretch record of lattice " + std::to_string(h.nx) + " x " + std::to_string(h.ny) + " x " + std::to_string(h.nz) + ", not of " +
+            std::to_string(c.p.nx) + " x " + std::to_string(c.p.ny) + " x " + std::to_string(c.p.nz);
+    return EKPNP_ERR_INVALID;
+  }
+  if (h.n != (int64_t)t->n) { std::fclose(f); c.err = "tracers: n = " + std::to_string((long long)h.n) + " in the stretch file, the cloud has " + std::to_string(t->n) + " particles"; return EKPNP_ERR_INVALID; }
+  if (h.reserved != 0 || h.reserved2 != 0 || h.reserved3 != 0) {
+    std::fclose(f);
+    c.err = "tracers: reserved = " + std::to_string(h.reserved) + ", " + std::to_string((long long)h.reserved2) + ", " + std::to_string((long long)h.reserved3) + " in the stretch file (must be 0)";
+    return EKPNP_ERR_INVALID;
+  }
+  const size_t n = (size_t)h.n;
+  std::vector<double> buf((76 * n + 7) / 8);
+  const bool ok = std::fread((char*)buf.data() + 72 * n, 1, 4 * n, f) == 4 * n && std::fread(buf.data(), 1, 72 * n, f) == 72 * n;
+  std::fclose(f);
+  if (!ok) { c.err = "tracers: the stretch file is shorter than its " + std::to_string((long long)h.n) + " entries"; return EKPNP_ERR_INVALID; }
+  HIPCHK(c, hipStreamSynchronize(c.stream));  // a tangent advance may still write the record
+  if (int rc = tracers_stretch_alloc(c, *t)) return rc;
+  HIPCHK(c, hipMemcpy(t->stretch, buf.data(), 76 * n, hipMemcpyHostToDevice));
   return EKPNP_OK;
 }
 

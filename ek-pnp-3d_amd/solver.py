@@ -466,6 +466,63 @@ def tracers_advance_host(p: "Params", u, x, y, z, wx=None, wy=None, E=None, mu: 
     return x, y, z, wx, wy
 
 
+def stretch_identity(x, y, z):
+    """(F [3, 3, n], e [n]) of a record that was just begun: the identity and 0, F = NaN for a lost particle"""
+    x, y, z = (np.asarray(a, dtype=np.float64).ravel() for a in (x, y, z))
+    F = np.zeros((3, 3, x.size), dtype=np.float64)
+    for c in range(3):
+        F[c, c] = 1.0
+    F[:, :, np.isnan(x) | np.isnan(y) | np.isnan(z)] = np.nan
+    return F, np.zeros(x.size, dtype=np.int32)
+
+
+def tracers_advance_tangent_host(p: "Params", u, x, y, z, F=None, e=None, E=None, mu: float = 0.0, h: float = 0.0, nsub: int = 1, wx=None, wy=None):
+    """nsub tangent substeps of h seconds: the positions of tracers_advance_host, bit for bit, and beside them the flow-map gradient
+    F [3, 3, n] (row: component of the end point, column: of the start point, lattice coordinates) with its exponent e [n] int32 -
+    the true gradient is F * 2^e.  F=None, e=None: a record just begun (stretch_identity).  THE definition of a tangent advance
+    (ekpnp_tracers_advance_tangent_host, host only).  Returns new (x, y, z, wx, wy, F, e)."""
+    L = load_library()
+    shape = (p.nz, p.ny, p.nx)
+    u = [np.ascontiguousarray(a, dtype=np.float64).reshape(shape) for a in u]
+    ef = [None] * 3 if E is None else [np.ascontiguousarray(a, dtype=np.float64).reshape(shape) for a in E]
+    x, y, z = (np.array(a, dtype=np.float64).ravel() for a in (x, y, z))
+    n = x.size
+    wx = np.zeros(n, dtype=np.int32) if wx is None else np.array(wx, dtype=np.int32).ravel()
+    wy = np.zeros(n, dtype=np.int32) if wy is None else np.array(wy, dtype=np.int32).ravel()
+    F0, e0 = stretch_identity(x, y, z)
+    F = F0 if F is None else np.array(F, dtype=np.float64)
+    e = e0 if e is None else np.array(e, dtype=np.int32).ravel()
+    if not (y.size == z.size == wx.size == wy.size == e.size == n) or F.size != 9 * n:
+        raise ValueError("tracers_advance_tangent_host: x, y, z, wx, wy, F, e differ in length")
+    F = np.ascontiguousarray(F.reshape(3, 3, n))
+    rc = L.ekpnp_tracers_advance_tangent_host(C.byref(p), *[_ptr(a) for a in u], *[None if a is None else _ptr(a) for a in ef], float(mu), float(h), int(nsub),
+                                              n, _ptr(x), _ptr(y), _ptr(z), _ptr(wx), _ptr(wy), _ptr(F), _ptr(e))
+    if rc:
+        _tracers_fail(L, "ekpnp_tracers_advance_tangent_host", rc)
+    return x, y, z, wx, wy, F, e
+
+
+STRETCH_NO_LEVEL = -2 ** 31  # INT32_MIN: a lost particle, or F = 0
+
+
+def stretch_level(F, e):
+    """floor(log2 of the squared Frobenius norm of F * 2^e) per particle, by integer arithmetic on the bit pattern of the sum of
+    squares (ekpnp_stretch_level, host only): the cell rule of tracers_stretch_levels.  STRETCH_NO_LEVEL for NaN or 0.  F is
+    [3, 3, n], [9, n], [3, 3] or [9]; an int for one particle, else an int32 array."""
+    L = load_library()
+    F = np.asarray(F, dtype=np.float64)
+    one = F.size == 9
+    F = np.array(F.reshape(9, -1).T, dtype=np.float64, order="C")   # [n, 9]: a particle's nine entries side by side
+    e = np.asarray(e, dtype=np.int32).ravel()
+    if e.size != F.shape[0]:
+        raise ValueError("stretch_level: F and e differ in length")
+    out = np.empty(e.size, dtype=np.int32)
+    base = F.ctypes.data
+    for i in range(e.size):
+        out[i] = L.ekpnp_stretch_level(base + 72 * i, int(e[i]))
+    return int(out[0]) if one else out
+
+
 def tracers_kick(seed: int, id: int, epoch: int) -> np.ndarray:
     """r[0..2] in (-1, 1): the draw of particle `id` at substep `epoch` of a Brownian advance - one Philox4x32-10 call, exact in
     FP64 (ekpnp_tracers_kick, host only)"""
@@ -1187,6 +1244,16 @@ def load_library():
         "ekpnp_landings_map": (i32, [ctx, i32, i32, i32, C.c_int64, C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]),
         "ekpnp_landings_save": (i32, [ctx, C.c_char_p]),
         "ekpnp_landings_load": (i32, [ctx, C.c_char_p]),
+        # the flow-map gradient: the tangent advance, the stretch record, its histogram of levels and its file
+        "ekpnp_tracers_advance_tangent_host": (i32, [C.POINTER(Params)] + [C.c_void_p] * 6 + [dbl, dbl, i32, C.c_int64] + [C.c_void_p] * 7),
+        "ekpnp_stretch_level": (i32, [C.c_void_p, i32]),
+        "ekpnp_tracers_stretch_begin": (i32, [ctx]),
+        "ekpnp_tracers_stretch_end": (i32, [ctx]),
+        "ekpnp_tracers_advance_tangent": (i32, [ctx, dbl, dbl, i32]),
+        "ekpnp_tracers_stretch_get": (i32, [ctx, C.c_void_p, C.c_void_p]),
+        "ekpnp_tracers_stretch_levels": (i32, [ctx, i32, i32, C.c_void_p, C.POINTER(C.c_int64)]),
+        "ekpnp_tracers_stretch_save": (i32, [ctx, C.c_char_p]),
+        "ekpnp_tracers_stretch_load": (i32, [ctx, C.c_char_p]),
         "ekpnp_tracers_save": (i32, [ctx, C.c_char_p, dbl]),
         "ekpnp_tracers_load": (i32, [ctx, C.c_char_p, pd]),
         "ekpnp_tracers_cell_counts": (i32, [ctx, i32, i32, i32, C.c_void_p, C.POINTER(C.c_int64)]),
@@ -1562,19 +1629,80 @@ class Solver(_Diagnostics):
     def tracers_release(self):
         self._call("tracers_release")
 
-    def tracers_advance(self, h: float, nsub: int = 1, mu: float = 0.0, D: float = None, seed: int = 0, absorb=None):
+    def tracers_advance(self, h: float, nsub: int = 1, mu: float = 0.0, D: float = None, seed: int = 0, absorb=None, stretch: bool = False):
         """nsub midpoint substeps of h seconds through the current, frozen fields with velocity u + mu E; enqueues only (place it
         between two step() calls).  mu != 0 brings a lazy solve's E arrays up to date first.  With a diffusivity D (m^2/s, 0.0
         allowed) every substep also kicks the particle by the numbers of (seed, its id, the cloud's epoch) and reflects it at the
         plates (ekpnp_tracers_advance_brownian); D=None is the deterministic advance.  absorb="bottom", "top" or "both": those
         plates keep what reaches them and the first arrival of every particle goes into the landing record (landings_*;
-        ekpnp_tracers_advance_absorbing; D=None then means 0.0: drift alone deposits)."""
-        if absorb is not None:
+        ekpnp_tracers_advance_absorbing; D=None then means 0.0: drift alone deposits).  stretch=True: the deterministic advance,
+        which also carries the flow-map gradient of the stretch record along (tracers_stretch_begin first;
+        ekpnp_tracers_advance_tangent); not together with D= or absorb=."""
+        if stretch:
+            if D is not None or absorb is not None:
+                raise ValueError("tracers_advance: stretch=True goes with the deterministic advance only, not with D= or absorb=")
+            self._call("tracers_advance_tangent", float(mu), float(h), int(nsub))
+        elif absorb is not None:
             self._call("tracers_advance_absorbing", float(mu), 0.0 if D is None else float(D), float(h), int(nsub), int(seed), _absorb_walls(absorb))
         elif D is None:
             self._call("tracers_advance", float(mu), float(h), int(nsub))
         else:
             self._call("tracers_advance_brownian", float(mu), float(D), float(h), int(nsub), int(seed))
+
+    def tracers_stretch_begin(self):
+        """make the stretch record of the cloud, or reset it: F = the identity, e = 0 (F = NaN for a lost particle); enqueues only"""
+        self._call("tracers_stretch_begin")
+
+    def tracers_stretch_end(self):
+        """drop the stretch record"""
+        self._call("tracers_stretch_end")
+
+    def tracers_stretch_get(self, by_id: bool = False):
+        """(F [3, 3, n], e [n] int32): the flow-map gradient F * 2^e of every particle over the tangent advances since
+        tracers_stretch_begin, in lattice coordinates (NaN: lost); synchronises.  The record is kept in slot order, the order of
+        tracers_get(); by_id=True: in the original particle order."""
+        n = self.tracers_size
+        F, e = np.empty((3, 3, n), dtype=np.float64), np.empty(n, dtype=np.int32)
+        self._call("tracers_stretch_get", _ptr(F), _ptr(e))
+        if not by_id:
+            return F, e
+        ids = self.tracers_ids()
+        Fo, eo = np.empty_like(F), np.empty_like(e)
+        Fo[:, :, ids] = F
+        eo[ids] = e
+        return Fo, eo
+
+    def tracers_stretch_levels(self, l_lo: int, nlevels: int):
+        """(counts [nlevels + 2] int64, none): the particles per level (stretch_level) below l_lo, at l_lo .. l_lo + nlevels - 1, and
+        at or above l_lo + nlevels, and those without a level (lost, or F = 0); exact, counts.sum() + none == n"""
+        counts, none = np.zeros(max(int(nlevels), 0) + 2, dtype=np.int64), C.c_int64()
+        self._call("tracers_stretch_levels", int(l_lo), int(nlevels), _ptr(counts), C.byref(none))
+        return counts, int(none.value)
+
+    def tracers_stretch_save(self, path: str):
+        self._call("tracers_stretch_save", os.fsencode(path))
+
+    def tracers_stretch_load(self, path: str):
+        """needs a cloud of the file's n (after tracers_load, which drops the record); replaces or creates the record"""
+        self._call("tracers_stretch_load", os.fsencode(path))
+
+    def tracers_ftle(self, T: float, by_id: bool = False):
+        """(ftle [n], det [n]): the finite-time Lyapunov exponent (ln sigma + e ln 2) / |T| of every particle, sigma the largest
+        singular value of D F D^-1 with D = diag(dx, dy, dz) (the gradient in physical coordinates), and det F * 2^(3e), which a
+        solenoidal flow keeps near 1 (the trilinear interpolant of a solenoidal field is not solenoidal: it drifts).  NaN for a
+        lost particle.  Computed in numpy on the fetched record; synchronises."""
+        F, e = self.tracers_stretch_get(by_id=by_id)
+        d = np.array([self.p.dx, self.p.dy, self.p.dz], dtype=np.float64)
+        A = np.moveaxis(F, 2, 0) * (d[:, None] / d[None, :])     # [n, 3, 3]
+        ok = np.isfinite(A).all(axis=(1, 2))
+        sigma = np.full(e.size, np.nan)
+        det = np.full(e.size, np.nan)
+        if ok.any():
+            sigma[ok] = np.linalg.svd(A[ok], compute_uv=False)[:, 0]
+            det[ok] = np.ldexp(np.linalg.det(A[ok]), 3 * e[ok].astype(np.int64))
+        with np.errstate(divide="ignore"):
+            ftle = (np.log(sigma) + e * np.log(2.0)) / abs(float(T))
+        return ftle, det
 
     def landings_get(self, by_id: bool = True):
         """(land_epoch, land_wall, land_x, land_y, land_wx, land_wy): the first arrival of every particle at an absorbing plate (-1,

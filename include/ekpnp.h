@@ -908,6 +908,72 @@ int ekpnp_landings_map(ekpnp_ctx* ctx, int wall /* 1 or 2 */, int bx, int by, in
  * not the number of entries with a wall.  Saving both files, loading both and continuing is not having stopped, bit for bit. */
 int ekpnp_landings_save(ekpnp_ctx* ctx, const char* path);
 int ekpnp_landings_load(ekpnp_ctx* ctx, const char* path);
+/* THE FLOW-MAP GRADIENT - how strongly the flow stretches a material element: what decides mixing in a roll pattern.  Ridges of
+ * the finite-time Lyapunov exponent (FTLE) are the barriers between rolls, its distribution tells algebraic from exponential
+ * stretching.  ekpnp_tracers_advance_tangent_host IS the definition of a tangent advance, written operation by operation like the
+ * three advances before it, and the device leaves exactly its bits.  The gradient of the trilinear interpolant is formed from the
+ * eight nodes per array that an evaluation loads anyway: a tangent advance issues not one load of a field array more than
+ * ekpnp_tracers_advance.
+ * THE STRETCH RECORD: per particle F[9] (doubles) and e (int32), 76 B, IN SLOT ORDER (ekpnp_tracers_sort permutes it with the
+ * cloud).  F is the deformation gradient in LATTICE COORDINATES (cells), row c (the component of the end point) and column r (the
+ * component of the start point) at index 3c + r; the true gradient is F * 2^e.  In memory and in every call: F as [9][n] doubles
+ * (entry q of particle i at F[q*n + i]), then e as [n] int32.
+ * THE GRADIENT OF THE INTERPOLANT, per cell, with L and a00, a10, a01, a11, b0, b1 of step 3 and a0 .. a7 the nodes (k0,j0,i0)
+ * (k0,j0,i1) (k0,j1,i0) (k0,j1,i1) (k1,j0,i0) (k1,j0,i1) (k1,j1,i0) (k1,j1,i1):
+ *     gx = L(L(a1 - a0, a3 - a2, fy), L(a5 - a4, a7 - a6, fy), fz);  gy = L(a10 - a00, a11 - a01, fz);  gz = b1 - b0;
+ *   the value beside it is step 3's, bit for bit.  The gradient of velocity component c along r: G[c][r] = g_r(u_c); if mu != 0.0:
+ *   t = mu*g_r(E_c); G[c][r] = g_r(u_c) + t (the shape of step 4).
+ * A TANGENT SUBSTEP.  The positions, image counts, folds, plate hold and loss rule are steps 1 - 7 above, unchanged, bit for
+ * bit.  G1 is the gradient at the start point, G2 the gradient at the folded midpoint.  EVERY SUM OF THREE TERMS IS ADDED AS
+ * (t0 + t1) + t2, every product rounded once, no fused multiply-add:
+ *     M1[s][r] = a_s*G1[s][r], and on the diagonal M1[s][s] = 1.0 + a_s*G1[s][s]                 (a_s: ax, ay, az)
+ *     S[c][r]  = (G2[c][0]*M1[0][r] + G2[c][1]*M1[1][r]) + G2[c][2]*M1[2][r]
+ *     J[c][r]  = h_c*S[c][r], and on the diagonal J[c][c] = 1.0 + h_c*S[c][c]                    (h_c: hx, hy, hz)
+ *     F'[c][r] = (J[c][0]*F[0][r] + J[c][1]*F[1][r]) + J[c][2]*F[2][r];  F = F'
+ *   J is the Jacobian of the discrete substep itself, so F is the derivative of the advance's own map (not of the flow the
+ *   advance approximates).  A periodic fold is a translation and does not change J.  THE PLATE HOLD (the z clamp of step 6) IS
+ *   IGNORED IN J: a particle held by a plate keeps the J of the unclamped map.  A particle lost in the substep gets F = NaN in all
+ *   nine entries and keeps its e; a particle lost on entry is skipped: its F and e are neither read nor written.
+ * RENORMALISATION, after every substep of a particle that was not lost in it: m = 0.0; for q = 0 .. 8: a = |F[q]|; if (a > m)
+ *   m = a.  If m >= 2^64: every F[q] = F[q]*2^-64 and e = e + 64; else if 0 < m < 2^-64: every F[q] = F[q]*2^64 and e = e - 64
+ *   (exact multiplications; both directions occur in a compressible field).
+ * THE LEVEL OF A PARTICLE, ekpnp_stretch_level (host only; the cell rule of the histogram below): trC = the sum of F[q]*F[q],
+ *   q = 0 .. 8 added in index order; the level is 2e + E - 1 with trC = f * 2^E, 0.5 <= f < 1, E taken from the BIT PATTERN of
+ *   trC (no log; a subnormal trC is scaled by 2^54 first; an infinite trC has E = 1025): floor(log2 of the squared Frobenius norm
+ *   of F * 2^e).  INT32_MIN when trC is NaN or 0: a lost particle, or F = 0.
+ * On the device: k_tracers_advance_tangent<MOB>, one thread per particle, workgroups of 256, the nsub loop inside; F and e are
+ * loaded once before the loop and stored once after it, coalesced from the [9][n] layout; the 24 (48) loads of an evaluation are
+ * issued before the first use, every index clamped before any load; M1 is formed before the second evaluation, so that G1 and
+ * G2 are never both live; no LDS, no atomics, no scratch.  The functions are those of the host.
+ * THE CALLS.  ekpnp_tracers_stretch_begin ENQUEUES ONLY: it makes the record (76 B per particle, counted by ekpnp_device_bytes)
+ * or resets it: F = the identity and e = 0, F = NaN for a particle that is already lost.  ekpnp_tracers_stretch_end drops it.
+ * ekpnp_tracers_advance_tangent ENQUEUES ONLY; the argument checks, lazy E, the step graph and "batch_moments": as for
+ * ekpnp_tracers_advance; without a record it is refused: "tracers: no stretch record (ekpnp_tracers_stretch_begin or
+ * ekpnp_tracers_stretch_load makes one)", and so are _get, _levels and _save.  The record is dropped (the stream is waited for
+ * first) by ekpnp_tracers_seed, _set, _load and _release, like the landing record.  ekpnp_tracers_advance, _advance_brownian and
+ * _advance_absorbing are allowed while a record exists and leave it untouched: F THEN COVERS THE TANGENT ADVANCES ONLY (a
+ * Brownian tangent advance does not exist).  ekpnp_tracers_sort permutes the nine F arrays and e through its slot list when a
+ * record exists; a cloud without one launches exactly what it always launched.
+ * ekpnp_tracers_stretch_levels (synchronous, exact): counts[0] the particles with a level below l_lo, counts[1 + k] those of level
+ * l_lo + k (0 <= k < nlevels; 1 <= nlevels <= 4096, so the table always fits the LDS), counts[nlevels + 1] those at or above
+ * l_lo + nlevels, *none those whose level is INT32_MIN.  uint32 counters in LDS, equal cells of a wavefront merged first, flushed
+ * with 64-bit integer atomics (the scheme of ekpnp_landings_hist).  It is the PDF of 2*log2 of the stretching in half-octave
+ * steps: its mean times ln2/(2T) is the mean FTLE in lattice coordinates to within +-0.17/T.
+ * The record's own file (the cloud's file is unchanged), raw little-endian: a 48-byte header {"EKPNPSF1", int32 nx, ny, nz,
+ * reserved = 0, int64 n, int64 reserved2 = 0, int64 reserved3 = 0}, then e as int32 [n], then F as FP64 [9][n], in slot order:
+ * 48 + 76 n bytes.  load needs a cloud of the same n and replaces or creates the record; it refuses another lattice or another
+ * n, a short file, a non-zero reserved word.  Saving both files, loading both and continuing is not having stopped, bit for bit. */
+int ekpnp_tracers_advance_tangent_host(const ekpnp_params* p, const double* ux, const double* uy, const double* uz, const double* ex, const double* ey,
+                                       const double* ez, double mu, double h, int nsub, int64_t n, double* x, double* y, double* z, int32_t* wx, int32_t* wy,
+                                       double* F /* [9][n] */, int32_t* e);
+int32_t ekpnp_stretch_level(const double F[9], int32_t e);                                         /* host only */
+int ekpnp_tracers_stretch_begin(ekpnp_ctx* ctx);                                                   /* enqueues only */
+int ekpnp_tracers_stretch_end(ekpnp_ctx* ctx);
+int ekpnp_tracers_advance_tangent(ekpnp_ctx* ctx, double mu, double h, int nsub);                  /* enqueues only */
+int ekpnp_tracers_stretch_get(ekpnp_ctx* ctx, double* F /* [9][n] */, int32_t* e);
+int ekpnp_tracers_stretch_levels(ekpnp_ctx* ctx, int l_lo, int nlevels, int64_t* counts /* [nlevels+2] */, int64_t* none);
+int ekpnp_tracers_stretch_save(ekpnp_ctx* ctx, const char* path);
+int ekpnp_tracers_stretch_load(ekpnp_ctx* ctx, const char* path);
 /* sort ENQUEUES ONLY: it permutes all eight arrays of the cloud (x, y, z, x0, y0, z0, wx, wy) by the perm ekpnp_tracers_sort_host
  * gives for the current positions, and composes the ids: id_new[s] = id_old[perm[s]].  id[s] is the index the particle in slot s
  * had when the cloud was last seeded, set or loaded; seed, set and a load of a file without ids reset the ids to 0 .. n-1.  A
